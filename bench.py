@@ -19,6 +19,7 @@ whose tail -> matcher -> warp -> head chain is longer than one forward).
     python bench.py                                   # 1 GPU, configs[1]
     python bench.py --gpus 8                          # spawns 8 ranks itself (one per GPU, RCCL)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --steps K --dump-outputs DIR      # + the last timed step's poses / status as DIR/*.npy (seeded inputs: comparable across builds)
 
 Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
 "roofline" (dominant kernel = the MFMA implicit-GEMM conv, live HIP-event timing),
@@ -117,7 +118,18 @@ def parse_args(argv=None):
                          "level derives its keypoints from its own feature maps like rputil.getKeypoint (synthetic SIFT detections given once; "
                          "descriptor gather + fused distance-map / NMS + random fill on the device INSIDE the timed region) -- reported beside the headline")
     ap.add_argument("--sift", type=int, default=120, help="--keypoint-mode reference: synthetic SIFT detections per view (+ <= 60 / <= 90 derived ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (pose.npy [pairs,4,4] float64, status.npy [pairs] float64; "
+                         "all pairs of the job, rank 0) to DIR.  The inputs are seeded, so two builds run with the same arguments can be compared "
+                         "output for output; the last step runs prepared batch (steps - 1) %% batches, so the dump depends on --steps")
     return ap.parse_args(argv)
+
+
+def dump_outputs(path, poses, status):
+    """The arrays the timed path hands its caller for the last timed step, as float64 .npy files (136 bytes per pair)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "pose.npy"), poses.detach().cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "status.npy"), status.detach().cpu().numpy().astype(np.float64))
 
 
 def cpu_baseline(cfg, N, data, pts, ptw, sigmas):
@@ -414,6 +426,8 @@ def worker(args):
     ncoll0 = D.COLLECTIVES["all_gather"]
     dt, (poses, status) = timed(args.steps)
     ncoll = D.COLLECTIVES["all_gather"] - ncoll0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, poses, status)
     dt_h2d = None
     if not args.no_h2d:
         run_steps(1, True)
@@ -592,11 +606,13 @@ def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched plainly (python bench.py --gpus N): spawn the N ranks here, one per GPU, RCCL over xGMI
-        import torch
-        have = torch.cuda.device_count()
-        if have < args.gpus and not os.environ.get("RELPOSE_FORCE_DEVICE"):
-            print(f"bench.py: --gpus {args.gpus} requested but only {have} GPU(s) visible; refusing to fall back", file=sys.stderr)
-            raise SystemExit(2)
+        # (counting the devices initialises HIP in this process; under the one-device test hook the parent leaves the GPU to its ranks)
+        if not os.environ.get("RELPOSE_FORCE_DEVICE"):
+            import torch
+            have = torch.cuda.device_count()
+            if have < args.gpus:
+                print(f"bench.py: --gpus {args.gpus} requested but only {have} GPU(s) visible; refusing to fall back", file=sys.stderr)
+                raise SystemExit(2)
         import torch.multiprocessing as mp
         for attempt in range(3):             # a free port can be taken between the probe and the rendezvous: retry with another one
             s = socket.socket()
