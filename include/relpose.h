@@ -18,7 +18,7 @@
  *    workspaces whose size is returned by the *_workspace_bytes functions;
  *  - all work is enqueued on `stream` (a hipStream_t passed as void*; NULL = the
  *    default stream); apart from the first-forward plan build and
- *    relpose_scnet_finalize / relpose_scnet_profile no entry point synchronises;
+ *    relpose_scnet_finalize / relpose_scnet_profile / relpose_sift_detect (its overflow flag) no entry point synchronises;
  *  - return value: 0 = enqueued, <0 = invalid argument (RELPOSE_EINVAL) or HIP
  *    error (-(1000+hipError_t)).  Per-pair degenerate inputs are NOT errors: the
  *    reference returns identity for them (rpmodule.py:346-348,377-379,406-408,
@@ -275,6 +275,48 @@ int relpose_keypoints_reference(const float* f, int64_t image_stride, int32_t fe
                                 int32_t nq_view_max, int32_t topk, int32_t window, const int32_t* slot_kind, const double* slot_xy, int32_t L,
                                 int32_t mask_method, int32_t flags, double* pts, double* weight, int32_t* npts, void* workspace, size_t workspace_bytes,
                                 void* stream);
+
+/* ------------------------------------------------------------------ SIFT detector
+ * The keypoint detector every recurrent level of the reference starts from: cv2.xfeatures2d.SIFT_create(contrastThreshold=0.02)
+ * .detectAndCompute on the observed face (SUNCG / Matterport, rputil.py:152-172) or on the 640x480 frame (ScanNet, :253-265); only the
+ * positions kp.pt are used.  Lowe's scale space with the reference's parameters (3 layers per octave, contrast 0.02, edge 10, sigma 1.6,
+ * image doubled first), batched over views; the detection contract (blur, refinement, orientations, output order) is DESIGN.md's
+ * "SIFT detector" section.  Descriptors are not computed (the reference discards them).
+ *   images       uint8, channels == 3: [n_views, img_h, img_w, 3] in cv2's BGR order (channel 0 weighted as B, cv2.COLOR_BGR2GRAY's
+ *                14-bit fixed-point weights, rputil.bgr2gray); channels == 1: gray [n_views, img_h, img_w]
+ *   crop_*       the rectangle the detector sees (like grays[:, H:2H]); coordinates come back in that rectangle's frame, like kp.pt;
+ *                16 <= crop_w, crop_h <= RELPOSE_SIFT_MAX_SIDE
+ *   xy           [n_views, max_kp, 2] f32 positions, per view sorted by (x, y, size desc, angle, response desc), exact
+ *                (x, y, size, angle) duplicates removed; a position repeats once per dominant orientation, like cv2
+ *   size, angle  optional (NULL) [n_views, max_kp] f32: the keypoint diameter and orientation in degrees [0, 360)
+ *   gray         optional (NULL) [n_views, crop_h, crop_w] uint8: the crop converted to gray (what the detector sees)
+ *   count        [n_views] i32: keypoints found per view
+ * Overflow: when a view has more than max_kp keypoints, count holds the true total, nothing is written past max_kp and the call returns
+ * RELPOSE_SIFT_OVERFLOW.  The per-view intermediate lists hold relpose_sift_stage_capacity(max_kp) entries; if one of them fills up, the
+ * call also returns RELPOSE_SIFT_OVERFLOW and count is then a lower bound.
+ * This entry point SYNCHRONISES `stream` once at its end (to read the overflow flag).  The number of kernel launches does not depend on
+ * n_views.  workspace: relpose_sift_workspace_bytes(n_views, crop_h, crop_w, max_kp) (0 for invalid sizes). */
+#define RELPOSE_SIFT_OVERFLOW (-3)
+#define RELPOSE_SIFT_MAX_SIDE 2048
+typedef struct RelposeSiftArgs {
+    uint32_t struct_size;       /* sizeof(RelposeSiftArgs) as the caller compiled it */
+    int32_t n_views;
+    const uint8_t* images;
+    int32_t img_h, img_w, channels;
+    int32_t crop_x, crop_y, crop_w, crop_h;
+    int32_t max_kp;
+    float* xy;
+    float* size;
+    float* angle;
+    uint8_t* gray;
+    int32_t* count;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeSiftArgs;
+size_t relpose_sift_workspace_bytes(int32_t n_views, int32_t h, int32_t w, int32_t max_kp);
+int32_t relpose_sift_stage_capacity(int32_t max_kp);
+int relpose_sift_detect(const RelposeSiftArgs* args);
 
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs

@@ -51,6 +51,18 @@ class MatchArgs(C.Structure):
                 ("debug_host", C.POINTER(MatchDebug)), ("stream", c_void_p), ("affinity_kernel", c_int), ("reserved0", c_int)]
 
 
+class SiftArgs(C.Structure):
+    """RelposeSiftArgs (include/relpose.h): the argument block of relpose_sift_detect."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_views", c_int), ("images", c_void_p), ("img_h", c_int), ("img_w", c_int), ("channels", c_int),
+                ("crop_x", c_int), ("crop_y", c_int), ("crop_w", c_int), ("crop_h", c_int), ("max_kp", c_int), ("xy", c_void_p), ("size", c_void_p),
+                ("angle", c_void_p), ("gray", c_void_p), ("count", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("stream", c_void_p)]
+
+
+SIFT_OVERFLOW = -3                  # include/relpose.h RELPOSE_SIFT_OVERFLOW
+SIFT_MAX_SIDE = 2048                # RELPOSE_SIFT_MAX_SIDE
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -82,6 +94,9 @@ SIGNATURES = {
     "relpose_keypoints_reference_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "relpose_keypoints_reference": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                             c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "relpose_sift_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "relpose_sift_stage_capacity": (c_int, [c_int]),
+    "relpose_sift_detect": (c_int, [C.POINTER(SiftArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

@@ -88,7 +88,8 @@ def _prepare_batch(pipe, batch, device):
     (rputil.map_detections of the SIFT detector's output, rputil.py:152-172) and optionally "kp_seeds" [B][levels]: every level then derives
     its keypoints from its own feature maps, as evaluation.py:278 does through getMatchingPrimitive."""
     if getattr(pipe, "keypoints", "given") == "reference":
-        return pipe.prepare(batch["rgb"], batch["norm"], batch["depth"], None, None, device, sift=batch["sift"], kp_seeds=batch.get("kp_seeds"))
+        return pipe.prepare(batch["rgb"], batch["norm"], batch["depth"], None, None, device, sift=batch["sift"], kp_seeds=batch.get("kp_seeds"),
+                            rgb_full=batch.get("rgb_full"))
     return pipe.prepare(batch["rgb"], batch["norm"], batch["depth"], batch["pts"], batch["ptw"], device)
 
 
@@ -125,9 +126,11 @@ class SyntheticBatch:
     seed + b) that materialises only the pairs a rank asks for -- evaluate_pairs_sharded hands every rank the same batch list, and a rank
     should not render the other ranks' panoramas."""
 
-    def __init__(self, size, seed, dataset, mask_method, keypoints, h=160, sift=0):
+    def __init__(self, size, seed, dataset, mask_method, keypoints, h=160, sift=0, sift_detector="synthetic"):
         self.size, self.seed, self.dataset, self.mask_method, self.keypoints, self.h = size, seed, dataset, mask_method, keypoints, h
         self.sift = int(sift)           # > 0: also `sift` synthetic SIFT detections per view (for RelativePosePipeline(keypoints="reference"))
+        # "gpu": no synthetic detections; the pipeline runs the HIP SIFT detector on the rendered views (prepare(sift="detect"))
+        self.sift_detector = sift_detector
 
     def take(self, idx):
         from . import synth
@@ -137,7 +140,12 @@ class SyntheticBatch:
         kps = [synth.make_keypoints(1, self.keypoints, 7919 * (self.seed + int(b)) + 13, self.mask_method, h=self.h) for b in idx]
         out = {k: np.concatenate([p[k] for p in parts]) for k in ("rgb", "norm", "depth", "R")}
         out["pts"], out["ptw"] = np.concatenate([k[0] for k in kps]), np.concatenate([k[1] for k in kps])
-        if self.sift:
+        if self.sift and self.sift_detector == "gpu":
+            out["sift"] = "detect"
+            if self.mask_method == "kinect":
+                out["rgb_full"] = synth.kinect_frames(out["rgb"], self.h)
+            out["kp_seeds"] = [[31 * (self.seed + int(b)) + lvl for lvl in range(8)] for b in idx]
+        elif self.sift:
             from . import rputil
             dets = [synth.make_sift_detections(1, self.sift, 15485863 * (self.seed + int(b)) + 7, self.mask_method, self.h)[0] for b in idx]
             out["sift"] = [(rputil.map_detections(a, self.mask_method, self.h), rputil.map_detections(c, self.mask_method, self.h)) for a, c in dets]
@@ -155,7 +163,9 @@ def _batch_take(batch, idx):
         return batch.take(idx)
     out = {k: v[idx] for k, v in batch.items() if isinstance(v, np.ndarray)}
     for k in ("sift", "kp_seeds"):                        # per-pair lists (keypoints="reference")
-        if k in batch:
+        if k in batch and isinstance(batch[k], str):      # sift="detect": the pipeline detects on the batch's own views
+            out[k] = batch[k]
+        elif k in batch:
             out[k] = [batch[k][int(i)] for i in idx]
     return out
 
@@ -326,6 +336,9 @@ def main(argv=None):
     ap.add_argument("--keypoint-mode", choices=["given", "reference"], default="given",
                     help="reference: every level derives its keypoints from its own feature maps like rputil.getKeypoint (synthetic SIFT detections)")
     ap.add_argument("--sift", type=int, default=120, help="--keypoint-mode reference: synthetic SIFT detections per view")
+    ap.add_argument("--sift-detector", choices=["synthetic", "gpu"], default="synthetic",
+                    help="--keypoint-mode reference: synthetic = uniform random detections (synth.make_sift_detections), gpu = the HIP SIFT "
+                         "detector on the rendered views (rputil.sift_views)")
     ap.add_argument("--precision", choices=["f32", "bf16x9", "bf16x6", "f16x3", "bf16x3", "f16"], default="f32",
                     help="conv arithmetic of SCNet (SCNet.set_precision): f32 = the fp32 MFMA kernels (default), bf16x6 = what bench.py runs configs 1-3 in")
     ap.add_argument("--completion", type=int, default=1, choices=[0, 1], help="0 = the reference's 'ours_nc' method (evaluation.py:74): observed-region keypoints only")
@@ -349,7 +362,8 @@ def main(argv=None):
         net.set_precision(args.precision)
         pipe = RelativePosePipeline(net, ds, mm, params.final_params(ds), keypoints=args.keypoint_mode, completion=args.completion)
         batches = [SyntheticBatch(min(args.batch, args.pairs - k), args.seed + k, ds, mm, args.keypoints,
-                                  sift=args.sift if args.keypoint_mode == "reference" else 0) for k in range(0, args.pairs, args.batch)]
+                                  sift=args.sift if args.keypoint_mode == "reference" else 0, sift_detector=args.sift_detector)
+                   for k in range(0, args.pairs, args.batch)]
         path = None if args.exp is None else args.exp + ".result.npy"
         D.barrier(world)
         t0 = time.perf_counter()

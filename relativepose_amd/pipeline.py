@@ -60,16 +60,24 @@ class RelativePosePipeline:
         # one process with different settings do not interfere (round 5 set a process-wide knob around the loop here).
         self.loop_fit_cluster = int(loop_fit_cluster)
 
-    def prepare(self, rgb, norm, depth, pts, ptw, device, keep_host=False, sift=None, kp_seeds=None):
+    def prepare(self, rgb, norm, depth, pts, ptw, device, keep_host=False, sift=None, kp_seeds=None, rgb_full=None):
         """Host arrays (dataset dict layout: rgb/norm [B,2,3,h,4h], depth [B,2,h,4h] f32; pts [B,2,N,2],
         ptw [B,2,N] f64) -> device-resident state.  Not part of the timed region.
         keypoints="reference": pts / ptw are ignored (None); sift = [(source detections [n,2], target detections [m,2])] * B in panorama
         coordinates (rputil.map_detections), kp_seeds [B][alter_steps] = the np.random seed of pair b's getKeypoint call at each level
-        (default: 7919 * b + level)."""
+        (default: 7919 * b + level).  sift="detect": the detections come from the HIP SIFT detector run on the batch's own views
+        (rputil.sift_views: the observed face of `rgb` for 'second'; the 640x480 frames rgb_full [B,2,3,480,640] for 'kinect')."""
         import torch
         B, _, _, h, w = rgb.shape
         if self.keypoints == "reference":
+            if isinstance(sift, str):
+                if sift != "detect":
+                    raise ValueError("prepare(sift=...) takes per-pair detections or 'detect'")
+                from . import rputil
+                sift = rputil.sift_views(rgb, self.mask_method, rgb_full)
             return self._prepare_reference(rgb, norm, depth, device, keep_host, sift, kp_seeds)
+        if isinstance(sift, str):
+            raise ValueError("prepare(sift='detect') needs RelativePosePipeline(keypoints='reference')")
         pts = np.asarray(pts, dtype=np.float64)
         ptw = np.asarray(ptw, dtype=np.float64)
         N = pts.shape[2]

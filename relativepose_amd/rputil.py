@@ -15,7 +15,10 @@
                                    runs at every recurrent level
 
 SIFT detection itself (cv2.xfeatures2d, third-party) is a hook: set_sift_detector(fn), fn(gray uint8 [h,w]) -> [[x, y], ...]; when
-cv2 with xfeatures2d is importable it is the default."""
+cv2 with xfeatures2d is importable it is the default.  The project's own detector (csrc/sift.hip, batched over views) is
+sift_detect_dev; gpu_sift_detector is a ready-made hook around it: set_sift_detector(rputil.gpu_sift_detector)."""
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
@@ -122,6 +125,94 @@ def _detect(gray):
                            "available); install one with rputil.set_sift_detector(fn)") from e
     kps, _ = sift.detectAndCompute(gray, None)
     return np.array([k.pt for k in kps], dtype=np.float64).reshape(-1, 2)
+
+
+SIFT_MAX_KP = 32768                # default per-view capacity of sift_detect_dev / gpu_sift_detector
+
+
+def sift_detect_tensors(images, crop=None, max_kp=SIFT_MAX_KP, want_size=False, want_angle=False, want_gray=False, check=True):
+    """The batched SIFT detector (relpose_sift_detect, csrc/sift.hip) on device tensors.
+    images: uint8 [V, h, w, 3] in cv2's BGR order (channel 0 weighted as B) or gray [V, h, w]; numpy arrays are uploaded.
+    crop: (x0, y0, width, height) of the rectangle the detector sees (None = the whole image); coordinates come back in its frame.
+    Returns {"xy": [V, max_kp, 2] f32, "count": [V] i32, "rc": the return code, and "size" / "angle" [V, max_kp] f32, "gray" [V, ch, cw] u8
+    when asked for}.  check=True raises on RELPOSE_SIFT_OVERFLOW (a view with more than max_kp keypoints); check=False returns the code."""
+    import torch
+    dev = _lib.require_gpu()
+    if isinstance(images, np.ndarray):
+        images = torch.from_numpy(np.ascontiguousarray(images))
+    if images.dtype != torch.uint8 or images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[3] != 3):
+        raise ValueError("sift_detect: images must be uint8 [V, h, w, 3] (BGR) or [V, h, w] (gray)")
+    images = images.to(dev).contiguous()
+    V, ih, iw = images.shape[:3]
+    ch = 3 if images.dim() == 4 else 1
+    x0, y0, cw, chh = (0, 0, iw, ih) if crop is None else (int(c) for c in crop)
+    nb = _lib.lib().relpose_sift_workspace_bytes(V, chh, cw, int(max_kp))
+    if nb == 0:
+        raise ValueError(f"sift_detect: unsupported crop {cw}x{chh} / max_kp {max_kp} (16 <= side <= {_lib.SIFT_MAX_SIDE})")
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    out = {"xy": torch.empty(V, int(max_kp), 2, dtype=torch.float32, device=dev), "count": torch.empty(V, dtype=torch.int32, device=dev)}
+    if want_size:
+        out["size"] = torch.empty(V, int(max_kp), dtype=torch.float32, device=dev)
+    if want_angle:
+        out["angle"] = torch.empty(V, int(max_kp), dtype=torch.float32, device=dev)
+    if want_gray:
+        out["gray"] = torch.empty(V, chh, cw, dtype=torch.uint8, device=dev)
+    a = _lib.SiftArgs(C.sizeof(_lib.SiftArgs), V, images.data_ptr(), ih, iw, ch, x0, y0, cw, chh, int(max_kp), out["xy"].data_ptr(),
+                      _lib.ptr(out.get("size")).value, _lib.ptr(out.get("angle")).value, _lib.ptr(out.get("gray")).value, out["count"].data_ptr(),
+                      ws.data_ptr(), nb, _lib.stream_ptr().value)
+    rc = _lib.lib().relpose_sift_detect(C.byref(a))
+    out["rc"] = rc
+    if rc == _lib.SIFT_OVERFLOW:
+        if check:
+            raise RuntimeError(f"relpose_sift_detect: more than max_kp={max_kp} keypoints in a view (counts {out['count'].cpu().tolist()})")
+    else:
+        _lib.check(rc, "relpose_sift_detect")
+    return out
+
+
+def sift_detect_dev(images, crop=None, max_kp=SIFT_MAX_KP):
+    """Keypoint positions of every view (the kp.pt list of cv2's SIFT_create(contrastThreshold=0.02).detectAndCompute,
+    rputil.py:152-172, :253-265): images / crop as sift_detect_tensors -> [V] float64 numpy arrays [n, 2] (x, y) in crop coordinates,
+    in the detector's output order (SIFT detector)."""
+    r = sift_detect_tensors(images, crop, max_kp)
+    xy, cnt = r["xy"].cpu().numpy(), r["count"].cpu().numpy()
+    return [xy[v, :cnt[v]].astype(np.float64) for v in range(len(cnt))]
+
+
+def gpu_sift_detector(gray):
+    """A set_sift_detector hook backed by the HIP detector: gray uint8 [h, w] -> [n, 2] float64 (x, y)."""
+    g = np.ascontiguousarray(gray, dtype=np.uint8)
+    return sift_detect_dev(g[None], None)[0]
+
+
+def sift_images(rgb, kind, rgb_full=None):
+    """The uint8 BGR images the reference hands its detector, built on the device, and the crop it detects in.
+    'second' (SUNCG / Matterport): trunc(clip(rgb * 255, 0, 255)) of the panoramas (evaluation.py:168; the mask of :256-257 leaves the
+    observed face unchanged), crop = the face [h, 2h) (rputil.py:152-163).  'kinect' (ScanNet): (rgb_full * 255).astype(uint8) of the
+    640x480 frames (evaluation.py:261-262), no crop (rputil.py:253-265).  Channel 0 of the array is weighted as cv2's B.
+    rgb [B, 2, 3, h, 4h] / rgb_full [B, 2, 3, 480, 640] float32 (numpy or torch) -> (uint8 [2B, ., ., 3] CUDA, crop or None)."""
+    import torch
+    dev = _lib.require_gpu()
+    if kind == "second":
+        x = torch.as_tensor(rgb).to(dev, torch.float32)
+        B, _, _, h, w = x.shape
+        u8 = (x.reshape(2 * B, 3, h, w) * 255).clamp(0, 255).to(torch.uint8)
+        return u8.permute(0, 2, 3, 1).contiguous(), (h, 0, h, h)
+    if rgb_full is None:
+        raise ValueError("SIFT detection with the 'kinect' mask needs the 640x480 frames (rgb_full [B, 2, 3, 480, 640])")
+    x = torch.as_tensor(rgb_full).to(dev, torch.float32)
+    B = x.shape[0]
+    u8 = (x.reshape(2 * B, 3, x.shape[3], x.shape[4]) * 255).to(torch.uint8)
+    return u8.permute(0, 2, 3, 1).contiguous(), None
+
+
+def sift_views(rgb, kind, rgb_full=None, max_kp=SIFT_MAX_KP):
+    """SIFT detections of both views of every pair, in panorama coordinates (map_detections): [(source [n,2], target [m,2])] * B --
+    what RelativePosePipeline.prepare(sift=...) takes.  One batched detector call for all 2B views."""
+    h = int(rgb.shape[3])
+    u8, crop = sift_images(rgb, kind, rgb_full)
+    det = sift_detect_dev(u8, crop, max_kp)
+    return [(map_detections(det[2 * b], kind, h), map_detections(det[2 * b + 1], kind, h)) for b in range(len(det) // 2)]
 
 
 def bgr2gray(img):

@@ -165,6 +165,17 @@ def make_sift_detections(B, n, seed, mask_method="second", h=H):
     return out
 
 
+def kinect_frames(rgb, h=H):
+    """Stand-in 640x480 kinect frames for synthetic ScanNet pairs (the renderer has no full-resolution camera): the observed kinect crop of
+    every panorama (observed_box) resized bilinearly to 480x640.  rgb [B,2,3,h,4h] -> [B,2,3,480,640] float32."""
+    import torch
+    y0, y1, x0, x1 = observed_box("kinect", h)
+    B = rgb.shape[0]
+    crop = torch.from_numpy(np.ascontiguousarray(rgb[:, :, :, y0:y1, x0:x1], dtype=np.float32)).reshape(2 * B, 3, y1 - y0, x1 - x0)
+    full = torch.nn.functional.interpolate(crop, size=(480, 640), mode="bilinear", align_corners=False)
+    return full.reshape(B, 2, 3, 480, 640).numpy()
+
+
 def make_match_case(N, seed, inlier=0.6, noise=0.005, Nt=None):
     """Matcher-only input (helper dict format, reference rpmodule.py:317-326):
     random cloud, rigidly moved + permuted target, 60 % inliers."""
