@@ -18,7 +18,7 @@
  *    workspaces whose size is returned by the *_workspace_bytes functions;
  *  - all work is enqueued on `stream` (a hipStream_t passed as void*; NULL = the
  *    default stream); apart from the first-forward plan build and
- *    relpose_scnet_finalize / relpose_scnet_profile / relpose_sift_detect (its overflow flag) no entry point synchronises;
+ *    relpose_scnet_finalize / relpose_scnet_profile / relpose_sift_detect (its overflow flag) / relpose_fgr (its statuses) no entry point synchronises;
  *  - return value: 0 = enqueued, <0 = invalid argument (RELPOSE_EINVAL) or HIP
  *    error (-(1000+hipError_t)).  Per-pair degenerate inputs are NOT errors: the
  *    reference returns identity for them (rpmodule.py:346-348,377-379,406-408,
@@ -317,6 +317,57 @@ typedef struct RelposeSiftArgs {
 size_t relpose_sift_workspace_bytes(int32_t n_views, int32_t h, int32_t w, int32_t max_kp);
 int32_t relpose_sift_stage_capacity(int32_t max_kp);
 int relpose_sift_detect(const RelposeSiftArgs* args);
+
+/* ------------------------------------------------------------------ FPFH + fast global registration
+ * The reference's `--method fgs` baseline, open3d_fast_global_registration (baselines.py:83-106, preprocess_point_cloud :36-50): voxel
+ * 0.05 downsample, normals (r 0.10, max_nn 30), FPFH (r 0.25, max_nn 100), mutual fp32 feature matches, the tuple test (0.95, <= 1000
+ * tuples) and 64 Gauss-Newton steps of FGR (division factor 1.4, max correspondence distance 0.075), batched over pairs.  The contract
+ * (orders, bins, tie rules, the tuple draws) is DESIGN.md §4.6; it is this project's own and not checked against Open3D.
+ *   pc, valid    [2 n_pairs, n_points, 3] f64 and [2 n_pairs, n_points] u8 (relpose_depth2pc's layout): cloud 2b = the source of pair b,
+ *                2b + 1 its target; the sensor sits at the origin of each cloud's frame (normals are turned toward it)
+ *   max_points   voxels kept per cloud, 1 .. RELPOSE_FGR_MAX_POINTS_LIMIT (RELPOSE_FGR_MAX_POINTS is the default the wrappers use)
+ *   seed         the tuple draws: splitmix64(seed * 0x9E3779B97F4A7C15 + 3 t + k) mod (mutual matches), the same for every pair
+ *   pose         [n_pairs, 4, 4] f64, T p_src ~ p_tgt (the convention of R_gt_44); identity unless status == 0
+ *   status       [n_pairs] i32 RELPOSE_FGR_STATUS_*
+ * Optional per-stage outputs (NULL = kept in the workspace), rows past a cloud's count are left unwritten:
+ *   down_points [2 n_pairs, max_points, 3] f64 and down_count [2 n_pairs] i32 (the TRUE voxel count, also above max_points),
+ *   nbr_index [2 n_pairs, max_points, 100] i32 and nbr_count [2 n_pairs, max_points] i32 (the r 0.25 lists, (d2, index) order),
+ *   normals [2 n_pairs, max_points, 3] f64, fpfh [2 n_pairs, max_points, 33] f64,
+ *   corr [n_pairs, max_points, 2] i32 and n_corr [n_pairs] (mutual matches, ascending source index),
+ *   tuple_corr [n_pairs, 3 * 1000, 2] i32 and n_tuples [n_pairs] (the accepted tuples, 3 matches each: what FGR optimises over).
+ * Overflow: a cloud with more than max_points voxels gets its pair status RELPOSE_FGR_STATUS_OVERFLOW, nothing is written past max_points
+ * and the call returns RELPOSE_FGR_OVERFLOW (the other pairs are complete).  This entry point SYNCHRONISES `stream` once at its end.  The
+ * number of kernel launches does not depend on n_pairs.  workspace: relpose_fgr_workspace_bytes(n_pairs, n_points, max_points). */
+#define RELPOSE_FGR_OVERFLOW (-4)
+#define RELPOSE_FGR_MAX_POINTS 32768
+#define RELPOSE_FGR_MAX_POINTS_LIMIT 65536
+enum { RELPOSE_FGR_STATUS_OK = 0, RELPOSE_FGR_STATUS_FEW_POINTS = 1, RELPOSE_FGR_STATUS_FEW_CORR = 2, RELPOSE_FGR_STATUS_OVERFLOW = 3 };
+typedef struct RelposeFgrArgs {
+    uint32_t struct_size;       /* sizeof(RelposeFgrArgs) as the caller compiled it */
+    int32_t n_pairs;
+    int32_t n_points;
+    int32_t max_points;
+    const double* pc;
+    const uint8_t* valid;
+    uint64_t seed;
+    double* pose;
+    int32_t* status;
+    double* down_points;
+    int32_t* down_count;
+    int32_t* nbr_index;
+    int32_t* nbr_count;
+    double* normals;
+    double* fpfh;
+    int32_t* corr;
+    int32_t* n_corr;
+    int32_t* tuple_corr;
+    int32_t* n_tuples;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeFgrArgs;
+size_t relpose_fgr_workspace_bytes(int32_t n_pairs, int32_t n_points, int32_t max_points);
+int relpose_fgr(const RelposeFgrArgs* args);
 
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs

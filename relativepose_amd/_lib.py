@@ -63,6 +63,21 @@ SIFT_OVERFLOW = -3                  # include/relpose.h RELPOSE_SIFT_OVERFLOW
 SIFT_MAX_SIDE = 2048                # RELPOSE_SIFT_MAX_SIDE
 
 
+class FgrArgs(C.Structure):
+    """RelposeFgrArgs (include/relpose.h): the argument block of relpose_fgr."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_pairs", c_int), ("n_points", c_int), ("max_points", c_int), ("pc", c_void_p), ("valid", c_void_p),
+                ("seed", C.c_uint64), ("pose", c_void_p), ("status", c_void_p), ("down_points", c_void_p), ("down_count", c_void_p),
+                ("nbr_index", c_void_p), ("nbr_count", c_void_p), ("normals", c_void_p), ("fpfh", c_void_p), ("corr", c_void_p),
+                ("n_corr", c_void_p), ("tuple_corr", c_void_p), ("n_tuples", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("stream", c_void_p)]
+
+
+FGR_OVERFLOW = -4                   # RELPOSE_FGR_OVERFLOW
+FGR_MAX_POINTS = 32768              # RELPOSE_FGR_MAX_POINTS
+FGR_MAX_POINTS_LIMIT = 65536        # RELPOSE_FGR_MAX_POINTS_LIMIT
+FGR_MAX_TUPLES = 1000
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -97,6 +112,8 @@ SIGNATURES = {
     "relpose_sift_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "relpose_sift_stage_capacity": (c_int, [c_int]),
     "relpose_sift_detect": (c_int, [C.POINTER(SiftArgs)]),
+    "relpose_fgr_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "relpose_fgr": (c_int, [C.POINTER(FgrArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

@@ -1,0 +1,76 @@
+"""The point-cloud registration baselines of the reference (baselines.py), on the GPU.
+
+  open3d_fast_global_registration   baselines.py:83-106 (`--method fgs`): FPFH features + fast global registration, csrc/fgr.hip
+  fast_global_registration_dev      the same for a batch of pairs on the device (relpose_fgr)
+
+The other baselines (super4pcs, open3d_global_registration, open3d_color_registration) are not implemented.
+The contract is the project's own; Open3D is not a dependency and agreement with it is not tested."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+STATUS = {0: "ok", 1: "too few points", 2: "too few correspondences", 3: "overflow"}
+
+
+def fast_global_registration_dev(pc, valid, max_points=_lib.FGR_MAX_POINTS, seed=0, stages=False):
+    """pc [2B, P, 3] f64 / valid [2B, P] u8 CUDA tensors (util.depth2pc_dev's layout; cloud 2b = the source of pair b, 2b+1 its target)
+    -> (pose [B,4,4] f64 with T p_src ~ p_tgt, status [B] i32, stages).  stages=True: a dict of every per-stage output (down_points,
+    down_count, nbr_index, nbr_count, normals, fpfh, corr, n_corr, tuple_corr, n_tuples); else an empty dict.
+    Raises on an invalid call; a cloud with more than max_points voxels gives its pair status 3 (overflow) and identity."""
+    import torch
+    _lib.require_gpu()
+    if pc.dim() != 3 or pc.shape[2] != 3 or pc.shape[0] % 2 or valid.shape != pc.shape[:2]:
+        raise ValueError("pc must be [2B, P, 3] and valid [2B, P]")
+    pc = pc.to(torch.float64).contiguous()
+    valid = valid.to(torch.uint8).contiguous()
+    C2, P = int(pc.shape[0]), int(pc.shape[1])
+    B, N, dev = C2 // 2, int(max_points), pc.device
+    L = _lib.lib()
+    wsb = L.relpose_fgr_workspace_bytes(B, P, N)
+    if wsb == 0:
+        raise ValueError(f"relpose_fgr: unsupported sizes (pairs {B}, points {P}, max_points {N})")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    pose = torch.empty(B, 4, 4, dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    st = {}
+    if stages:
+        st = {"down_points": torch.zeros(C2, N, 3, dtype=torch.float64, device=dev), "down_count": torch.zeros(C2, dtype=torch.int32, device=dev),
+              "nbr_index": torch.full((C2, N, 100), -1, dtype=torch.int32, device=dev), "nbr_count": torch.zeros(C2, N, dtype=torch.int32, device=dev),
+              "normals": torch.zeros(C2, N, 3, dtype=torch.float64, device=dev), "fpfh": torch.zeros(C2, N, 33, dtype=torch.float64, device=dev),
+              "corr": torch.zeros(B, N, 2, dtype=torch.int32, device=dev), "n_corr": torch.zeros(B, dtype=torch.int32, device=dev),
+              "tuple_corr": torch.zeros(B, 3 * _lib.FGR_MAX_TUPLES, 2, dtype=torch.int32, device=dev),
+              "n_tuples": torch.zeros(B, dtype=torch.int32, device=dev)}
+    a = _lib.FgrArgs()
+    a.struct_size = C.sizeof(a)
+    a.n_pairs, a.n_points, a.max_points, a.seed = B, P, N, int(seed)
+    a.pc, a.valid, a.pose, a.status = pc.data_ptr(), valid.data_ptr(), pose.data_ptr(), status.data_ptr()
+    for k, v in st.items():
+        setattr(a, k, v.data_ptr())
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), wsb, _lib.stream_ptr()
+    rc = L.relpose_fgr(C.byref(a))
+    if rc not in (0, _lib.FGR_OVERFLOW):
+        _lib.check(rc, "relpose_fgr")
+    return pose, status, st
+
+
+def pack_clouds(clouds):
+    """[pc_0, pc_1, ...] numpy [n_i, 3] -> (pc [len, P, 3] f64, valid [len, P] u8) numpy, P = the largest n_i (at least 1)."""
+    P = max(1, max(len(c) for c in clouds))
+    pc = np.zeros((len(clouds), P, 3))
+    valid = np.zeros((len(clouds), P), np.uint8)
+    for i, c in enumerate(clouds):
+        pc[i, :len(c)] = c
+        valid[i, :len(c)] = 1
+    return pc, valid
+
+
+def open3d_fast_global_registration(pc_src, pc_tgt):
+    """baselines.py:83-106: pc_src [n1,3], pc_tgt [n2,3] numpy -> R_hat [4,4] numpy (T p_src ~ p_tgt; identity when the pair has too
+    few points or correspondences, or more voxels than RELPOSE_FGR_MAX_POINTS)."""
+    import torch
+    dev = _lib.require_gpu()
+    pc, valid = pack_clouds([np.asarray(pc_src, np.float64).reshape(-1, 3), np.asarray(pc_tgt, np.float64).reshape(-1, 3)])
+    pose, _, _ = fast_global_registration_dev(torch.from_numpy(pc).to(dev), torch.from_numpy(valid).to(dev))
+    return pose[0].cpu().numpy()

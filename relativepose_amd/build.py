@@ -16,6 +16,7 @@ SOURCES = [
     ("geometry.hip", ["-ffp-contract=off"]),
     ("keypoints.hip", ["-ffp-contract=off"]),
     ("sift.hip", ["-ffp-contract=off"]),          # the detector and its numpy model must round alike
+    ("fgr.hip", ["-ffp-contract=off"]),           # FPFH + FGR: bins and matches must agree with tests/fgr_model.py bit for bit
     ("scnet.hip", []),
 ]
 

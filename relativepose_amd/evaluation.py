@@ -189,6 +189,39 @@ def _default_record(pipe, sub, poses, device, names, ks):
     return out
 
 
+def evaluate_fgs(batches, device, dataset, result_path=None, max_points=None, seed=0):
+    """The reference's `--method fgs` loop (evaluation.py:182-203, 286-320) over batches of synthetic pairs: the observed-block clouds
+    of both views (util.depth2pc_dev, as _default_record builds them), ONE batched FPFH + fast global registration call per batch
+    (baselines.fast_global_registration_dev), then per pair the overlap statistics; pairs with overlap < 0.1 are skipped without a
+    record (evaluation.py:190-191).  Returns the record list (the reference's keys + 'status'); written to result_path if given."""
+    import torch
+    from . import _lib, baselines, util
+    stats = []
+    for batch in batches:
+        n = _batch_size(batch)
+        sub = _batch_take(batch, np.arange(n))
+        depth = torch.from_numpy(np.ascontiguousarray(sub["depth"].reshape(2 * n, *sub["depth"].shape[2:]))).to(device)
+        pcs, valid = util.depth2pc_dev(depth, dataset)
+        pose, status, _ = baselines.fast_global_registration_dev(pcs, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)
+        pose, status = pose.cpu().numpy(), status.cpu().numpy()
+        pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
+        for q in range(n):
+            R_gt_44 = np.matmul(sub["R"][q, 1], np.linalg.inv(sub["R"][q, 0]))
+            pc_src, pc_tgt = pcs[2 * q][valid[2 * q]], pcs[2 * q + 1][valid[2 * q + 1]]
+            if len(pc_src) == 0 or len(pc_tgt) == 0:                  # evaluation.py:184-186
+                continue
+            ov, cam_dist, pc_dist, pc_nn = util.point_cloud_overlap(pc_src, pc_tgt, R_gt_44)
+            if ov < 0.1:                                                  # evaluation.py:190-191
+                continue
+            k = len(stats)
+            rec = result_record(f"pair{k}/src", f"pair{k}/tgt", pose[q], R_gt_44, pc_src, ov, pc_dist, cam_dist, pc_nn)
+            rec['status'] = int(status[q])
+            stats.append(rec)
+    if result_path is not None:
+        save_results(result_path, stats)
+    return stats
+
+
 def evaluate_pairs_sharded(pipe, batches, device, result_path=None, names=None, rank=0, world=1, resume=True, round_batches=None,
                            record_fn=None, depth=2):
     """`evaluate_pairs` over `world` ranks (one process per GPU, torch.distributed initialised by the caller:
@@ -342,7 +375,31 @@ def main(argv=None):
     ap.add_argument("--precision", choices=["f32", "bf16x9", "bf16x6", "f16x3", "bf16x3", "f16"], default="f32",
                     help="conv arithmetic of SCNet (SCNet.set_precision): f32 = the fp32 MFMA kernels (default), bf16x6 = what bench.py runs configs 1-3 in")
     ap.add_argument("--completion", type=int, default=1, choices=[0, 1], help="0 = the reference's 'ours_nc' method (evaluation.py:74): observed-region keypoints only")
+    ap.add_argument("--method", choices=["ours", "fgs"], default="ours",
+                    help="fgs = the reference's fast global registration baseline (baselines.py:83-106) on the observed clouds: no network")
     args = ap.parse_args(argv)
+
+    if args.method == "fgs":
+        if args.gpus > 1:
+            raise SystemExit("--method fgs runs on one GPU (--gpus 1): the baseline is not sharded")
+        if args.dataset == "scannet":
+            raise SystemExit("--method fgs: the synthetic ScanNet pairs have no full-resolution depth, which the reference's baselines use "
+                             "(util.parse_data(..., 'scannet', 'fgs')); run real 480x640 frames through util.parse_data and "
+                             "baselines.open3d_fast_global_registration")
+        import torch
+        from . import _lib
+        dev = _lib.require_gpu()
+        mm = "second"
+        batches = [SyntheticBatch(min(args.batch, args.pairs - k), args.seed + k, args.dataset, mm, args.keypoints)
+                   for k in range(0, args.pairs, args.batch)]
+        path = None if args.exp is None else args.exp + ".result.npy"
+        t0 = time.perf_counter()
+        stats = evaluate_fgs(batches, dev, args.dataset, result_path=path)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(json.dumps({"method": "fgs", "pairs": args.pairs, "records": len(stats), "seconds": dt, "result_file": path,
+                          "dataset": args.dataset, "stats": summarize(stats)}), flush=True)
+        return
 
     def worker():
         import torch

@@ -1,0 +1,168 @@
+"""GPU: the batched FPFH + fast global registration (csrc/fgr.hip, relpose_fgr) against the numpy model of its contract
+(tests/fgr_model.py), stage by stage, and its uses: baselines.open3d_fast_global_registration,
+torch.ops.relpose.fast_global_registration and evaluation --method fgs.  Reference: baselines.py:36-50, 83-106."""
+import numpy as np
+import pytest
+
+import fgr_model as M
+import fgr_scenes as S
+from gpu_util import log
+from test_fgr_cpu import MAX_DEG, MAX_T, SEEDS
+
+pytestmark = pytest.mark.gpu
+
+
+def _dev():
+    import torch
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _run(clouds, **kw):
+    import torch
+    from relativepose_amd import baselines
+    pc, valid = baselines.pack_clouds(clouds)
+    pose, status, st = baselines.fast_global_registration_dev(torch.from_numpy(pc).to(_dev()), torch.from_numpy(valid).to(_dev()), stages=True, **kw)
+    return pose.cpu().numpy(), status.cpu().numpy(), {k: v.cpu().numpy() for k, v in st.items()}
+
+
+def _room_clouds(n, seed):
+    """Observed-block clouds of synth.make_pairs SUNCG pairs (util.depth2pc_dev) -> pc, valid CUDA tensors [2n, P, .]."""
+    import torch
+    from relativepose_amd import synth, util
+    d = synth.make_pairs(n, seed, "suncg")
+    return util.depth2pc_dev(torch.from_numpy(d["depth"].reshape(2 * n, *d["depth"].shape[2:])).to(_dev()), "suncg")
+
+
+def _check_cloud(st, c, pts):
+    """Stages 1-4 of cloud c against the model."""
+    down, _, _ = M.voxel_down(pts)
+    n = len(down)
+    assert st["down_count"][c] == n
+    assert np.array_equal(st["down_points"][c, :n], down)
+    f = M.features(down)
+    assert np.array_equal(st["nbr_count"][c, :n], f["cnt"])
+    got_idx = np.where(np.arange(100)[None] < f["cnt"][:, None], st["nbr_index"][c, :n], -1)
+    assert np.array_equal(got_idx, f["idx"])
+    dn = np.abs(st["normals"][c, :n] - f["normal"]).max()
+    assert dn <= 1e-9, dn
+    rel = np.abs(st["fpfh"][c, :n] - f["fpfh"]).max() / max(np.abs(f["fpfh"]).max(), 1e-300)
+    assert rel <= 1e-6, rel
+    return dn, rel
+
+
+def _check_pair(pose, status, st, b, src, tgt):
+    r = M.register(src, tgt)
+    assert status[b] == r["status"]
+    if "corr" in r:
+        nc = len(r["corr"])
+        assert st["n_corr"][b] == nc and np.array_equal(st["corr"][b, :nc], r["corr"])
+        nt = len(r["tuples"])
+        assert st["n_tuples"][b] == nt and np.array_equal(st["tuple_corr"][b, :3 * nt], r["tuple_corr"])
+    dp = np.abs(pose[b] - r["pose"]).max()
+    assert dp <= 1e-9, dp
+    return r, dp
+
+
+def test_stages_match_the_model_on_planted_pairs():
+    pairs = [S.planted_pair(s, density=800.0) for s in (10, 11)]
+    clouds = [c for s, t, _ in pairs for c in (s, t)]
+    pose, status, st = _run(clouds)
+    for c, pts in enumerate(clouds):
+        dn, rel = _check_cloud(st, c, pts)
+        log("fgr_stages_planted", cloud=c, n=int(st["down_count"][c]), normal_err=dn, fpfh_rel=rel)
+    for b, (s, t, _) in enumerate(pairs):
+        r, dp = _check_pair(pose, status, st, b, s, t)
+        log("fgr_pair_planted", pair=b, status=int(status[b]), n_corr=int(st["n_corr"][b]), n_tuples=int(st["n_tuples"][b]), pose_err=dp)
+
+
+def test_stages_match_the_model_on_room_clouds():
+    from relativepose_amd import baselines
+    pc, valid = _room_clouds(1, 31)
+    pose, status, st = baselines.fast_global_registration_dev(pc, valid, stages=True)
+    pose, status, st = pose.cpu().numpy(), status.cpu().numpy(), {k: v.cpu().numpy() for k, v in st.items()}
+    pcn, vn = pc.cpu().numpy(), valid.cpu().numpy().astype(bool)
+    clouds = [pcn[c][vn[c]] for c in range(2)]
+    for c in range(2):
+        dn, rel = _check_cloud(st, c, clouds[c])
+        log("fgr_stages_room", cloud=c, n=int(st["down_count"][c]), normal_err=dn, fpfh_rel=rel)
+    for b in range(1):
+        _, dp = _check_pair(pose, status, st, b, clouds[2 * b], clouds[2 * b + 1])
+        log("fgr_pair_room", pair=b, status=int(status[b]), pose_err=dp)
+
+
+def test_batch_of_32_equals_single_calls_and_repeats_bitwise():
+    from relativepose_amd import baselines
+    pc, valid = _room_clouds(32, 500)
+    p1, s1, st1 = baselines.fast_global_registration_dev(pc, valid, stages=True)
+    p2, s2, st2 = baselines.fast_global_registration_dev(pc, valid, stages=True)
+    assert np.array_equal(p1.cpu().numpy(), p2.cpu().numpy()) and np.array_equal(s1.cpu().numpy(), s2.cpu().numpy())
+    for k in st1:
+        assert np.array_equal(st1[k].cpu().numpy(), st2[k].cpu().numpy()), k
+    for b in range(32):
+        pb, sb, stb = baselines.fast_global_registration_dev(pc[2 * b:2 * b + 2], valid[2 * b:2 * b + 2], stages=True)
+        assert np.array_equal(pb.cpu().numpy()[0], p1.cpu().numpy()[b]), b
+        assert int(sb[0]) == int(s1[b])
+        for k in ("down_count", "fpfh", "n_corr", "tuple_corr"):
+            big = st1[k].cpu().numpy()
+            sl = big[2 * b:2 * b + 2] if big.shape[0] == 64 else big[b:b + 1]
+            assert np.array_equal(stb[k].cpu().numpy(), sl), (b, k)
+    log("fgr_batch32", status=s1.cpu().numpy())
+
+
+def test_overflow_returns_true_counts():
+    import torch
+    from relativepose_amd import _lib, baselines
+    s, t, _ = S.planted_pair(0, density=300.0)
+    pc, valid = baselines.pack_clouds([s, t])
+    pose, status, st = baselines.fast_global_registration_dev(torch.from_numpy(pc).to(_dev()), torch.from_numpy(valid).to(_dev()),
+                                                              max_points=64, stages=True)
+    ns, nt = len(M.voxel_down(s)[0]), len(M.voxel_down(t)[0])
+    assert ns > 64 and nt > 64
+    assert st["down_count"].cpu().numpy().tolist() == [ns, nt]
+    assert int(status[0]) == M.STATUS_OVERFLOW and np.array_equal(pose[0].cpu().numpy(), np.eye(4))
+    assert st["down_points"].shape[1] == 64
+    import ctypes as C
+    a = _lib.FgrArgs()                                            # the raw return code
+    a.struct_size = C.sizeof(a)
+    pcd, vd = torch.from_numpy(pc).to(_dev()), torch.from_numpy(valid).to(_dev())
+    wsb = _lib.lib().relpose_fgr_workspace_bytes(1, pc.shape[1], 64)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=_dev())
+    a.n_pairs, a.n_points, a.max_points = 1, pc.shape[1], 64
+    a.pc, a.valid, a.pose, a.status = pcd.data_ptr(), vd.data_ptr(), pose.data_ptr(), status.data_ptr()
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), wsb, _lib.stream_ptr()
+    assert _lib.lib().relpose_fgr(C.byref(a)) == _lib.FGR_OVERFLOW
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_planted_motion_on_the_gpu(seed):
+    from relativepose_amd import baselines
+    src, tgt, T = S.planted_pair(seed)
+    T_hat = baselines.open3d_fast_global_registration(src, tgt)
+    deg, dt = S.pose_error(T_hat, T)
+    log("fgr_planted_gpu", seed=seed, deg=deg, t=dt)
+    assert deg < MAX_DEG and dt < MAX_T, (deg, dt)
+
+
+def test_torch_op_matches_the_direct_call():
+    import torch
+    from relativepose_amd import baselines, ops  # noqa: F401
+    pc, valid = _room_clouds(4, 77)
+    p1, s1 = torch.ops.relpose.fast_global_registration(pc, valid)
+    p2, s2, _ = baselines.fast_global_registration_dev(pc, valid)
+    assert torch.equal(p1, p2) and torch.equal(s1, s2)
+    assert p1.shape == (4, 4, 4) and s1.dtype == torch.int32
+
+
+def test_evaluation_method_fgs_writes_reference_records(tmp_path, capsys):
+    from relativepose_amd import evaluation
+    exp = str(tmp_path / "fgs")
+    evaluation.main(["--method", "fgs", "--dataset", "suncg", "--pairs", "64", "--batch", "32", "--exp", exp])
+    recs = evaluation.load_results(exp + ".result.npy")
+    keys = {'img_src', 'img_tgt', 'err_ad', 'err_t', 'err_blind', 'err_t_blind', 'overlap', 'pc_dist', 'cam_dist', 'pc_nearest', 'R_gt',
+            'R_pred_44', 'status'}
+    assert 0 < len(recs) <= 64
+    assert all(set(r) == keys for r in recs)
+    assert all(r['overlap'] >= 0.1 for r in recs)
+    out = capsys.readouterr().out
+    assert '"method": "fgs"' in out
+    log("fgr_evaluation", records=len(recs), stats=evaluation.summarize(recs))
