@@ -18,7 +18,7 @@
  *    workspaces whose size is returned by the *_workspace_bytes functions;
  *  - all work is enqueued on `stream` (a hipStream_t passed as void*; NULL = the
  *    default stream); apart from the first-forward plan build and
- *    relpose_scnet_finalize / relpose_scnet_profile / relpose_sift_detect (its overflow flag) / relpose_fgr (its statuses) no entry point synchronises;
+ *    relpose_scnet_finalize / relpose_scnet_profile / relpose_sift_detect (its overflow flag) / relpose_fgr / relpose_ransac (their statuses) no entry point synchronises;
  *  - return value: 0 = enqueued, <0 = invalid argument (RELPOSE_EINVAL) or HIP
  *    error (-(1000+hipError_t)).  Per-pair degenerate inputs are NOT errors: the
  *    reference returns identity for them (rpmodule.py:346-348,377-379,406-408,
@@ -368,6 +368,66 @@ typedef struct RelposeFgrArgs {
 } RelposeFgrArgs;
 size_t relpose_fgr_workspace_bytes(int32_t n_pairs, int32_t n_points, int32_t max_points);
 int relpose_fgr(const RelposeFgrArgs* args);
+
+/* ------------------------------------------------------------------ RANSAC feature registration
+ * The reference's `--method gs` baseline, open3d_global_registration (baselines.py:52-81): the front end of relpose_fgr (voxel 0.05,
+ * normals, FPFH; the exact fp32 feature nearest neighbour from source to target, one correspondence per source voxel), then RANSAC over
+ * those correspondences as registration_ransac_based_on_feature_matching(..., 0.075, point-to-point, 4, [EdgeLength(0.9), Distance(0.075)],
+ * RANSACConvergenceCriteria(4000000, 500)) reads: 4-point hypotheses, the first max_validations that pass both checkers validated in
+ * iteration order, the best by (inlier count, then smaller rmse).  The contract (draws, orders, reductions) is DESIGN.md §4.7; it is this
+ * project's own and not checked against Open3D.
+ *   pc, valid        as relpose_fgr (cloud 2b = the source of pair b, 2b + 1 its target)
+ *   max_points       voxels kept per cloud, 1 .. RELPOSE_FGR_MAX_POINTS_LIMIT
+ *   seed             draw k of iteration t: splitmix64(seed * 0x9E3779B97F4A7C15 + 4 t + k) mod (source voxels)
+ *   max_iterations   0 = 4000000; at most RELPOSE_RANSAC_MAX_ITERATIONS_LIMIT
+ *   max_validations  0 = 500; at most RELPOSE_RANSAC_MAX_VALIDATIONS_LIMIT
+ *   pose             [n_pairs, 4, 4] f64, T p_src ~ p_tgt (the convention of R_gt_44); identity unless status == 0
+ *   status           [n_pairs] i32 RELPOSE_RANSAC_STATUS_*
+ * Optional per-pair outputs (NULL = not written): fitness [n_pairs] f64 (inliers / source voxels), inlier_rmse [n_pairs] f64,
+ *   n_iterations, n_validations, best_index [n_pairs] i32 (best_index: the slot of the chosen hypothesis in the validated set, -1 if none).
+ * Optional stage outputs (NULL = kept in the workspace), rows past a count are left unwritten:
+ *   down_points [2 n_pairs, max_points, 3] f64 and down_count [2 n_pairs] i32 (the true voxel count), fpfh [2 n_pairs, max_points, 33] f64,
+ *   nn [n_pairs, max_points] i32 (the source voxels' nearest target feature), val_iter, val_inliers [n_pairs, max_validations] i32 and
+ *   val_err [n_pairs, max_validations] f64 (the validated iterations in order, their inlier counts and inlier rmse).
+ * Overflow: as relpose_fgr (status RELPOSE_RANSAC_STATUS_OVERFLOW, the call returns RELPOSE_RANSAC_OVERFLOW, other pairs complete).  This
+ * entry point SYNCHRONISES `stream` once at its end.  The number of kernel launches depends on max_iterations only.
+ * workspace: relpose_ransac_workspace_bytes(n_pairs, n_points, max_points, max_iterations, max_validations) (0 = the defaults). */
+#define RELPOSE_RANSAC_OVERFLOW (-5)
+#define RELPOSE_RANSAC_MAX_ITERATIONS 4000000
+#define RELPOSE_RANSAC_MAX_VALIDATIONS 500
+#define RELPOSE_RANSAC_MAX_ITERATIONS_LIMIT 16777216
+#define RELPOSE_RANSAC_MAX_VALIDATIONS_LIMIT 4096
+enum { RELPOSE_RANSAC_STATUS_OK = 0, RELPOSE_RANSAC_STATUS_FEW_POINTS = 1, RELPOSE_RANSAC_STATUS_OVERFLOW = 3, RELPOSE_RANSAC_STATUS_NO_HYPOTHESIS = 4 };
+typedef struct RelposeRansacArgs {
+    uint32_t struct_size;       /* sizeof(RelposeRansacArgs) as the caller compiled it */
+    int32_t n_pairs;
+    int32_t n_points;
+    int32_t max_points;
+    const double* pc;
+    const uint8_t* valid;
+    uint64_t seed;
+    int32_t max_iterations;
+    int32_t max_validations;
+    double* pose;
+    int32_t* status;
+    double* fitness;
+    double* inlier_rmse;
+    int32_t* n_iterations;
+    int32_t* n_validations;
+    int32_t* best_index;
+    double* down_points;
+    int32_t* down_count;
+    double* fpfh;
+    int32_t* nn;
+    int32_t* val_iter;
+    int32_t* val_inliers;
+    double* val_err;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeRansacArgs;
+size_t relpose_ransac_workspace_bytes(int32_t n_pairs, int32_t n_points, int32_t max_points, int32_t max_iterations, int32_t max_validations);
+int relpose_ransac(const RelposeRansacArgs* args);
 
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs

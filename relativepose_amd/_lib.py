@@ -78,6 +78,22 @@ FGR_MAX_POINTS_LIMIT = 65536        # RELPOSE_FGR_MAX_POINTS_LIMIT
 FGR_MAX_TUPLES = 1000
 
 
+class RansacArgs(C.Structure):
+    """RelposeRansacArgs (include/relpose.h): the argument block of relpose_ransac."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_pairs", c_int), ("n_points", c_int), ("max_points", c_int), ("pc", c_void_p), ("valid", c_void_p),
+                ("seed", C.c_uint64), ("max_iterations", c_int), ("max_validations", c_int), ("pose", c_void_p), ("status", c_void_p),
+                ("fitness", c_void_p), ("inlier_rmse", c_void_p), ("n_iterations", c_void_p), ("n_validations", c_void_p), ("best_index", c_void_p),
+                ("down_points", c_void_p), ("down_count", c_void_p), ("fpfh", c_void_p), ("nn", c_void_p), ("val_iter", c_void_p),
+                ("val_inliers", c_void_p), ("val_err", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
+RANSAC_OVERFLOW = -5                # RELPOSE_RANSAC_OVERFLOW
+RANSAC_MAX_ITERATIONS = 4000000     # RELPOSE_RANSAC_MAX_ITERATIONS
+RANSAC_MAX_VALIDATIONS = 500        # RELPOSE_RANSAC_MAX_VALIDATIONS
+RANSAC_MAX_ITERATIONS_LIMIT = 16777216
+RANSAC_MAX_VALIDATIONS_LIMIT = 4096
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -114,6 +130,8 @@ SIGNATURES = {
     "relpose_sift_detect": (c_int, [C.POINTER(SiftArgs)]),
     "relpose_fgr_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "relpose_fgr": (c_int, [C.POINTER(FgrArgs)]),
+    "relpose_ransac_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "relpose_ransac": (c_int, [C.POINTER(RansacArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

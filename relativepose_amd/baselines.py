@@ -2,16 +2,18 @@
 
   open3d_fast_global_registration   baselines.py:83-106 (`--method fgs`): FPFH features + fast global registration, csrc/fgr.hip
   fast_global_registration_dev      the same for a batch of pairs on the device (relpose_fgr)
+  open3d_global_registration        baselines.py:52-81 (`--method gs`): the same FPFH front end + RANSAC over feature matches, csrc/ransac.hip
+  global_registration_dev           the same for a batch of pairs on the device (relpose_ransac)
 
-The other baselines (super4pcs, open3d_global_registration, open3d_color_registration) are not implemented.
-The contract is the project's own; Open3D is not a dependency and agreement with it is not tested."""
+The other baselines (super4pcs, open3d_color_registration) are not implemented.
+The contracts are the project's own; Open3D is not a dependency and agreement with it is not tested."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 
-STATUS = {0: "ok", 1: "too few points", 2: "too few correspondences", 3: "overflow"}
+STATUS = {0: "ok", 1: "too few points", 2: "too few correspondences", 3: "overflow", 4: "no hypothesis"}
 
 
 def fast_global_registration_dev(pc, valid, max_points=_lib.FGR_MAX_POINTS, seed=0, stages=False):
@@ -73,4 +75,56 @@ def open3d_fast_global_registration(pc_src, pc_tgt):
     dev = _lib.require_gpu()
     pc, valid = pack_clouds([np.asarray(pc_src, np.float64).reshape(-1, 3), np.asarray(pc_tgt, np.float64).reshape(-1, 3)])
     pose, _, _ = fast_global_registration_dev(torch.from_numpy(pc).to(dev), torch.from_numpy(valid).to(dev))
+    return pose[0].cpu().numpy()
+
+
+def global_registration_dev(pc, valid, max_points=_lib.FGR_MAX_POINTS, seed=0, max_iterations=_lib.RANSAC_MAX_ITERATIONS,
+                            max_validations=_lib.RANSAC_MAX_VALIDATIONS, stages=False):
+    """pc [2B, P, 3] f64 / valid [2B, P] u8 CUDA tensors (cloud 2b = the source of pair b, 2b+1 its target) -> (pose [B,4,4] f64 with
+    T p_src ~ p_tgt, status [B] i32, out).  out always holds the per-pair fitness, inlier_rmse, n_iterations, n_validations and
+    best_index; stages=True adds down_points, down_count, fpfh, nn (source -> target feature match), val_iter, val_inliers and val_err.
+    Raises on an invalid call; a cloud with more than max_points voxels gives its pair status 3 (overflow) and identity."""
+    import torch
+    _lib.require_gpu()
+    if pc.dim() != 3 or pc.shape[2] != 3 or pc.shape[0] % 2 or valid.shape != pc.shape[:2]:
+        raise ValueError("pc must be [2B, P, 3] and valid [2B, P]")
+    pc = pc.to(torch.float64).contiguous()
+    valid = valid.to(torch.uint8).contiguous()
+    C2, P = int(pc.shape[0]), int(pc.shape[1])
+    B, N, dev = C2 // 2, int(max_points), pc.device
+    MI, MV = int(max_iterations), int(max_validations)
+    L = _lib.lib()
+    wsb = L.relpose_ransac_workspace_bytes(B, P, N, MI, MV)
+    if wsb == 0 or MI <= 0 or MV <= 0:
+        raise ValueError(f"relpose_ransac: unsupported sizes (pairs {B}, points {P}, max_points {N}, max_iterations {MI}, max_validations {MV})")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    pose = torch.empty(B, 4, 4, dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+    f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
+    out = {"fitness": f64(B), "inlier_rmse": f64(B), "n_iterations": i32(B), "n_validations": i32(B), "best_index": i32(B)}
+    if stages:
+        out.update(down_points=f64(C2, N, 3), down_count=i32(C2), fpfh=f64(C2, N, 33), nn=torch.full((B, N), -1, dtype=torch.int32, device=dev),
+                   val_iter=torch.full((B, MV), -1, dtype=torch.int32, device=dev), val_inliers=i32(B, MV), val_err=f64(B, MV))
+    a = _lib.RansacArgs()
+    a.struct_size = C.sizeof(a)
+    a.n_pairs, a.n_points, a.max_points, a.seed = B, P, N, int(seed)
+    a.max_iterations, a.max_validations = MI, MV
+    a.pc, a.valid, a.pose, a.status = pc.data_ptr(), valid.data_ptr(), pose.data_ptr(), status.data_ptr()
+    for k, v in out.items():
+        setattr(a, k, v.data_ptr())
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), wsb, _lib.stream_ptr()
+    rc = L.relpose_ransac(C.byref(a))
+    if rc not in (0, _lib.RANSAC_OVERFLOW):
+        _lib.check(rc, "relpose_ransac")
+    return pose, status, out
+
+
+def open3d_global_registration(pc_src, pc_tgt):
+    """baselines.py:52-81: pc_src [n1,3], pc_tgt [n2,3] numpy -> R_hat [4,4] numpy (T p_src ~ p_tgt; identity when the pair has too
+    few points, more voxels than RELPOSE_FGR_MAX_POINTS, or no hypothesis with an inlier)."""
+    import torch
+    dev = _lib.require_gpu()
+    pc, valid = pack_clouds([np.asarray(pc_src, np.float64).reshape(-1, 3), np.asarray(pc_tgt, np.float64).reshape(-1, 3)])
+    pose, _, _ = global_registration_dev(torch.from_numpy(pc).to(dev), torch.from_numpy(valid).to(dev))
     return pose[0].cpu().numpy()

@@ -17,6 +17,7 @@ SOURCES = [
     ("keypoints.hip", ["-ffp-contract=off"]),
     ("sift.hip", ["-ffp-contract=off"]),          # the detector and its numpy model must round alike
     ("fgr.hip", ["-ffp-contract=off"]),           # FPFH + FGR: bins and matches must agree with tests/fgr_model.py bit for bit
+    ("ransac.hip", ["-ffp-contract=off"]),        # RANSAC: draws, Horn and the validation sums must agree with tests/ransac_model.py
     ("scnet.hip", []),
 ]
 

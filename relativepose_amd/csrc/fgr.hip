@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.h"
+#include "fgr_internal.h"
 
 namespace {
 
@@ -46,32 +47,6 @@ __constant__ double kEdgeCos[10] = {-0.8412535328311811, -0.4154150130018863, 0.
                                     0.9594929736144975,  0.6548607339452851,  0.14231483827328512, -0.41541501300188616, -0.8412535328311813};
 __constant__ double kEdgeSin[10] = {-0.5406408174555978, -0.9096319953545184, -0.9898214418809327, -0.7557495743542583, -0.2817325568414295,
                                     0.2817325568414295,  0.7557495743542583,  0.9898214418809327,  0.9096319953545186,  0.5406408174555974};
-
-struct FgrBufs {
-    int n_clouds, P, cap;
-    const double* pc;
-    const uint8_t* valid;
-    long long* key[2];       // [2B, P] ping-pong
-    int* idx[2];
-    double* pts;             // [2B, cap, 3]
-    int* ix;                 // [2B, cap]
-    int* count;              // [2B] true voxel count
-    int* nbr;                // [2B, cap, 100]
-    double* nd2;             // [2B, cap, 100]
-    int* ncnt;               // [2B, cap]
-    double* normal;          // [2B, cap, 3]
-    double* spfh;            // [2B, cap, 33]
-    double* fpfh;            // [2B, cap, 33]
-    float* f32;              // [2B, cap, 33]
-    int* nn;                 // [2B, cap]
-    int* corr;               // [B, cap, 2]
-    int* ncorr;              // [B]
-    int* tcorr;              // [B, 3000, 2]
-    int* ntup;               // [B]
-    double* pose;            // [B, 4, 4]
-    int* status;             // [B]
-    unsigned long long seed;
-};
 
 __device__ __forceinline__ int cloud_n(const FgrBufs& f, int c) { return min(f.count[c], f.cap); }
 
@@ -376,7 +351,6 @@ __global__ __launch_bounds__(256) void fgr_normals_kernel(FgrBufs f) {
 }
 
 // ------------------------------------------------------------------------------------------------------- 4. SPFH / FPFH
-__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
     o[0] = a[1] * b[2] - a[2] * b[1];
     o[1] = a[2] * b[0] - a[0] * b[2];
@@ -401,10 +375,10 @@ __device__ __forceinline__ int angle_bin(double x, double y) {
 // Open3D's ComputePairFeatures + the SPFH binning; the zero feature -> bins 5, 5, 5
 __device__ void pair_bins(const double* p1, const double* n1, const double* p2, const double* n2, int* bins) {
     double dp[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
-    const double L = sqrt(dot3(dp, dp));
+    const double L = sqrt(fgr_dot3(dp, dp));
     bins[0] = bins[1] = bins[2] = 5;
     if (L == 0.0) return;
-    const double a1 = dot3(n1, dp) / L, a2 = dot3(n2, dp) / L;
+    const double a1 = fgr_dot3(n1, dp) / L, a2 = fgr_dot3(n2, dp) / L;
     const double* m1 = n1;
     const double* m2 = n2;
     double f2 = a1;
@@ -415,12 +389,12 @@ __device__ void pair_bins(const double* p1, const double* n1, const double* p2, 
     }
     double v[3], w[3];
     cross3(dp, m1, v);
-    const double vn = sqrt(dot3(v, v));
+    const double vn = sqrt(fgr_dot3(v, v));
     if (vn == 0.0) return;
     v[0] = v[0] / vn; v[1] = v[1] / vn; v[2] = v[2] / vn;
     cross3(m1, v, w);
-    bins[0] = angle_bin(dot3(m1, m2), dot3(w, m2));
-    bins[1] = lin_bin(dot3(v, m2));
+    bins[0] = angle_bin(fgr_dot3(m1, m2), fgr_dot3(w, m2));
+    bins[1] = lin_bin(fgr_dot3(v, m2));
     bins[2] = lin_bin(f2);
 }
 
@@ -526,19 +500,6 @@ __global__ __launch_bounds__(256) void fgr_nn_kernel(FgrBufs f) {
     if (q < nq) f.nn[(long long)c * f.cap + q] = bi;
 }
 
-__device__ __forceinline__ unsigned long long splitmix(unsigned long long x) {
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ double dist3(const double* a, const double* b) {
-    const double d[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
-    return sqrt(dot3(d, d));
-}
-
 __global__ __launch_bounds__(1024) void fgr_match_kernel(FgrBufs f) {
     const int b = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
     __shared__ int wsum[16];
@@ -572,15 +533,15 @@ __global__ __launch_bounds__(1024) void fgr_match_kernel(FgrBufs f) {
             bool ok = false;
             int r[3] = {0, 0, 0};
             if (t < trials) {
-                for (int k = 0; k < 3; ++k) r[k] = (int)(splitmix(base + (unsigned long long)t * 3ull + (unsigned long long)k) % (unsigned long long)nc);
+                for (int k = 0; k < 3; ++k) r[k] = (int)(fgr_splitmix(base + (unsigned long long)t * 3ull + (unsigned long long)k) % (unsigned long long)nc);
                 const double* a0 = ps + 3 * corr[2 * r[0]];
                 const double* a1 = ps + 3 * corr[2 * r[1]];
                 const double* a2 = ps + 3 * corr[2 * r[2]];
                 const double* c0 = pt + 3 * corr[2 * r[0] + 1];
                 const double* c1 = pt + 3 * corr[2 * r[1] + 1];
                 const double* c2 = pt + 3 * corr[2 * r[2] + 1];
-                const double li[3] = {dist3(a0, a1), dist3(a1, a2), dist3(a2, a0)};
-                const double lj[3] = {dist3(c0, c1), dist3(c1, c2), dist3(c2, c0)};
+                const double li[3] = {fgr_dist3(a0, a1), fgr_dist3(a1, a2), fgr_dist3(a2, a0)};
+                const double lj[3] = {fgr_dist3(c0, c1), fgr_dist3(c1, c2), fgr_dist3(c2, c0)};
                 ok = true;
                 for (int k = 0; k < 3; ++k) ok = ok && (li[k] * kTupleScale < lj[k]) && (lj[k] < li[k] / kTupleScale);
             }
@@ -639,11 +600,11 @@ __global__ __launch_bounds__(256) void fgr_optimize_kernel(FgrBufs f) {
     double mx = 0.0;
     for (int i = tid; i < ns; i += 256) {
         const double d[3] = {ps[3 * i] - ms[0], ps[3 * i + 1] - ms[1], ps[3 * i + 2] - ms[2]};
-        mx = fmax(mx, sqrt(dot3(d, d)));
+        mx = fmax(mx, sqrt(fgr_dot3(d, d)));
     }
     for (int i = tid; i < nt; i += 256) {
         const double d[3] = {pt[3 * i] - mt[0], pt[3 * i + 1] - mt[1], pt[3 * i + 2] - mt[2]};
-        mx = fmax(mx, sqrt(dot3(d, d)));
+        mx = fmax(mx, sqrt(fgr_dot3(d, d)));
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) mx = fmax(mx, rp_shfl_xor_d(mx, m));
@@ -667,7 +628,7 @@ __global__ __launch_bounds__(256) void fgr_optimize_kernel(FgrBufs f) {
             double q[3];
             for (int a = 0; a < 3; ++a) q[a] = ((R[3 * a] * q0[0] + R[3 * a + 1] * q0[1]) + R[3 * a + 2] * q0[2]) + t[a];
             const double r[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
-            const double w = par / (dot3(r, r) + par);
+            const double w = par / (fgr_dot3(r, r) + par);
             const double s = w * w;
             const double J[3][6] = {{0, -q[2], q[1], -1, 0, 0}, {q[2], 0, -q[0], 0, -1, 0}, {-q[1], q[0], 0, 0, 0, -1}};
             int k = 0;
@@ -779,6 +740,17 @@ bool fgr_plan(int B, int P, int cap, FgrPlan& p) {
 
 }  // namespace
 
+void fgr_front_end(const FgrBufs& f, hipStream_t s) {
+    const int C = f.n_clouds, N = f.cap;
+    const dim3 per_point((N + 255) / 256, C), per_point64((N + 63) / 64, C);
+    hipLaunchKernelGGL(fgr_voxel_kernel, dim3(C), dim3(1024), 0, s, f);
+    hipLaunchKernelGGL(fgr_neighbors_kernel, dim3(std::min(N, 1024), C), dim3(64), 0, s, f);
+    hipLaunchKernelGGL(fgr_normals_kernel, per_point, dim3(256), 0, s, f);
+    hipLaunchKernelGGL(fgr_spfh_kernel, per_point64, dim3(64), 0, s, f);
+    hipLaunchKernelGGL(fgr_fpfh_kernel, per_point, dim3(256), 0, s, f);
+    hipLaunchKernelGGL(fgr_nn_kernel, per_point, dim3(256), 0, s, f);
+}
+
 extern "C" {
 
 size_t relpose_fgr_workspace_bytes(int32_t n_pairs, int32_t n_points, int32_t max_points) {
@@ -824,13 +796,7 @@ int relpose_fgr(const RelposeFgrArgs* args_in) {
     f.pose = a.pose;
     f.status = a.status;
     f.seed = a.seed;
-    const dim3 per_point((N + 255) / 256, C), per_point64((N + 63) / 64, C);
-    hipLaunchKernelGGL(fgr_voxel_kernel, dim3(C), dim3(1024), 0, s, f);
-    hipLaunchKernelGGL(fgr_neighbors_kernel, dim3(std::min(N, 1024), C), dim3(64), 0, s, f);
-    hipLaunchKernelGGL(fgr_normals_kernel, per_point, dim3(256), 0, s, f);
-    hipLaunchKernelGGL(fgr_spfh_kernel, per_point64, dim3(64), 0, s, f);
-    hipLaunchKernelGGL(fgr_fpfh_kernel, per_point, dim3(256), 0, s, f);
-    hipLaunchKernelGGL(fgr_nn_kernel, per_point, dim3(256), 0, s, f);
+    fgr_front_end(f, s);
     hipLaunchKernelGGL(fgr_match_kernel, dim3(B), dim3(1024), 0, s, f);
     hipLaunchKernelGGL(fgr_optimize_kernel, dim3(B), dim3(256), 0, s, f);
     RP_CHECK_LAUNCH();

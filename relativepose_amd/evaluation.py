@@ -194,15 +194,30 @@ def evaluate_fgs(batches, device, dataset, result_path=None, max_points=None, se
     of both views (util.depth2pc_dev, as _default_record builds them), ONE batched FPFH + fast global registration call per batch
     (baselines.fast_global_registration_dev), then per pair the overlap statistics; pairs with overlap < 0.1 are skipped without a
     record (evaluation.py:190-191).  Returns the record list (the reference's keys + 'status'); written to result_path if given."""
+    from . import _lib, baselines
+    reg = lambda pcs, valid: baselines.fast_global_registration_dev(pcs, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)[:2]
+    return _evaluate_baseline(batches, device, dataset, reg, result_path)
+
+
+def evaluate_gs(batches, device, dataset, result_path=None, max_points=None, seed=0):
+    """The reference's `--method gs` loop: as evaluate_fgs, with ONE batched FPFH + RANSAC call per batch
+    (baselines.global_registration_dev, baselines.py:52-81)."""
+    from . import _lib, baselines
+    reg = lambda pcs, valid: baselines.global_registration_dev(pcs, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)[:2]
+    return _evaluate_baseline(batches, device, dataset, reg, result_path)
+
+
+def _evaluate_baseline(batches, device, dataset, register, result_path):
+    """register(pcs, valid) -> (pose [B,4,4], status [B]) tensors for the observed-block clouds of a batch."""
     import torch
-    from . import _lib, baselines, util
+    from . import util
     stats = []
     for batch in batches:
         n = _batch_size(batch)
         sub = _batch_take(batch, np.arange(n))
         depth = torch.from_numpy(np.ascontiguousarray(sub["depth"].reshape(2 * n, *sub["depth"].shape[2:]))).to(device)
         pcs, valid = util.depth2pc_dev(depth, dataset)
-        pose, status, _ = baselines.fast_global_registration_dev(pcs, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)
+        pose, status = register(pcs, valid)
         pose, status = pose.cpu().numpy(), status.cpu().numpy()
         pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
         for q in range(n):
@@ -375,17 +390,20 @@ def main(argv=None):
     ap.add_argument("--precision", choices=["f32", "bf16x9", "bf16x6", "f16x3", "bf16x3", "f16"], default="f32",
                     help="conv arithmetic of SCNet (SCNet.set_precision): f32 = the fp32 MFMA kernels (default), bf16x6 = what bench.py runs configs 1-3 in")
     ap.add_argument("--completion", type=int, default=1, choices=[0, 1], help="0 = the reference's 'ours_nc' method (evaluation.py:74): observed-region keypoints only")
-    ap.add_argument("--method", choices=["ours", "fgs"], default="ours",
-                    help="fgs = the reference's fast global registration baseline (baselines.py:83-106) on the observed clouds: no network")
+    ap.add_argument("--method", choices=["ours", "fgs", "gs"], default="ours",
+                    help="fgs = the reference's fast global registration baseline (baselines.py:83-106), gs = its RANSAC global registration "
+                         "baseline (baselines.py:52-81), both on the observed clouds: no network")
     args = ap.parse_args(argv)
 
-    if args.method == "fgs":
+    if args.method in ("fgs", "gs"):
+        m = args.method
         if args.gpus > 1:
-            raise SystemExit("--method fgs runs on one GPU (--gpus 1): the baseline is not sharded")
+            raise SystemExit(f"--method {m} runs on one GPU (--gpus 1): the baseline is not sharded")
         if args.dataset == "scannet":
-            raise SystemExit("--method fgs: the synthetic ScanNet pairs have no full-resolution depth, which the reference's baselines use "
-                             "(util.parse_data(..., 'scannet', 'fgs')); run real 480x640 frames through util.parse_data and "
-                             "baselines.open3d_fast_global_registration")
+            fn = "open3d_fast_global_registration" if m == "fgs" else "open3d_global_registration"
+            raise SystemExit(f"--method {m}: the synthetic ScanNet pairs have no full-resolution depth, which the reference's baselines use "
+                             f"(util.parse_data(..., 'scannet', '{m}')); run real 480x640 frames through util.parse_data and "
+                             f"baselines.{fn}")
         import torch
         from . import _lib
         dev = _lib.require_gpu()
@@ -394,10 +412,10 @@ def main(argv=None):
                    for k in range(0, args.pairs, args.batch)]
         path = None if args.exp is None else args.exp + ".result.npy"
         t0 = time.perf_counter()
-        stats = evaluate_fgs(batches, dev, args.dataset, result_path=path)
+        stats = (evaluate_fgs if m == "fgs" else evaluate_gs)(batches, dev, args.dataset, result_path=path)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(json.dumps({"method": "fgs", "pairs": args.pairs, "records": len(stats), "seconds": dt, "result_file": path,
+        print(json.dumps({"method": m, "pairs": args.pairs, "records": len(stats), "seconds": dt, "result_file": path,
                           "dataset": args.dataset, "stats": summarize(stats)}), flush=True)
         return
 

@@ -29,6 +29,7 @@ Operator                    replaces (reference file:line)
   keypoints_reference       rputil.getKeypoint / getKeypoint_kinect behind the SIFT detector, rputil.py:141-353 (batched, per level)
   sift_detect               the SIFT detector behind them: cv2 SIFT_create(contrastThreshold=0.02) keypoint positions, rputil.py:152-172, :253-265
   fast_global_registration  the fgs baseline: FPFH + fast global registration, baselines.py:83-106 (batched over pairs)
+  global_registration       the gs baseline: FPFH + RANSAC over feature matches, baselines.py:52-81 (batched over pairs)
   affinity_topk             rpmodule.py:342-379
   match_pairs               RelativePoseEstimation_helper, rpmodule.py:317-508
 """
@@ -63,6 +64,7 @@ _lib.define("keypoints_reference(Tensor f, int feat_off, Tensor q_src, Tensor q_
 _lib.define("sift_detect(Tensor images, int[] crop, int max_kp) -> (Tensor, Tensor)")
 # pc f64 [2B,P,3], valid u8 [2B,P] (cloud 2b = source of pair b) -> pose [B,4,4] f64, status [B] i32
 _lib.define("fast_global_registration(Tensor pc, Tensor valid, int max_points=32768, int seed=0) -> (Tensor, Tensor)")
+_lib.define("global_registration(Tensor pc, Tensor valid, int max_points=32768, int seed=0) -> (Tensor, Tensor)")
 _lib.define("affinity_topk(Tensor feat_s, Tensor weight_s, Tensor feat_t, Tensor weight_t, Tensor ns, Tensor nt, "
             "float[] params, int topK, bool want_wij) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("match_pairs(Tensor pc_s, Tensor normal_s, Tensor feat_s, Tensor weight_s, Tensor pc_t, Tensor normal_t, "
@@ -150,6 +152,12 @@ def _fast_global_registration(pc, valid, max_points=32768, seed=0):
     return pose, status
 
 
+def _global_registration(pc, valid, max_points=32768, seed=0):
+    from . import baselines as _bl
+    pose, status, _ = _bl.global_registration_dev(pc, valid, max_points=int(max_points), seed=int(seed))
+    return pose, status
+
+
 def _affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     wij, cj, cw, keff = _rp.affinity_topk(feat_s.contiguous(), weight_s.contiguous(), feat_t.contiguous(), weight_t.contiguous(),
                                           ns.contiguous(), nt.contiguous(), _para(params, topK), want_wij=bool(want_wij))
@@ -168,7 +176,8 @@ def _match_pairs(pc_s, normal_s, feat_s, weight_s, pc_t, normal_t, feat_t, weigh
 for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scnet_forward_out), ("apply_mask", _apply_mask), ("build_view", _build_view), ("warp", _warp),
                    ("warp_pairs_", _warp_pairs_), ("pano2pc", _pano2pc), ("pose_inverse", _pose_inverse),
                    ("sample_primitives", _sample_primitives), ("keypoints_reference", _keypoints_reference), ("affinity_topk", _affinity_topk), ("match_pairs", _match_pairs),
-                   ("sift_detect", _sift_detect), ("fast_global_registration", _fast_global_registration)):
+                   ("sift_detect", _sift_detect), ("fast_global_registration", _fast_global_registration),
+                   ("global_registration", _global_registration)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -229,6 +238,11 @@ def _m_fast_global_registration(pc, valid, max_points=32768, seed=0):
     return pc.new_empty(B, 4, 4, dtype=torch.float64), pc.new_empty(B, dtype=torch.int32)
 
 
+def _m_global_registration(pc, valid, max_points=32768, seed=0):
+    B = pc.shape[0] // 2
+    return pc.new_empty(B, 4, 4, dtype=torch.float64), pc.new_empty(B, dtype=torch.int32)
+
+
 def _m_affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     B, ns_max, nt_max = feat_s.shape[0], feat_s.shape[1], feat_t.shape[1]
     wij = feat_s.new_empty(B, ns_max, nt_max, dtype=torch.float32) if want_wij else feat_s.new_empty(0)
@@ -244,8 +258,9 @@ def _m_match_pairs(pc_s, normal_s, feat_s, weight_s, pc_t, normal_t, feat_t, wei
 for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m_scnet_forward_out), ("apply_mask", _m_apply_mask), ("build_view", _m_build_view),
                    ("warp", _m_warp), ("warp_pairs_", _m_warp_pairs_), ("pano2pc", _m_pano2pc), ("pose_inverse", _m_pose_inverse),
                    ("sample_primitives", _m_sample_primitives), ("keypoints_reference", _m_keypoints_reference), ("affinity_topk", _m_affinity_topk),
-                   ("match_pairs", _m_match_pairs), ("sift_detect", _m_sift_detect), ("fast_global_registration", _m_fast_global_registration)):
+                   ("match_pairs", _m_match_pairs), ("sift_detect", _m_sift_detect), ("fast_global_registration", _m_fast_global_registration),
+                   ("global_registration", _m_global_registration)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
-       "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration")
+       "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration")
