@@ -2916,13 +2916,18 @@ void build_plan(RelposeSCNet* net, int n, Builder& R) {
     if (RP_ENV("RELPOSE_GEMM_HEADS") || (net->S != 15 && net->S != 21)) {   // generic implicit-GEMM path (5 members)
         if (R.pose_only) R.rc = RELPOSE_EINVAL;                               // (pose-only plans need the fused heads kernel: S = 15 / 21)
         const int ooff[5] = {0, 3, 6, 7, 7 + net->S};
-        R.begin_group();
-        for (int m = 0; m < 5; ++m) {
-            if (!wanted(m)) continue;
-            if (m < 3) { sk = R.src("A1", 2 * m * 32, 32); R.conv(std::string("deconv1") + heads[m], R.src("D2", d2off[m], 32), &sk, 224, "OUT", ooff[m]); }
-            else R.conv(std::string("deconv1") + heads[m], R.src("D2", d2off[m], 64), nullptr, 224, "OUT", ooff[m]);
+        // a group's members share one tile config (end_group): heads of another cout_pad -- the semantic head from S = 33 on (64, the
+        // others 32) -- form a group of their own
+        for (int cp = 32; cp <= 64; cp *= 2) {
+            R.begin_group();
+            for (int m = 0; m < 5; ++m) {
+                const auto L = net->layers.find(std::string("deconv1") + heads[m]);
+                if (!wanted(m) || L == net->layers.end() || L->second.cout_pad != cp) continue;
+                if (m < 3) { sk = R.src("A1", 2 * m * 32, 32); R.conv(std::string("deconv1") + heads[m], R.src("D2", d2off[m], 32), &sk, 224, "OUT", ooff[m]); }
+                else R.conv(std::string("deconv1") + heads[m], R.src("D2", d2off[m], 64), nullptr, 224, "OUT", ooff[m]);
+            }
+            R.end_group();
         }
-        R.end_group();
     } else {
         Op o; o.type = OP_HEADS; o.first = o.count = o.cfg = 0; R.plan->ops.push_back(o);
         R.plan->heads_snap_off = R.plan->snap_floats;              // the heads' skip-half accumulators (HeadsDesc::snap): 12 floats per pixel
@@ -3059,9 +3064,10 @@ int relpose_scnet_finalize(RelposeSCNet* net) {
         float* bh = blob.data() + net->bh_off;
         const char* hn[5] = {"rgb", "n", "d", "s", "f"};
         const int hc[5] = {3, 3, 1, net->S, 32};
-        if (net->S > 24) return RELPOSE_EINVAL;
+        // (the image holds a semantic head of up to 24 channels and the bias 64 outputs; only S = 15 / 21 run heads_kernel -- any other S
+        // runs the heads as implicit-GEMM groups with their own packed weights and leaves this image zero)
         int ob = 0;
-        for (int m = 0; m < 5; ++m) {
+        for (int m = 0; m < 5 && net->S <= 24; ++m) {
             if (!((net->omask >> m) & 1)) { ob += hc[m]; continue; }       // a head that was not constructed: zero weights and bias, its channels come out 0
             const float* W = net->params[std::string("deconv1") + hn[m] + ".weight"].data();     // [Cout][64]
             const float* Bv = net->params[std::string("deconv1") + hn[m] + ".bias"].data();

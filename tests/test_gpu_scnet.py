@@ -15,22 +15,11 @@ import pytest
 from cases import SCNET_CASES, SCNET_VARIANT_CASES
 from gpu_util import log
 from oracle.scnet_oracle import SCNetOracle
+from scnet_f64 import TAP_MAP
 from relativepose_amd import weights
 from test_oracle_golden import oracle_scnet_input
 
 pytestmark = pytest.mark.gpu
-
-# buffer -> list of (oracle tap name, call index, channel offset, channels)
-TAP_MAP = {
-    "A1": [("conv1rgb", 0, 0, 32), ("conv1rgb", 1, 32, 32), ("conv1n", 0, 64, 32), ("conv1n", 1, 96, 32), ("conv1d", 0, 128, 32), ("conv1d", 1, 160, 32)],
-    "A2": [("conv2rgb", 0, 0, 64), ("conv2rgb", 1, 64, 64), ("conv2n", 0, 128, 64), ("conv2n", 1, 192, 64), ("conv2d", 0, 256, 64), ("conv2d", 1, 320, 64)],
-    "A3": [("conv3rgb", 0, 0, 128), ("conv3rgb", 1, 128, 128), ("conv3n", 0, 256, 128), ("conv3n", 1, 384, 128), ("conv3d", 0, 512, 128), ("conv3d", 1, 640, 128)],
-    "A4": [("conv4", 0, 0, 256)], "A5": [("conv5", 0, 0, 512)], "A6": [("conv6", 0, 0, 512)], "A7": [("conv7", 0, 0, 512)],
-    "A8": [("conv8", 0, 0, 512)], "A9": [("conv9", 0, 0, 1024)], "D9": [("deconv9", 0, 0, 512)], "D8": [("deconv8", 0, 0, 512)],
-    "D7": [("deconv7", 0, 0, 512)], "D6": [("deconv6", 0, 0, 512)], "D5": [("deconv5", 0, 0, 256)], "D4": [("deconv4", 0, 0, 128)],
-    "D3": [("deconv3rgb", 0, 0, 64), ("deconv3n", 0, 64, 64), ("deconv3d", 0, 128, 64), ("deconv3s", 0, 192, 64), ("deconv3f", 0, 256, 64)],
-    "D2": [("deconv2rgb", 0, 0, 32), ("deconv2n", 0, 32, 32), ("deconv2d", 0, 64, 32), ("deconv2s", 0, 96, 64), ("deconv2f", 0, 160, 64)],
-}
 
 
 class TapOracle(SCNetOracle):
