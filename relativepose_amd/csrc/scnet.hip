@@ -19,6 +19,7 @@
 //    concatenated buffer; conv1 (K = 18/36) and the five 1x1 heads have their own direct kernels;
 //  * bilinear resize kernels (align_corners=False) in and out.
 #include "common.h"
+#include "matcher_internal.h"      // g_rp_tune
 #include <map>
 #include <string>
 #include <vector>
@@ -1700,8 +1701,10 @@ constexpr int HEADS_W = 4352;
 // heads workgroup fits where a conv workgroup does not) -- the working hypothesis; the converse experiment, head / tail launches padded with unused
 // LDS so that they need more than one freed conv slot (conv1 +6 / +12 KB, heads and resize_out +8 KB), changed nothing at configs[1] (675.0 / 674.2
 // base, 673.6, 676.2, 676.3, 673.1) and cost 2.7 % at configs[2]: not kept either (tools/gpu_r5_pads.sh).
+// The lane-per-pixel kernel (rounds 1-6): every lane fetches its own pixel's 128-byte lines and stores its own output row.  Kept as the bitwise
+// reference and the A arm of heads_kernel below (relpose_set_tuning(RELPOSE_TUNE_HEADS_KERNEL, 1)).
 template <int S, bool POSE = false>      // POSE (RELPOSE_FWD_POSE_OUTPUTS): the n, d and f heads only; rgb and semantic channels are written as zeros
-__global__ __launch_bounds__(256) void heads_kernel(const HeadsDesc hd) {
+__global__ __launch_bounds__(256) void heads_lanepix_kernel(const HeadsDesc hd) {
     __shared__ __attribute__((aligned(16))) float wl[HEADS_W];
     __shared__ float2 ssl[320];                        // scale/shift of this block's BatchNorm group
     constexpr int cf = 7 + S + 32;
@@ -1811,6 +1814,187 @@ __global__ __launch_bounds__(256) void heads_kernel(const HeadsDesc hd) {
     float* o = hd.out + pix * cf;
 #pragma unroll
     for (int k = 0; k < cf / 2; ++k) *reinterpret_cast<float2*>(o + 2 * k) = make_float2(r[2 * k], r[2 * k + 1]);
+}
+
+// The streamed kernel (the default): the arithmetic of heads_lanepix_kernel -- one lane per pixel, every output's fused-multiply-add chain in the
+// same order, so the same bits -- with all global traffic coalesced through LDS.  A wave owns 64 consecutive pixels: their D2 rows are one
+// contiguous 56 KB run, their OUT rows one 13.5 KB run, their snapshot rows one 3 KB run.
+//  * Loads: a line-set (the same 32-channel block = 128-byte line of the wave's 64 pixels, 8 KB) is fetched by 8 global_load_dwordx4 per lane
+//    with 8 consecutive lanes on the 8 16-byte pieces of one line (a wave instruction = 8 whole lines, not 64 sixteen-byte pieces of 64 lines),
+//    staged in registers and written to the wave's own 8 KB LDS buffer; two line-sets are in flight (two register sets, alternating) under
+//    the arithmetic of a third.  LDS slot of (pixel p, piece q) = p * 8 + (q ^ ((p >> 1) & 7)): the XOR is applied on the global-address side,
+//    the ds_write_b128 of a wave is one contiguous 1 KB, and the lane-per-pixel ds_read_b128 is conflict-free (the 16 lanes of a read group
+//    cover the 16 sixteen-byte bank slots once; a plain 128-byte row stride would put them on two).
+//  * Stores: bias / tanh results go to the wave's LDS buffer in OUT's NHWC order, 32 pixels at a time (32 rows of cf floats <= 8 KB), and leave
+//    as contiguous 16-byte stores; the snapshot rows (12 floats per pixel) are written and read the same way.
+//  * A wave only ever touches its own LDS buffer, so the hand-overs need wave-level ordering only (LDS operations of a wave execute in order):
+//    no workgroup barrier after the weights are in place.
+__device__ __forceinline__ void rp_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// Occupancy: 3 waves per SIMD (<= 168 VGPRs; three 51.75 KB workgroups fill a CU's LDS); -DRP_HEADS_WAVES=2 builds the 2-wave variant (240 VGPRs) for A/B
+// runs: 949 against 901 us per call alone and 38.84 against 38.79 ms per bench step in the loop (parent 39.22; profiles/heads_stream_bench.txt) -- here the
+// lower-register kernel is the better neighbour too, unlike the round-5 experiment above heads_lanepix_kernel.
+#ifndef RP_HEADS_WAVES
+#define RP_HEADS_WAVES 3
+#endif
+template <int S, bool POSE = false>
+__global__ __launch_bounds__(256, RP_HEADS_WAVES) void heads_kernel(const HeadsDesc hd) {
+    __shared__ __attribute__((aligned(16))) float wl[HEADS_W];
+    __shared__ float2 ssl[320];                        // scale/shift of this block's BatchNorm group
+    __shared__ float bl[64];                           // bias (the epilogue's 7 + S + 32 adds read it here: from global memory every one was a trip to L2 of its own)
+    __shared__ __attribute__((aligned(16))) float4 xl[4][512];          // per wave: one line-set (64 pixels x 8 pieces) / 32 output rows / 64 snapshot rows
+    constexpr int cf = 7 + S + 32;
+    static_assert(32 * cf <= 512 * 4 && (cf & 1) == 0, "32 output rows fit the wave's buffer");
+    const size_t pix0 = (size_t)blockIdx.x * 256;      // 256 consecutive pixels: one image, one BatchNorm group
+    const int g = (int)(pix0 / ((size_t)RS * RS)) >> 1;
+    // weights and scale/shift: every load issued before the first wait (one trip to L2, not nine), then the first two line-sets
+    static_assert(HEADS_W == 17 * 256, "17 weights per thread");
+    float wv[17];
+#pragma unroll
+    for (int k = 0; k < 17; ++k) wv[k] = hd.w[k * 256 + threadIdx.x];
+    const float bv = threadIdx.x < 64 ? hd.bias[threadIdx.x] : 0.f;
+    float2 ssv[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        // A1 skip blocks: channels [0:32] (rgb self), [64:96] (n self), [128:160] (d self) of the 192-channel buffer
+        const int i = k * 256 + threadIdx.x;
+        if (i < 320) ssv[k] = i < 224 ? hd.ss_d2[(size_t)g * 224 + i] : hd.ss_a1[(size_t)g * 192 + ((i - 224) >> 5) * 64 + ((i - 224) & 31)];
+    }
+    const int lane = threadIdx.x & 63;
+    const size_t wpix0 = pix0 + (threadIdx.x & ~63);   // the wave's first pixel
+    float4* const xw = xl[threadIdx.x >> 6];
+    // fetch side: lane = (pixel lane >> 3 of each group of 8 rows, stored piece lane & 7); row group k = 0..7 holds pixels 8k .. 8k + 7, whose
+    // swizzle ((p >> 1) & 7) is (lane >> 4) ^ (4 * (k & 1)): one lane offset for the even and one for the odd row groups
+    const int fo_e = 4 * ((lane & 7) ^ (lane >> 4)), fo_o = fo_e ^ 16;
+    const float* const gd = hd.d2 + (wpix0 + (lane >> 3)) * 224;
+    const float* const ga = hd.a1 + (wpix0 + (lane >> 3)) * 192;
+    // arithmetic side: the lane's pixel row and its swizzle
+    const float4* const xrow = xw + lane * 8;
+    const int sw = (lane >> 1) & 7;
+    rp_v2f a3[6], as_[12], af[16];                     // rgb 0:3 | n 4:7 | d 8:11 (padded quads), s, f: as in heads_lanepix_kernel
+#pragma unroll
+    for (int o = 0; o < 6; ++o) a3[o] = (rp_v2f){0.f, 0.f};
+#pragma unroll
+    for (int o = 0; o < 12; ++o) as_[o] = (rp_v2f){0.f, 0.f};
+#pragma unroll
+    for (int o = 0; o < 16; ++o) af[o] = (rp_v2f){0.f, 0.f};
+#define RP_HS_FETCH(X8, BASE, STRIDE, C0)                                                                 \
+    { _Pragma("unroll") for (int k = 0; k < 8; ++k) X8[k] = rp_ldg4((BASE) + (size_t)k * 8 * (STRIDE) + (C0) + ((k & 1) ? fo_o : fo_e)); }
+#define RP_HS_FETCH_D2(X8, C0) RP_HS_FETCH(X8, gd, 224, C0)
+#define RP_HS_FETCH_A1(X8, C0) RP_HS_FETCH(X8, ga, 192, C0)
+    // one line-set: registers -> LDS, the set after next -> the registers just freed, then the arithmetic of heads_lanepix_kernel's RP_HEAD_LINE
+    // on the lane's row (the next piece is read from LDS under the current one's multiply-adds)
+#define RP_HS_LINE(X8, NEXT, SSROW, WOFF, WSTRIDE, NQ4, ACC, OBASE)                                       \
+    {                                                                                                    \
+        _Pragma("unroll") for (int k = 0; k < 8; ++k) xw[k * 64 + lane] = X8[k];                         \
+        rp_wave_lds_sync();                                                                              \
+        NEXT                                                                                             \
+        float4 xn = xrow[sw];                                                                            \
+        _Pragma("unroll 1") for (int q = 0; q < 8; ++q) {                                                \
+            const float4 x4 = xn;                                                                        \
+            xn = xrow[((q + 1) & 7) ^ sw];                                                               \
+            const float xv[4] = {x4.x, x4.y, x4.z, x4.w};                                                \
+            _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                              \
+                const float2 sc = ssl[(SSROW) + q * 4 + t];                                              \
+                const float v = lrelu(xv[t] * sc.x + sc.y, LRELU);                                       \
+                const rp_v2f vv = {v, v};                                                                \
+                _Pragma("unroll") for (int j = 0; j < (NQ4); ++j) {                                      \
+                    const float4 w4 = *reinterpret_cast<const float4*>(&wl[(WOFF) + (q * 4 + t) * (WSTRIDE) + j * 4]); \
+                    ACC[(OBASE) / 2 + j * 2 + 0] = __builtin_elementwise_fma(vv, (rp_v2f){w4.x, w4.y}, ACC[(OBASE) / 2 + j * 2 + 0]); \
+                    ACC[(OBASE) / 2 + j * 2 + 1] = __builtin_elementwise_fma(vv, (rp_v2f){w4.z, w4.w}, ACC[(OBASE) / 2 + j * 2 + 1]); \
+                }                                                                                        \
+            }                                                                                            \
+        }                                                                                                \
+        rp_wave_lds_sync();                                                                              \
+    }
+#define RP_HS_SKIP(X8, NEXT, M_) RP_HS_LINE(X8, NEXT, 224 + (M_) * 32, (96 + (M_) * 32) * 4, 4, 1, a3, (M_) * 4)
+#define RP_HS_D2(X8, NEXT, M_) RP_HS_LINE(X8, NEXT, (M_) * 32, ((M_) * 32) * 4, 4, 1, a3, (M_) * 4)
+    // line-set order as in heads_lanepix_kernel: A1 skip sets of [rgb,] n, d (the snapshot point), then the D2 sets of [rgb,] n, d, [s: 2,] f: 2
+    float4 xa[8], xb[8];
+    float* const snw = hd.snap + wpix0 * 12;           // the wave's 64 snapshot rows: 192 float4, contiguous
+#pragma unroll
+    for (int k = 0; k < 17; ++k) wl[k * 256 + threadIdx.x] = wv[k];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) if (k * 256 + threadIdx.x < 320) ssl[k * 256 + threadIdx.x] = ssv[k];
+    if (threadIdx.x < 64) bl[threadIdx.x] = bv;
+    __syncthreads();                                   // the only workgroup barrier
+    if (hd.snap_mode == 2) {
+        float4 sv[3];
+#pragma unroll
+        for (int m = 0; m < 3; ++m) sv[m] = rp_ldg4(snw + (m * 64 + lane) * 4);
+        if constexpr (POSE) { RP_HS_FETCH_D2(xa, 32) RP_HS_FETCH_D2(xb, 64) } else { RP_HS_FETCH_D2(xb, 0) RP_HS_FETCH_D2(xa, 32) }
+#pragma unroll
+        for (int m = 0; m < 3; ++m) xw[m * 64 + lane] = sv[m];
+        rp_wave_lds_sync();
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            const float4 v = xw[lane * 3 + m];
+            a3[2 * m] = (rp_v2f){v.x, v.y}; a3[2 * m + 1] = (rp_v2f){v.z, v.w};
+        }
+        rp_wave_lds_sync();
+    } else {
+        if constexpr (POSE) { RP_HS_FETCH_A1(xa, 64) RP_HS_FETCH_A1(xb, 128) } else { RP_HS_FETCH_A1(xa, 0) RP_HS_FETCH_A1(xb, 64) }
+        if constexpr (POSE) {
+            RP_HS_SKIP(xa, RP_HS_FETCH_D2(xa, 32), 1)
+            RP_HS_SKIP(xb, RP_HS_FETCH_D2(xb, 64), 2)
+        } else {
+            RP_HS_SKIP(xa, RP_HS_FETCH_A1(xa, 128), 0)
+            RP_HS_SKIP(xb, RP_HS_FETCH_D2(xb, 0), 1)
+            RP_HS_SKIP(xa, RP_HS_FETCH_D2(xa, 32), 2)
+        }
+        if (hd.snap_mode == 1) {
+#pragma unroll
+            for (int m = 0; m < 3; ++m) xw[lane * 3 + m] = make_float4(a3[2 * m].x, a3[2 * m].y, a3[2 * m + 1].x, a3[2 * m + 1].y);
+            rp_wave_lds_sync();
+#pragma unroll
+            for (int m = 0; m < 3; ++m) rp_stg4(snw + (m * 64 + lane) * 4, xw[m * 64 + lane]);
+            rp_wave_lds_sync();
+        }
+    }
+    if constexpr (POSE) {
+        RP_HS_D2(xa, RP_HS_FETCH_D2(xa, 160), 1)
+        RP_HS_D2(xb, RP_HS_FETCH_D2(xb, 192), 2)
+        RP_HS_LINE(xa, , 160, 2304, 32, 8, af, 0)                                                                           // f
+        RP_HS_LINE(xb, , 192, 2304 + 32 * 32, 32, 8, af, 0)
+    } else {
+        RP_HS_D2(xb, RP_HS_FETCH_D2(xb, 64), 0)
+        RP_HS_D2(xa, RP_HS_FETCH_D2(xa, 96), 1)
+        RP_HS_D2(xb, RP_HS_FETCH_D2(xb, 128), 2)
+        RP_HS_LINE(xa, RP_HS_FETCH_D2(xa, 160), 96, 768, 24, 6, as_, 0)                                                     // s
+        RP_HS_LINE(xb, RP_HS_FETCH_D2(xb, 192), 128, 768 + 32 * 24, 24, 6, as_, 0)
+        RP_HS_LINE(xa, , 160, 2304, 32, 8, af, 0)                                                                           // f
+        RP_HS_LINE(xb, , 192, 2304 + 32 * 32, 32, 8, af, 0)
+    }
+#undef RP_HS_SKIP
+#undef RP_HS_D2
+#undef RP_HS_LINE
+#undef RP_HS_FETCH_A1
+#undef RP_HS_FETCH_D2
+#undef RP_HS_FETCH
+    // bias, tanh as in heads_lanepix_kernel; then 32 rows at a time through the wave's buffer
+    float r[cf + 1];
+#pragma unroll
+    for (int o = 0; o < 3; ++o) { r[o] = POSE ? 0.f : a3[o >> 1][o & 1] + bl[o]; r[3 + o] = a3[2 + (o >> 1)][o & 1] + bl[3 + o]; }
+    r[6] = a3[4].x + bl[6];
+#pragma unroll
+    for (int o = 0; o < S; ++o) r[7 + o] = POSE ? 0.f : as_[o >> 1][o & 1] + bl[7 + o];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) { const float v = af[k >> 1][k & 1] + bl[7 + S + k]; r[7 + S + k] = hd.use_tanh ? tanhf(v) : v; }
+    float* const xwf = reinterpret_cast<float*>(xw);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if ((lane >> 5) == h) {
+#pragma unroll
+            for (int k = 0; k < cf / 2; ++k) *reinterpret_cast<float2*>(xwf + (lane & 31) * cf + 2 * k) = make_float2(r[2 * k], r[2 * k + 1]);
+        }
+        rp_wave_lds_sync();
+        float* const o = hd.out + (wpix0 + h * 32) * cf;
+        for (int i = lane; i < 8 * cf; i += 64) rp_stg4(o + i * 4, xw[i]);
+        rp_wave_lds_sync();
+    }
 }
 
 // Split-K reduce + BatchNorm partial sums in one pass (round 2): grid (chunk, group, member); a workgroup adds the K slices of a
@@ -3462,11 +3646,15 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
             hd.snap_mode = plan->snap_mode; hd.snap = (float*)(ws + o.snap) + plan->heads_snap_off;
             mark(1);
             const dim3 hg((unsigned)((size_t)n * RS * RS / 256));
+            // RELPOSE_TUNE_HEADS_KERNEL: 0 = the streamed kernel, 1 = the lane-per-pixel kernel (the same bits; tests/test_gpu_heads_stream.py)
+#define RP_HEADS_LAUNCH(S_, POSE_)                                                                                         \
+            { if (lanepix) hipLaunchKernelGGL((heads_lanepix_kernel<S_, POSE_>), hg, dim3(256), 0, s, hd);               \
+              else hipLaunchKernelGGL((heads_kernel<S_, POSE_>), hg, dim3(256), 0, s, hd); }
+            const bool lanepix = g_rp_tune[RELPOSE_TUNE_HEADS_KERNEL] == 1;
             if (plan->pose_only) {
-                if (net->S == 15) hipLaunchKernelGGL((heads_kernel<15, true>), hg, dim3(256), 0, s, hd);
-                else hipLaunchKernelGGL((heads_kernel<21, true>), hg, dim3(256), 0, s, hd);
-            } else if (net->S == 15) hipLaunchKernelGGL((heads_kernel<15, false>), hg, dim3(256), 0, s, hd);
-            else hipLaunchKernelGGL((heads_kernel<21, false>), hg, dim3(256), 0, s, hd);
+                if (net->S == 15) RP_HEADS_LAUNCH(15, true) else RP_HEADS_LAUNCH(21, true)
+            } else if (net->S == 15) RP_HEADS_LAUNCH(15, false) else RP_HEADS_LAUNCH(21, false)
+#undef RP_HEADS_LAUNCH
             mark(-1);
         } else if (op.type == OP_REDUCE) {
             mark(4);
