@@ -430,6 +430,69 @@ typedef struct RelposeRansacArgs {
 size_t relpose_ransac_workspace_bytes(int32_t n_pairs, int32_t n_points, int32_t max_points, int32_t max_iterations, int32_t max_validations);
 int relpose_ransac(const RelposeRansacArgs* args);
 
+/* -------------------------------------------------------------------- coloured ICP (the `cgs` baseline's refinement)
+ * Replaces the three registration_colored_icp levels of open3d_color_registration (baselines.py:110-168; Park, Zhou, Koltun, "Colored
+ * Point Cloud Registration Revisited", ICCV 2017) for a batch of pairs: per level (radius 0.04, 0.02, 0.01 with at most 50, 30, 14
+ * iterations) a coloured voxel grid of both clouds, normals and colour gradients of the target, then Gauss-Newton on the joint
+ * geometric + photometric objective from the previous level's pose, with ICPConvergenceCriteria(1e-6, 1e-6, max_iteration)'s stopping
+ * rule evaluated on the device.  The reference starts it from its RANSAC result (relpose_ransac); any initial pose may be passed.
+ * The contract is DESIGN.md 4.8 (the project's own; Open3D is not a dependency).
+ *   pc, valid        as relpose_fgr (cloud 2b = the source of pair b, 2b + 1 its target)
+ *   color            [2 n_pairs, n_points, 3] f64, the colour of every point (rows with valid == 0 are ignored)
+ *   init             [n_pairs, 4, 4] f64 starting transform (T p_src ~ p_tgt), NULL = the identity
+ *   lambda_geometric weight of the geometric term, 0 .. 1, taken as given (RELPOSE_CICP_LAMBDA_GEOMETRIC = Open3D's default 0.968)
+ *   max_points       voxels kept per cloud and level, 1 .. RELPOSE_FGR_MAX_POINTS_LIMIT
+ *   pose             [n_pairs, 4, 4] f64, T p_src ~ p_tgt; the identity unless status == 0
+ *   status           [n_pairs] i32 RELPOSE_CICP_STATUS_* (too few points: a cloud with fewer than 3 voxels at some level)
+ * Optional per-level outputs (NULL = not written): fitness, inlier_rmse [n_pairs, 3] f64 and n_iterations [n_pairs, 3] i32 (the last
+ *   evaluation of the level and the number of evaluations it made), level_pose [n_pairs, 3, 4, 4] f64 (the pose the level ended with).
+ * Optional stage outputs (NULL = kept in the workspace or not kept), rows past a count and trace slots that were not evaluated are left
+ * unwritten: down_points, down_colors [2 n_pairs, 3, max_points, 3] f64 and down_count [2 n_pairs, 3] i32 (the true voxel count);
+ *   normals, gradient [n_pairs, 3, max_points, 3] f64 (the target's); and the trace over the RELPOSE_CICP_TRACE_SLOTS = 50 + 30 + 14
+ *   iteration slots (level l, iteration k -> slot {0, 50, 80}[l] + k): iter_pose [n_pairs, 94, 4, 4] f64 (the transform the evaluation
+ *   used), iter_ncorr [n_pairs, 94] i32, iter_rmse [n_pairs, 94] f64, iter_corr [n_pairs, 94, max_points] i32 (the target voxel of every
+ *   source voxel, -1 = none) and iter_x [n_pairs, 94, 6] f64 (the step; unwritten where the level ended without one).
+ * Overflow: as relpose_fgr, at any level (status RELPOSE_CICP_STATUS_OVERFLOW, the call returns RELPOSE_CICP_OVERFLOW, other pairs
+ * complete).  This entry point SYNCHRONISES `stream` once at its end; nothing inside the iteration loop waits for the device.  The number
+ * of kernel launches is fixed (4 + 2 x 94).  workspace: relpose_cicp_workspace_bytes(n_pairs, n_points, max_points). */
+#define RELPOSE_CICP_OVERFLOW (-6)
+#define RELPOSE_CICP_LEVELS 3
+#define RELPOSE_CICP_TRACE_SLOTS 94
+#define RELPOSE_CICP_LAMBDA_GEOMETRIC 0.968
+enum { RELPOSE_CICP_STATUS_OK = 0, RELPOSE_CICP_STATUS_FEW_POINTS = 1, RELPOSE_CICP_STATUS_OVERFLOW = 3 };
+typedef struct RelposeCicpArgs {
+    uint32_t struct_size;       /* sizeof(RelposeCicpArgs) as the caller compiled it */
+    int32_t n_pairs;
+    int32_t n_points;
+    int32_t max_points;
+    const double* pc;
+    const uint8_t* valid;
+    const double* color;
+    const double* init;
+    double lambda_geometric;
+    double* pose;
+    int32_t* status;
+    double* fitness;
+    double* inlier_rmse;
+    int32_t* n_iterations;
+    double* level_pose;
+    double* down_points;
+    double* down_colors;
+    int32_t* down_count;
+    double* normals;
+    double* gradient;
+    double* iter_pose;
+    int32_t* iter_ncorr;
+    double* iter_rmse;
+    int32_t* iter_corr;
+    double* iter_x;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeCicpArgs;
+size_t relpose_cicp_workspace_bytes(int32_t n_pairs, int32_t n_points, int32_t max_points);
+int relpose_cicp(const RelposeCicpArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

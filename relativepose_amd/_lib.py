@@ -94,6 +94,22 @@ RANSAC_MAX_ITERATIONS_LIMIT = 16777216
 RANSAC_MAX_VALIDATIONS_LIMIT = 4096
 
 
+class CicpArgs(C.Structure):
+    """RelposeCicpArgs (include/relpose.h): the argument block of relpose_cicp."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_pairs", c_int), ("n_points", c_int), ("max_points", c_int), ("pc", c_void_p), ("valid", c_void_p),
+                ("color", c_void_p), ("init", c_void_p), ("lambda_geometric", c_double), ("pose", c_void_p), ("status", c_void_p),
+                ("fitness", c_void_p), ("inlier_rmse", c_void_p), ("n_iterations", c_void_p), ("level_pose", c_void_p),
+                ("down_points", c_void_p), ("down_colors", c_void_p), ("down_count", c_void_p), ("normals", c_void_p), ("gradient", c_void_p),
+                ("iter_pose", c_void_p), ("iter_ncorr", c_void_p), ("iter_rmse", c_void_p), ("iter_corr", c_void_p), ("iter_x", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
+CICP_OVERFLOW = -6                  # RELPOSE_CICP_OVERFLOW
+CICP_LEVELS = 3                     # RELPOSE_CICP_LEVELS
+CICP_TRACE_SLOTS = 94               # RELPOSE_CICP_TRACE_SLOTS
+CICP_LAMBDA_GEOMETRIC = 0.968       # RELPOSE_CICP_LAMBDA_GEOMETRIC
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -132,6 +148,8 @@ SIGNATURES = {
     "relpose_fgr": (c_int, [C.POINTER(FgrArgs)]),
     "relpose_ransac_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "relpose_ransac": (c_int, [C.POINTER(RansacArgs)]),
+    "relpose_cicp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "relpose_cicp": (c_int, [C.POINTER(CicpArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

@@ -18,6 +18,7 @@ SOURCES = [
     ("sift.hip", ["-ffp-contract=off"]),          # the detector and its numpy model must round alike
     ("fgr.hip", ["-ffp-contract=off"]),           # FPFH + FGR: bins and matches must agree with tests/fgr_model.py bit for bit
     ("ransac.hip", ["-ffp-contract=off"]),        # RANSAC: draws, Horn and the validation sums must agree with tests/ransac_model.py
+    ("cicp.hip", ["-ffp-contract=off"]),          # coloured ICP: voxels, correspondences and the reductions must agree with tests/cicp_model.py
     ("scnet.hip", []),
 ]
 

@@ -207,8 +207,26 @@ def evaluate_gs(batches, device, dataset, result_path=None, max_points=None, see
     return _evaluate_baseline(batches, device, dataset, reg, result_path)
 
 
-def _evaluate_baseline(batches, device, dataset, register, result_path):
-    """register(pcs, valid) -> (pose [B,4,4], status [B]) tensors for the observed-block clouds of a batch."""
+def evaluate_cgs(batches, device, dataset, result_path=None, max_points=None, seed=0):
+    """The reference's `--method cgs` loop: as evaluate_gs, with the RANSAC pose of every pair refined by the three coloured ICP levels
+    (baselines.color_registration_dev, baselines.py:110-168).  The colours are the observed block of `rgb` in the clouds' point order,
+    quantised as the reference does: clip(rgb * 255, 0, 255) to uint8 (evaluation.py:168), then / 255 (util.py:53)."""
+    from . import _lib, baselines
+    reg = lambda pcs, valid, colors: baselines.color_registration_dev(pcs, colors, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)[:2]
+    return _evaluate_baseline(batches, device, dataset, reg, result_path, with_colors=True)
+
+
+def observed_colors(rgb):
+    """rgb [n,3,h,4h] float numpy in [0, 1] -> [n, h*h, 3] f64: the observed block (columns h:2h) in util.depth2pc_dev's point order
+    (row-major pixels), through the reference's uint8 quantisation."""
+    h = rgb.shape[2]
+    q = (np.asarray(rgb) * 255).clip(0, 255).astype('uint8')
+    return np.ascontiguousarray(q[:, :, :, h:2 * h].transpose(0, 2, 3, 1).reshape(len(q), h * h, 3)) / 255.
+
+
+def _evaluate_baseline(batches, device, dataset, register, result_path, with_colors=False):
+    """register(pcs, valid) -> (pose [B,4,4], status [B]) tensors for the observed-block clouds of a batch; with_colors: register(pcs,
+    valid, colors [2B,P,3] f64)."""
     import torch
     from . import util
     stats = []
@@ -217,7 +235,11 @@ def _evaluate_baseline(batches, device, dataset, register, result_path):
         sub = _batch_take(batch, np.arange(n))
         depth = torch.from_numpy(np.ascontiguousarray(sub["depth"].reshape(2 * n, *sub["depth"].shape[2:]))).to(device)
         pcs, valid = util.depth2pc_dev(depth, dataset)
-        pose, status = register(pcs, valid)
+        if with_colors:
+            colors = torch.from_numpy(observed_colors(sub["rgb"].reshape(2 * n, *sub["rgb"].shape[2:]))).to(device)
+            pose, status = register(pcs, valid, colors)
+        else:
+            pose, status = register(pcs, valid)
         pose, status = pose.cpu().numpy(), status.cpu().numpy()
         pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
         for q in range(n):
@@ -390,17 +412,17 @@ def main(argv=None):
     ap.add_argument("--precision", choices=["f32", "bf16x9", "bf16x6", "f16x3", "bf16x3", "f16"], default="f32",
                     help="conv arithmetic of SCNet (SCNet.set_precision): f32 = the fp32 MFMA kernels (default), bf16x6 = what bench.py runs configs 1-3 in")
     ap.add_argument("--completion", type=int, default=1, choices=[0, 1], help="0 = the reference's 'ours_nc' method (evaluation.py:74): observed-region keypoints only")
-    ap.add_argument("--method", choices=["ours", "fgs", "gs"], default="ours",
+    ap.add_argument("--method", choices=["ours", "fgs", "gs", "cgs"], default="ours",
                     help="fgs = the reference's fast global registration baseline (baselines.py:83-106), gs = its RANSAC global registration "
-                         "baseline (baselines.py:52-81), both on the observed clouds: no network")
+                         "baseline (baselines.py:52-81), cgs = gs refined by coloured ICP (baselines.py:110-168), all on the observed clouds: no network")
     args = ap.parse_args(argv)
 
-    if args.method in ("fgs", "gs"):
+    if args.method in ("fgs", "gs", "cgs"):
         m = args.method
         if args.gpus > 1:
             raise SystemExit(f"--method {m} runs on one GPU (--gpus 1): the baseline is not sharded")
         if args.dataset == "scannet":
-            fn = "open3d_fast_global_registration" if m == "fgs" else "open3d_global_registration"
+            fn = {"fgs": "open3d_fast_global_registration", "gs": "open3d_global_registration", "cgs": "open3d_color_registration"}[m]
             raise SystemExit(f"--method {m}: the synthetic ScanNet pairs have no full-resolution depth, which the reference's baselines use "
                              f"(util.parse_data(..., 'scannet', '{m}')); run real 480x640 frames through util.parse_data and "
                              f"baselines.{fn}")
@@ -412,7 +434,7 @@ def main(argv=None):
                    for k in range(0, args.pairs, args.batch)]
         path = None if args.exp is None else args.exp + ".result.npy"
         t0 = time.perf_counter()
-        stats = (evaluate_fgs if m == "fgs" else evaluate_gs)(batches, dev, args.dataset, result_path=path)
+        stats = {"fgs": evaluate_fgs, "gs": evaluate_gs, "cgs": evaluate_cgs}[m](batches, dev, args.dataset, result_path=path)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         print(json.dumps({"method": m, "pairs": args.pairs, "records": len(stats), "seconds": dt, "result_file": path,

@@ -30,6 +30,8 @@ Operator                    replaces (reference file:line)
   sift_detect               the SIFT detector behind them: cv2 SIFT_create(contrastThreshold=0.02) keypoint positions, rputil.py:152-172, :253-265
   fast_global_registration  the fgs baseline: FPFH + fast global registration, baselines.py:83-106 (batched over pairs)
   global_registration       the gs baseline: FPFH + RANSAC over feature matches, baselines.py:52-81 (batched over pairs)
+  colored_icp               the three coloured ICP levels of the cgs baseline from a given pose, baselines.py:141-166 (batched over pairs)
+  color_registration        the cgs baseline: the gs RANSAC result refined by coloured ICP, baselines.py:110-168 (batched over pairs)
   affinity_topk             rpmodule.py:342-379
   match_pairs               RelativePoseEstimation_helper, rpmodule.py:317-508
 """
@@ -65,6 +67,9 @@ _lib.define("sift_detect(Tensor images, int[] crop, int max_kp) -> (Tensor, Tens
 # pc f64 [2B,P,3], valid u8 [2B,P] (cloud 2b = source of pair b) -> pose [B,4,4] f64, status [B] i32
 _lib.define("fast_global_registration(Tensor pc, Tensor valid, int max_points=32768, int seed=0) -> (Tensor, Tensor)")
 _lib.define("global_registration(Tensor pc, Tensor valid, int max_points=32768, int seed=0) -> (Tensor, Tensor)")
+# color f64 [2B,P,3]; init f64 [B,4,4] (T p_src ~ p_tgt) -> pose [B,4,4] f64, status [B] i32
+_lib.define("colored_icp(Tensor pc, Tensor color, Tensor valid, Tensor init, float lambda_geometric=0.968, int max_points=32768) -> (Tensor, Tensor)")
+_lib.define("color_registration(Tensor pc, Tensor color, Tensor valid, int max_points=32768, int seed=0, float lambda_geometric=0.968) -> (Tensor, Tensor)")
 _lib.define("affinity_topk(Tensor feat_s, Tensor weight_s, Tensor feat_t, Tensor weight_t, Tensor ns, Tensor nt, "
             "float[] params, int topK, bool want_wij) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("match_pairs(Tensor pc_s, Tensor normal_s, Tensor feat_s, Tensor weight_s, Tensor pc_t, Tensor normal_t, "
@@ -158,6 +163,19 @@ def _global_registration(pc, valid, max_points=32768, seed=0):
     return pose, status
 
 
+def _colored_icp(pc, color, valid, init, lambda_geometric=0.968, max_points=32768):
+    from . import baselines as _bl
+    pose, status, _ = _bl.colored_icp_dev(pc, color, valid, init=init, lambda_geometric=float(lambda_geometric), max_points=int(max_points))
+    return pose, status
+
+
+def _color_registration(pc, color, valid, max_points=32768, seed=0, lambda_geometric=0.968):
+    from . import baselines as _bl
+    pose, status, _ = _bl.color_registration_dev(pc, color, valid, seed=int(seed), lambda_geometric=float(lambda_geometric),
+                                                 max_points=int(max_points))
+    return pose, status
+
+
 def _affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     wij, cj, cw, keff = _rp.affinity_topk(feat_s.contiguous(), weight_s.contiguous(), feat_t.contiguous(), weight_t.contiguous(),
                                           ns.contiguous(), nt.contiguous(), _para(params, topK), want_wij=bool(want_wij))
@@ -177,7 +195,7 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("warp_pairs_", _warp_pairs_), ("pano2pc", _pano2pc), ("pose_inverse", _pose_inverse),
                    ("sample_primitives", _sample_primitives), ("keypoints_reference", _keypoints_reference), ("affinity_topk", _affinity_topk), ("match_pairs", _match_pairs),
                    ("sift_detect", _sift_detect), ("fast_global_registration", _fast_global_registration),
-                   ("global_registration", _global_registration)):
+                   ("global_registration", _global_registration), ("colored_icp", _colored_icp), ("color_registration", _color_registration)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -243,6 +261,16 @@ def _m_global_registration(pc, valid, max_points=32768, seed=0):
     return pc.new_empty(B, 4, 4, dtype=torch.float64), pc.new_empty(B, dtype=torch.int32)
 
 
+def _m_colored_icp(pc, color, valid, init, lambda_geometric=0.968, max_points=32768):
+    B = pc.shape[0] // 2
+    return pc.new_empty(B, 4, 4, dtype=torch.float64), pc.new_empty(B, dtype=torch.int32)
+
+
+def _m_color_registration(pc, color, valid, max_points=32768, seed=0, lambda_geometric=0.968):
+    B = pc.shape[0] // 2
+    return pc.new_empty(B, 4, 4, dtype=torch.float64), pc.new_empty(B, dtype=torch.int32)
+
+
 def _m_affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     B, ns_max, nt_max = feat_s.shape[0], feat_s.shape[1], feat_t.shape[1]
     wij = feat_s.new_empty(B, ns_max, nt_max, dtype=torch.float32) if want_wij else feat_s.new_empty(0)
@@ -259,8 +287,9 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("warp", _m_warp), ("warp_pairs_", _m_warp_pairs_), ("pano2pc", _m_pano2pc), ("pose_inverse", _m_pose_inverse),
                    ("sample_primitives", _m_sample_primitives), ("keypoints_reference", _m_keypoints_reference), ("affinity_topk", _m_affinity_topk),
                    ("match_pairs", _m_match_pairs), ("sift_detect", _m_sift_detect), ("fast_global_registration", _m_fast_global_registration),
-                   ("global_registration", _m_global_registration)):
+                   ("global_registration", _m_global_registration), ("colored_icp", _m_colored_icp), ("color_registration", _m_color_registration)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
-       "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration")
+       "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
+       "color_registration")
