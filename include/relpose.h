@@ -87,9 +87,12 @@ void relpose_default_params(RelposeParams* p_host);
  *                                   reach the tolerance (default), 1 = a test every 8 products (the earlier rule; A/B switch).  The
  *                                   one knob whose settings agree to round-off only (both converge to 1e-13; the number of Lanczos
  *                                   steps differs)
- *   RELPOSE_TUNE_HEADS_KERNEL       0 = SCNet's heads on the streamed kernel (default), 1 = on the lane-per-pixel kernel (same bits) */
+ *   RELPOSE_TUNE_HEADS_KERNEL       0 = SCNet's heads on the streamed kernel (default), 1 = on the lane-per-pixel kernel (same bits)
+ *   RELPOSE_TUNE_DECONV_STRIP       0 = SCNet's split-K deconv4 / deconv5 on the phase strip kernel (default), 1 = on the implicit-GEMM
+ *                                   kernel (same K split, same bits); read when a forward looks up its plan: each value has plans of its own */
 enum { RELPOSE_TUNE_AFFINITY_KERNEL = 0, RELPOSE_TUNE_FIT_MAX_PRODUCTS = 1, RELPOSE_TUNE_FIT_CLUSTER = 2,
-       RELPOSE_TUNE_FIT_GLOBAL_VECTORS = 3, RELPOSE_TUNE_FIT_FIXED_CHECKS = 4, RELPOSE_TUNE_HEADS_KERNEL = 5, RELPOSE_TUNE_COUNT = 8 };
+       RELPOSE_TUNE_FIT_GLOBAL_VECTORS = 3, RELPOSE_TUNE_FIT_FIXED_CHECKS = 4, RELPOSE_TUNE_HEADS_KERNEL = 5, RELPOSE_TUNE_DECONV_STRIP = 6,
+       RELPOSE_TUNE_COUNT = 8 };
 int relpose_set_tuning(int32_t key, int32_t value);
 const char* relpose_version(void);
 /* ------------------------------------------------------------------ matcher

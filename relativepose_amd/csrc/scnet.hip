@@ -1440,6 +1440,197 @@ __global__ __launch_bounds__(256, SPLIT >= 4 ? 2 : 3) void conv_s2_strip_kernel(
     }
 }
 
+// ---- stride-2 4x4 transposed convs, one sub-pixel phase per workgroup, LINEAR tiles (deconv4, deconv5: 28 x 28 / 14 x 14 input grids) ----
+// One phase of a stride-2 4x4 transposed conv is a stride-1 2x2-tap conv of the input: output (y, x) of the phase reads input
+// (y + offy[t], x + offx[t]) with offy / offx in {-1, 0} (py / px = 0) or {0, +1} (py / px = 1).  That is conv_s2_strip_kernel's per-plane
+// problem with ONE plane and an input step of 1: in the padded plane of (Hin + 1) x (Win + 1) positions per image (local (r, c) = input
+// pixel (r + min offy, c + min offx): the pad row / column sits before the image for offsets {-1, 0}, behind it for {0, +1}) output
+// (img, y, x) sits at P = (img (Hin + 1) + y)(Win + 1) + x and tap t at P + (offy[t] - min offy)(Win + 1) + (offx[t] - min offx).  The
+// <= 192 positions of a 128-pixel tile are fetched, BatchNorm-transformed, split and stored to LDS ONCE per 32-channel chunk and the four
+// taps run off that strip (conv_igemm_kernel stages 128 rows per tap: 48 MFMAs per wave and staged tile, here 192), each A fragment
+// feeding NI = 4 accumulators.  K order = conv_igemm_kernel's for these members (chunk outer, natural channel order over both sources, tap
+// inner; slices cut at the same k-tiles), products and transforms are the same expressions: every accumulator receives the same MFMAs
+// in the same order and the partial sums [ks][M][cout_pad] are bitwise those of the implicit GEMM (tests/test_gpu_deconv_strip.py).
+// descs: the 4 phase descriptors of head blockIdx.z; blockIdx.x: conv_igemm_kernel's ninner == 4 order (the four phases of a spatial
+// tile back to back on one XCD: they read the same input lines); blockIdx.y = (K slice, N tile).  Split-K launches only.
+// Workgroups per CU: 3 with fp32 products (<= 168 VGPRs), 2 in the 16-bit modes (the f16 modes spill 14-31 registers at 168; the
+// three-piece bf16 rows take 65 KB of LDS).
+template <int NI, int SPLIT = 0>
+__global__ __launch_bounds__(256, SPLIT == 0 ? 3 : 2) void deconv_strip_kernel(const ConvDesc* __restrict__ descs, int mtiles) {
+    constexpr int LD = RowLd<SPLIT>::v;                               // LDS row stride (floats)
+    constexpr bool S3 = SPLIT >= 4;                                   // three-piece bf16 operands: 6 bytes per weight, rows [hi | mid | lo]
+    constexpr int WB = S3 ? 6 : 4;
+    constexpr int BM = 128, SMAX = 192, PSTEP = 256 / KQ, A_SLOTS = SMAX / PSTEP, B_ROWS = NI * 32, B_SLOTS = B_ROWS / PSTEP;
+    static_assert(BK == 32 && SMAX % PSTEP == 0 && B_ROWS % PSTEP == 0 && A_SLOTS <= 8, "slot layout");
+    __shared__ __attribute__((aligned(16))) float At[SMAX * LD];
+    __shared__ __attribute__((aligned(16))) float Bt[B_ROWS * LD];
+    const int xcd = blockIdx.x & 7, bslot = blockIdx.x >> 3;
+    const int phase = bslot & 3, mtile = (bslot >> 2) * 8 + xcd;
+    if (mtile >= mtiles) return;                                      // (the grid is padded to whole rounds of 8 tiles)
+    const ConvDesc* dp = descs + 4 * blockIdx.z + phase;
+    const ConvDesc d = *dp;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l31 = lane & 31;
+    const int ks = blockIdx.y / d.ntiles_n, n0 = (blockIdx.y - ks * d.ntiles_n) * NI * 32;
+    const int m0 = mtile * BM, hw = d.Hin * d.Win, W1 = d.Win + 1, H1 = d.Hin + 1, img_pos = H1 * W1;
+    const int dy0 = min((int)dp->offy[0], (int)dp->offy[3]), dx0 = min((int)dp->offx[0], (int)dp->offx[3]);   // -1 or 0
+    auto pos_of = [&](int m) { const int img = m / hw, rem = m - img * hw; const int y = rem / d.Win; return (img * H1 + y) * W1 + (rem - y * d.Win); };
+    const int pmin = pos_of(m0);
+    const int nvalid = pos_of(min(m0 + BM, d.M) - 1) + W1 + 2 - pmin;          // staged positions (host guarantees <= SMAX)
+    const int g0 = (m0 / hw) >> 1;                                             // first BatchNorm group of the tile; rsrcs start at image 2 g0
+    const int kqa = tid % KQ;
+    const int a_lds0 = (tid / KQ) * LD;
+    // slot it = position pmin + tid / 8 + PSTEP it: input pixel index relative to image 2 g0, in-image flag and BatchNorm group (0 / 1
+    // relative to g0), one bit per slot in a_ok / a_grp
+    int a_in[A_SLOTS], a_ok = 0, a_grp = 0;
+#pragma unroll
+    for (int it = 0; it < A_SLOTS; ++it) {
+        const int sl = tid / KQ + it * PSTEP;
+        const int pos = pmin + sl;
+        const int img = pos / img_pos, rem = pos - img * img_pos;
+        const int r = rem / W1, c = rem - r * W1;
+        const int iy = r + dy0, ix = c + dx0;
+        const bool ok = sl < nvalid && img < d.Nimg && iy >= 0 && iy < d.Hin && ix >= 0 && ix < d.Win;
+        a_in[it] = ok ? ((img - 2 * g0) * d.Hin + iy) * d.Win + ix : 0;
+        a_ok |= (ok ? 1 : 0) << it;
+        a_grp |= (((img >> 1) - g0) & 1) << it;
+    }
+    const size_t base_px = (size_t)(2 * g0) * hw;
+    const int nimg_left = min(4, d.Nimg - 2 * g0);
+    const bool two = d.nsrc > 1;
+    const int C0 = d.src[0].C;
+    const __amdgpu_buffer_rsrc_t rs_a0 = __builtin_amdgcn_make_buffer_rsrc((void*)(d.src[0].x + base_px * d.src[0].cstride), 0,
+                                                                          nimg_left * hw * 4 * d.src[0].cstride, 0x00020000);
+    // (one source: the second descriptor is never selected, a valid copy of the first all the same)
+    const float* xB = two ? d.src[1].x : d.src[0].x;
+    const float2* ssB = two ? d.src[1].ss : d.src[0].ss;
+    const int csB = two ? d.src[1].cstride : d.src[0].cstride, sstB = two ? d.src[1].sstride : d.src[0].sstride;
+    const __amdgpu_buffer_rsrc_t rs_a1 = __builtin_amdgcn_make_buffer_rsrc((void*)(xB + base_px * csB), 0, nimg_left * hw * 4 * csB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)d.w, 0, d.cout_pad * d.K * WB, 0x00020000);
+    // scale / shift tables of the two groups the tile can touch (clamped to the last group), per source
+    const int ng = d.Nimg / 2, g1 = min(g0 + 1, ng - 1);
+    const float* ssA0 = reinterpret_cast<const float*>(d.src[0].ss + (size_t)g0 * d.src[0].sstride);
+    const float* ssA1 = reinterpret_cast<const float*>(d.src[0].ss + (size_t)g1 * d.src[0].sstride);
+    const float* ssB0 = reinterpret_cast<const float*>(ssB + (size_t)g0 * sstB);
+    const float* ssB1 = reinterpret_cast<const float*>(ssB + (size_t)g1 * sstB);
+    int b_off[B_SLOTS];
+#pragma unroll
+    for (int it = 0; it < B_SLOTS; ++it) b_off[it] = (n0 + tid / KQ + it * PSTEP) * d.K * WB + kqa * 16;
+    const int b_lds0 = (tid / KQ) * LD + kqa * 4;
+    floatx16 acc[1][NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
+    const int mrow = min(m0 + 32 * wave + l31, d.M - 1);                        // this lane's MFMA row (rows past M are never stored)
+    const int arow = (pos_of(mrow) - pmin) * LD + h * 4;
+    const int brow = l31 * LD + h * 4;
+    // LDS offset of tap t relative to the output pixel's position (block-uniform)
+    const int aoff0 = (((int)dp->offy[0] - dy0) * W1 + (int)dp->offx[0] - dx0) * LD, aoff1 = (((int)dp->offy[1] - dy0) * W1 + (int)dp->offx[1] - dx0) * LD;
+    const int aoff2 = (((int)dp->offy[2] - dy0) * W1 + (int)dp->offx[2] - dx0) * LD, aoff3 = (((int)dp->offy[3] - dy0) * W1 + (int)dp->offx[3] - dx0) * LD;
+    const float slope = d.src[0].slope;                                        // both sources of a skip concatenation use LeakyReLU(0.1)
+    // K slice: k-tiles [kt_begin, kt_end) of conv_igemm_kernel's (chunk, tap) order; the host cuts the slices at whole chunks (kt_per % 4 == 0)
+    const int kt_begin = ks * d.kt_per, kt_end = min(d.K / BK, kt_begin + d.kt_per);
+    const int ch_begin = kt_begin >> 2, ch_end = kt_end >> 2;
+    float4 ra[A_SLOTS], rb[B_SLOTS];
+    float2 rbl[S3 ? B_SLOTS : 1];                                              // (S3) the lo pieces of the weight rows
+    float4 sc0a, sc0b, sc1a, sc1b;                                             // {scale, shift} pairs of the thread's 4 channels, groups g0 / g0 + 1
+
+    // chunk CH = channels [32 CH, 32 CH + 32) of cat(src[0], src[1]): source, its channel offset, its tables
+#define RP_DS_LOAD_A(CH)                                                                                       \
+    {                                                                                                         \
+        const bool s1_ = two && (CH) * BK >= C0;                                                              \
+        const int cc_ = (CH) * BK - (s1_ ? C0 : 0);                                                           \
+        const float* t0_ = (s1_ ? ssB0 : ssA0) + (cc_ + kqa * 4) * 2;                                         \
+        const float* t1_ = (s1_ ? ssB1 : ssA1) + (cc_ + kqa * 4) * 2;                                         \
+        sc0a = rp_ldg4(t0_); sc0b = rp_ldg4(t0_ + 4); sc1a = rp_ldg4(t1_); sc1b = rp_ldg4(t1_ + 4);           \
+        const int scs4_ = (s1_ ? csB : d.src[0].cstride) * 4;                                                 \
+        const __amdgpu_buffer_rsrc_t rs_ = s1_ ? rs_a1 : rs_a0;                                               \
+        _Pragma("unroll") for (int it = 0; it < A_SLOTS; ++it) {                                              \
+            int px_ = a_in[it];                                                                               \
+            asm volatile("" : "+v"(px_));                                                                     \
+            const int voff_ = px_ * scs4_ + kqa * 16;                                                         \
+            ra[it] = rp_bufld4(rs_, voff_, cc_ * 4);                                                          \
+        }                                                                                                     \
+    }
+#define RP_DS_STORE_A()                                                                                        \
+    {                                                                                                         \
+        const rp_v2f sl2_ = {slope, slope};                                                                   \
+        _Pragma("unroll") for (int it = 0; it < A_SLOTS; ++it) {                                              \
+            const bool g1_ = (a_grp >> it) & 1;                                                               \
+            const float4 qa_ = g1_ ? sc1a : sc0a, qb_ = g1_ ? sc1b : sc0b;     /* {s0, h0, s1, h1}, {s2, h2, s3, h3} */ \
+            rp_v2f v01 = {ra[it].x, ra[it].y}, v23 = {ra[it].z, ra[it].w};                                    \
+            v01 = v01 * (rp_v2f){qa_.x, qa_.z} + (rp_v2f){qa_.y, qa_.w};                                      \
+            v23 = v23 * (rp_v2f){qb_.x, qb_.z} + (rp_v2f){qb_.y, qb_.w};                                      \
+            const rp_v2f t01 = v01 * sl2_, t23 = v23 * sl2_;                                                  \
+            const float okf_ = ((a_ok >> it) & 1) ? 1.f : 0.f;                                                \
+            const rp_v2f mk_ = {okf_, okf_};                                                                  \
+            v01 = (rp_v2f){fmaxf(v01.x, t01.x), fmaxf(v01.y, t01.y)} * mk_;                                   \
+            v23 = (rp_v2f){fmaxf(v23.x, t23.x), fmaxf(v23.y, t23.y)} * mk_;                                   \
+            rp_tile_store_a<SPLIT>(&At[a_lds0 + it * PSTEP * LD], kqa, v01, v23);                            \
+        }                                                                                                     \
+    }
+    // k-tile S = 4 chunk + tap: weight columns [tap Cin + 32 chunk, + 32) of the phase's rows
+#define RP_DS_LOAD_B(S)                                                                                        \
+    {                                                                                                         \
+        const int so_ = (((S) & 3) * d.Cin + ((S) >> 2) * BK) * WB;                                           \
+        _Pragma("unroll") for (int it = 0; it < B_SLOTS; ++it) {                                              \
+            rb[it] = rp_bufld4(rs_b, b_off[it], so_);                                                         \
+            if (S3) rbl[S3 ? it : 0] = rp_bufld2(rs_b, b_off[it] + 128 - kqa * 8, so_);                        \
+        }                                                                                                     \
+    }
+#define RP_DS_STORE_B()                                                                                        \
+    {                                                                                                         \
+        _Pragma("unroll") for (int it = 0; it < B_SLOTS; ++it) {                                              \
+            *reinterpret_cast<float4*>(&Bt[b_lds0 + it * PSTEP * LD]) = rb[it];                               \
+            if (S3) *reinterpret_cast<float2*>(&Bt[b_lds0 + 32 - kqa * 2 + it * PSTEP * LD]) = rbl[S3 ? it : 0]; \
+        }                                                                                                     \
+    }
+
+    if (ch_begin < ch_end) {
+        const int s_end = ch_end * 4;
+        RP_DS_LOAD_A(ch_begin)
+        RP_DS_LOAD_B(ch_begin * 4)
+        RP_DS_STORE_A()
+        RP_DS_STORE_B()
+        __syncthreads();
+        for (int ch = ch_begin; ch < ch_end; ++ch) {
+            const bool lastc = (ch + 1 == ch_end);
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) {
+                const int sidx = ch * 4 + tt;
+                if (sidx + 1 < s_end) RP_DS_LOAD_B(sidx + 1)
+                // the strip of this chunk is in LDS and its scale / shift registers are free: the next chunk's loads fly under all four taps
+                if (tt == 0 && !lastc) RP_DS_LOAD_A(ch + 1)
+                {
+                    const int ar_[1] = {arow + (tt == 0 ? aoff0 : tt == 1 ? aoff1 : tt == 2 ? aoff2 : aoff3)};
+                    int br_[NI];
+#pragma unroll
+                    for (int j = 0; j < NI; ++j) br_[j] = brow + j * 32 * LD;
+                    rp_tile_mma<SPLIT, 1, NI>(acc, At, ar_, Bt, br_);
+                }
+                __syncthreads();
+                if (sidx + 1 < s_end) RP_DS_STORE_B()
+                if (tt == 3 && !lastc) RP_DS_STORE_A()
+                __syncthreads();
+            }
+        }
+    }
+#undef RP_DS_LOAD_A
+#undef RP_DS_STORE_A
+#undef RP_DS_LOAD_B
+#undef RP_DS_STORE_B
+    // partial sums of this K slice (an empty slice writes zeros): reduced in fixed order by splitk_reduce_kernel
+    const float wsc = (SPLIT == 2 || SPLIT == 3) ? d.wscale : 1.f;             // (16-bit modes: the power-of-two weight pre-scale, exact)
+    float* po = d.partial + (size_t)ks * d.M * d.cout_pad;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = m0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (m >= d.M) continue;
+#pragma unroll
+        for (int j = 0; j < NI; ++j) rp_stg(po + (size_t)m * d.cout_pad + n0 + j * 32 + l31, acc[0][j][r] * wsc);
+    }
+}
+
 // y[pix(m)][col] = sum over K slices (fixed order) of the partial tiles
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvDesc* __restrict__ descs) {
     const ConvDesc d = descs[blockIdx.z];
@@ -2885,6 +3076,28 @@ void Builder::end_group() {
     const int min_slice = ms_env > 0 ? ms_env : 8;
     while (!dtile && s2_cfg < 0 && tiles * ksplit < want_tiles && ksplit < 64 && min_kt / (ksplit * 2) >= min_slice) ksplit *= 2;
     if (force_ksplit && !dtile && s2_cfg < 0) ksplit = force_ksplit;
+    // Phase strip kernel (deconv_strip_kernel): the 4 phases of stride-2 4x4 transposed convs with Cout a multiple of 128 whose input grid
+    // does not tile into patches (deconv4: 28 x 28, deconv5: 14 x 14), split-K launches.  RELPOSE_TUNE_DECONV_STRIP: 0 = that kernel,
+    // 1 = conv_igemm_kernel (the arms differ in the kernel only: same split, same partial sums, same reduce pass, same bits).
+    // The split rule above is not touched: a layer it leaves whole (deconv4 in the three-piece bf16 modes) stays on conv_igemm_kernel --
+    // run as two slices on this kernel it is 160 us faster per forward (profiles/deconv_strip_layers.txt), but its sums are then added
+    // in another order than before, and the poses bench.py dumps for its random-weight network moved with them.
+    const int ds_sel = g_rp_tune[RELPOSE_TUNE_DECONV_STRIP];
+    bool dstrip = ksplit > 1 && !dtile && s2_cfg < 0 && !force_ksplit && cfg == 0 && net->prec != 1 && count % 4 == 0 && cp % 128 == 0;
+    for (int i = first; i < first + count && dstrip; ++i) {
+        const ConvDesc& d = plan->descs[i];
+        const ConvDesc& d0 = plan->descs[first + ((i - first) & ~3)];
+        dstrip = d.osy == 2 && d.osx == 2 && d.sy == 1 && d.sx == 1 && d.ntaps == 4 && d.Hp == d.Hin && d.Wp == d.Win && d.Hin * d.Win >= 128 && !d.bias &&
+                 d.src[0].sstride != 0 && (d.nsrc == 1 || d.src[1].sstride != 0) && d.nsrc == d0.nsrc && d.src[0].x == d0.src[0].x &&
+                 (d.nsrc == 1 || d.src[1].x == d0.src[1].x) && d.Cin == d0.Cin && d.y == d0.y && d.ychoff == d0.ychoff && d.M == plan->descs[first].M &&
+                 // taps t = 2 ty + tx at offsets {-1, 0} or {0, +1} per axis: one pad row and one pad column per image
+                 d.offy[0] == d.offy[1] && d.offy[2] == d.offy[3] && d.offx[0] == d.offx[2] && d.offx[1] == d.offx[3] &&
+                 std::abs(d.offy[0] - d.offy[2]) == 1 && std::abs(d.offx[0] - d.offx[1]) == 1 &&
+                 std::min(d.offy[0], d.offy[2]) >= -1 && std::max(d.offy[0], d.offy[2]) <= 1 && std::min(d.offx[0], d.offx[1]) >= -1 && std::max(d.offx[0], d.offx[1]) <= 1 &&
+                 // staged positions of a 128-pixel tile: 127 + row wraps + one image crossing + the taps' reach
+                 127 + (127 + d.Win - 1) / d.Win + (d.Win + 1) + (d.Win + 1) + 2 <= 192;
+    }
+    if (dstrip && min_kt % (4 * ksplit) != 0) dstrip = false;          // K slices are whole chunks (4 k-tiles)
     size_t pf = 0;
     for (int i = first; i < first + count; ++i) {
         ConvDesc& d = plan->descs[i];
@@ -2961,6 +3174,16 @@ void Builder::end_group() {
             pend_reduce = (int)plan->ops.size() - 1;
             return;
         }
+    }
+    if (dstrip && ds_sel == 0) {
+        const int mt = (plan->descs[first].M + 127) / 128;
+        Op o; o.type = OP_CONV_STRIP; o.first = first; o.count = count; o.cfg = 1; o.split = net->prec; o.mt_max = mt;
+        o.grid = dim3((unsigned)(((mt + 7) / 8) * 8 * 4), (cp / 128) * ksplit, count / 4);
+        plan->ops.push_back(o);
+        Op r; r.type = OP_REDUCE; r.first = first; r.count = count; r.cfg = 0; r.grid = dim3(256, 1, count);
+        plan->ops.push_back(r);
+        pend_reduce = (int)plan->ops.size() - 1;
+        return;
     }
     Op o; o.type = OP_CONV; o.first = first; o.count = count; o.cfg = cfg;
     // runs of 4 consecutive members that are the phases of one stride-2 transposed conv share their input tile
@@ -3394,10 +3617,11 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     bool self_cached = self_tag != 0 && prev.tag == self_tag && prev.n == n && prev.H == H && prev.W == W && prev.pose_only == pose_only && !zero_warp &&
                        prev.gen == ws_gen;
     int snap_mode = 0;
+    const int ds_key = (g_rp_tune[RELPOSE_TUNE_DECONV_STRIP] == 1 ? 1 : 0) << 28;       // the builder reads the knob: one plan per value
     for (int attempt = 0; attempt < 2 && !plan; ++attempt) {
         // a tagged forward that computes the self streams also leaves the accumulator snapshots of the skip-connection halves
         snap_mode = self_cached ? 2 : (self_tag != 0 ? 1 : 0);
-        const int plan_key = (int)n | (zero_warp ? 1 << 24 : 0) | (pose_only ? 1 << 25 : 0) | (self_cached ? 1 << 26 : 0) | (snap_mode == 1 ? 1 << 27 : 0);
+        const int plan_key = (int)n | (zero_warp ? 1 << 24 : 0) | (pose_only ? 1 << 25 : 0) | (self_cached ? 1 << 26 : 0) | (snap_mode == 1 ? 1 << 27 : 0) | ds_key;
         auto it = net->plans.find(std::make_pair(workspace, plan_key));
         if (it != net->plans.end()) { plan = (Plan*)it->second; break; }
         const WsOffsets o = ws_offsets(net, n);
@@ -3424,7 +3648,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         }
         RP_HIP(hipMalloc((void**)&p->d_descs, MAX_DESCS * sizeof(ConvDesc)));
         RP_HIP(hipMemcpy(p->d_descs, p->descs.data(), p->descs.size() * sizeof(ConvDesc), hipMemcpyHostToDevice));
-        const int key2 = (int)n | (zero_warp ? 1 << 24 : 0) | (pose_only ? 1 << 25 : 0) | (self_cached ? 1 << 26 : 0) | (snap_mode == 1 ? 1 << 27 : 0);
+        const int key2 = (int)n | (zero_warp ? 1 << 24 : 0) | (pose_only ? 1 << 25 : 0) | (self_cached ? 1 << 26 : 0) | (snap_mode == 1 ? 1 << 27 : 0) | ds_key;
         net->plans[std::make_pair(workspace, key2)] = p;
         plan = p;
     }
@@ -3575,8 +3799,11 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
                 else { LAUNCH_(0); }                                      \
             } while (0)
 #define RP_L_STRIP(SP_) hipLaunchKernelGGL((conv_s2_strip_kernel<4, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
-            RP_TILE_SPLIT(RP_L_STRIP);
+#define RP_L_DSTRIP(SP_) hipLaunchKernelGGL((deconv_strip_kernel<4, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first, op.mt_max)
+            if (op.cfg == 1) RP_TILE_SPLIT(RP_L_DSTRIP);        // the phases of a transposed conv (deconv4, deconv5)
+            else RP_TILE_SPLIT(RP_L_STRIP);
 #undef RP_L_STRIP
+#undef RP_L_DSTRIP
             mark(-1);
         } else if (op.type == OP_CONV_S2) {
             mark(1);
