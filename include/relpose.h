@@ -496,6 +496,84 @@ typedef struct RelposeCicpArgs {
 size_t relpose_cicp_workspace_bytes(int32_t n_pairs, int32_t n_points, int32_t max_points);
 int relpose_cicp(const RelposeCicpArgs* args);
 
+/* -------------------------------------------------------------------- descriptor evaluation
+ * The reference's feature-quality metric for a batch of panorama pairs: dense ground-truth correspondences between the two clouds
+ * (datasets/SUNCG.py:315-341), their observed / unobserved class (mainPanoCompletion2view.py:535-542) and, per correspondence, the
+ * number of target pixels whose descriptor lies closer to the source descriptor than the true match does (evalDLDescriptor,
+ * mainPanoCompletion2view.py:383-414).  The contract is DESIGN.md 4.9; both entry points only enqueue on `stream`.
+ *
+ * relpose_dense_nn: the batched nearest neighbour with index behind the KDTree query of datasets/SUNCG.py:323-332.
+ *   pc, valid        [2 n_pairs, 3, n_points] f64 and [2 n_pairs, n_points] u8 as relpose_pano2pc writes them (cloud 2b = the source of
+ *                    pair b, 2b + 1 its target); n_points = 4 h h
+ *   to_world         [2 n_pairs, 4, 4] f64, applied to every cloud: w_a = ((M_a0 x + M_a1 y) + M_a2 z) + M_a3
+ *   query            [n_pairs, n_query] i32 point indices into the source cloud, -1 = an unused slot
+ *   max_dist         0 = 0.08 (datasets/SUNCG.py:328)
+ *   nn_index         [n_pairs, n_query] i32: the valid target point with the smallest d2 = (dx dx + dy dy) + dz dz, d = target - query;
+ *                    ties go to the lowest index
+ *   nn_dist          [n_pairs, n_query] f64 = sqrt(d2);  hit [n_pairs, n_query] u8 = nn_dist < max_dist
+ *   idx_src, idx_tgt [n_pairs, n_query, 2] i32: the (x, y) panorama pixel of the query and of its neighbour (PanoIdx,
+ *                    datasets/SUNCG.py:164-174)
+ * An unused slot, a query whose source point is invalid and a pair whose target has no valid point (none with a d2 below +inf) give
+ * nn_index -1, nn_dist -1, hit 0 and pixels 0. */
+typedef struct RelposeDenseNnArgs {
+    uint32_t struct_size;       /* sizeof(RelposeDenseNnArgs) as the caller compiled it */
+    int32_t n_pairs;
+    int32_t n_points;
+    int32_t n_query;
+    int32_t h;
+    int32_t reserved0;
+    const double* pc;
+    const uint8_t* valid;
+    const double* to_world;
+    const int32_t* query;
+    double max_dist;
+    int32_t* nn_index;
+    double* nn_dist;
+    uint8_t* hit;
+    int32_t* idx_src;
+    int32_t* idx_tgt;
+    void* stream;
+} RelposeDenseNnArgs;
+int relpose_dense_nn(const RelposeDenseNnArgs* args);
+
+/* relpose_descriptor_rank: the counts behind evalDLDescriptor's ratio (mainPanoCompletion2view.py:401-405).
+ *   f                [2 n_pairs, total_channels, h, 4h] f32, the network output, read in place (8-byte aligned); the descriptor is
+ *                    channels feat_off .. feat_off + n_channels - 1, 1 <= n_channels <= RELPOSE_DESC_MAX_CHANNELS
+ *   idx_src, idx_tgt [n_pairs, n_corres, 2] i32 (x, y) pixels in image 2b and 2b + 1
+ *   sel              [n_pairs, n_slots] i32 indices into n_corres, -1 = unused; NULL = every correspondence (n_slots is ignored and
+ *                    the outputs have n_corres slots)
+ *   pair_valid       [n_pairs] u8 or NULL (all valid)
+ *   mask             [2 n_pairs, h, 4h] f32 or NULL, nonzero = observed (what relpose_apply_mask returns)
+ *   thr              [n_pairs, n_slots] f32 = sum_c (f[2b, off + c, y_s, x_s] - f[2b + 1, off + c, y_t, x_t])^2, accumulated in fp32 from 0
+ *                    with c ascending as acc = acc + d * d (no fused multiply-add)
+ *   count            [n_pairs, n_slots] i32 = #{target pixels p : d_p < thr}, d_p the same expression at pixel p of image 2b + 1 (the
+ *                    true match has d_p == thr bit for bit and is never counted); -1 for an unused slot, a slot whose pixels lie
+ *                    outside the map and every slot of a pair with pair_valid 0
+ *   type             [n_pairs, n_slots] i32 = (mask at the source pixel != 0) + (mask at the target pixel != 0); -1 without a mask or
+ *                    where count is -1 */
+#define RELPOSE_DESC_MAX_CHANNELS 64
+typedef struct RelposeDescRankArgs {
+    uint32_t struct_size;       /* sizeof(RelposeDescRankArgs) as the caller compiled it */
+    int32_t n_pairs;
+    int32_t h;
+    int32_t total_channels;
+    int32_t feat_off;
+    int32_t n_channels;
+    int32_t n_corres;
+    int32_t n_slots;
+    const float* f;
+    const int32_t* idx_src;
+    const int32_t* idx_tgt;
+    const int32_t* sel;
+    const uint8_t* pair_valid;
+    const float* mask;
+    int32_t* count;
+    float* thr;
+    int32_t* type;
+    void* stream;
+} RelposeDescRankArgs;
+int relpose_descriptor_rank(const RelposeDescRankArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

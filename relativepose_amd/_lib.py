@@ -110,6 +110,25 @@ CICP_TRACE_SLOTS = 94               # RELPOSE_CICP_TRACE_SLOTS
 CICP_LAMBDA_GEOMETRIC = 0.968       # RELPOSE_CICP_LAMBDA_GEOMETRIC
 
 
+class DenseNnArgs(C.Structure):
+    """RelposeDenseNnArgs (include/relpose.h): the argument block of relpose_dense_nn."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_pairs", c_int), ("n_points", c_int), ("n_query", c_int), ("h", c_int), ("reserved0", c_int),
+                ("pc", c_void_p), ("valid", c_void_p), ("to_world", c_void_p), ("query", c_void_p), ("max_dist", c_double),
+                ("nn_index", c_void_p), ("nn_dist", c_void_p), ("hit", c_void_p), ("idx_src", c_void_p), ("idx_tgt", c_void_p),
+                ("stream", c_void_p)]
+
+
+class DescRankArgs(C.Structure):
+    """RelposeDescRankArgs (include/relpose.h): the argument block of relpose_descriptor_rank."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_pairs", c_int), ("h", c_int), ("total_channels", c_int), ("feat_off", c_int),
+                ("n_channels", c_int), ("n_corres", c_int), ("n_slots", c_int), ("f", c_void_p), ("idx_src", c_void_p), ("idx_tgt", c_void_p),
+                ("sel", c_void_p), ("pair_valid", c_void_p), ("mask", c_void_p), ("count", c_void_p), ("thr", c_void_p), ("type", c_void_p),
+                ("stream", c_void_p)]
+
+
+DESC_MAX_CHANNELS = 64              # RELPOSE_DESC_MAX_CHANNELS
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -150,6 +169,8 @@ SIGNATURES = {
     "relpose_ransac": (c_int, [C.POINTER(RansacArgs)]),
     "relpose_cicp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "relpose_cicp": (c_int, [C.POINTER(CicpArgs)]),
+    "relpose_dense_nn": (c_int, [C.POINTER(DenseNnArgs)]),
+    "relpose_descriptor_rank": (c_int, [C.POINTER(DescRankArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

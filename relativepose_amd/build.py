@@ -19,6 +19,7 @@ SOURCES = [
     ("fgr.hip", ["-ffp-contract=off"]),           # FPFH + FGR: bins and matches must agree with tests/fgr_model.py bit for bit
     ("ransac.hip", ["-ffp-contract=off"]),        # RANSAC: draws, Horn and the validation sums must agree with tests/ransac_model.py
     ("cicp.hip", ["-ffp-contract=off"]),          # coloured ICP: voxels, correspondences and the reductions must agree with tests/cicp_model.py
+    ("descriptor.hip", ["-ffp-contract=off"]),    # descriptor evaluation: the thresholds and counts must agree with tests/descriptor_model.py
     ("scnet.hip", []),
 ]
 

@@ -259,6 +259,38 @@ def _evaluate_baseline(batches, device, dataset, register, result_path, with_col
     return stats
 
 
+def evaluate_descriptors(batches, net, device, dataset, mask_method, seed=0, n_eval=100, **corres):
+    """The reference's descriptor metric (evalDLDescriptor, mainPanoCompletion2view.py:383-414) over batches of pairs with ground-truth
+    poses: per batch the level-0 forward the pipeline builds (masked own view, zero warped view), the descriptor = the feature channels
+    at the pipeline's feat_off, dense correspondences from the batch's depth and poses (descriptor.dense_correspondences; batch["R"] is
+    camera-to-world and is passed as is; `corres` = its keyword overrides) and the rank ratios.  One np.random.RandomState(seed) serves
+    every draw, batch after batch.  -> {"pairs", "valid_pairs", "ratiosObs", "ratiosUnobs" (one entry per valid pair with a non-empty
+    class), "ratio_obs", "ratio_unobs" (their means; NaN when empty)}."""
+    import torch
+    from . import descriptor, util
+    from .pipeline import RelativePosePipeline
+    pipe = RelativePosePipeline(net, dataset, mask_method, alter_steps=1)
+    rng = np.random.RandomState(seed)
+    obs, unobs, pairs, valid = [], [], 0, 0
+    for batch in batches:
+        n = _batch_size(batch)
+        sub = _batch_take(batch, np.arange(n))
+        h = sub["depth"].shape[2]
+        st = pipe.prepare(sub["rgb"], sub["norm"], sub["depth"], np.zeros((n, 2, 1, 2)), np.zeros((n, 2, 1)), device)
+        x = pipe._net_input(st)
+        x[:, 8:].zero_()                              # level 0: the warp under the identity is the all-zero view (util.py:95-96)
+        f = net.forward(x, out=st["f"], zero_warp=True)
+        _, mask = util.apply_mask_dev(torch.ones(2 * n, 1, h, 4 * h, dtype=torch.float32, device=device), mask_method)
+        dc = descriptor.dense_correspondences(st["depth"], sub["R"].reshape(2 * n, 4, 4), dataset, rng, **corres)
+        o, u = descriptor.evalDLDescriptor(f, pipe.feat_off, net.out_channels - pipe.feat_off, dc, mask, rng, n_eval=n_eval)
+        obs += o
+        unobs += u
+        pairs += n
+        valid += int(dc["valid"].sum())
+    mean = lambda v: float(np.mean(v)) if v else float("nan")
+    return {"pairs": pairs, "valid_pairs": valid, "ratiosObs": obs, "ratiosUnobs": unobs, "ratio_obs": mean(obs), "ratio_unobs": mean(unobs)}
+
+
 def evaluate_pairs_sharded(pipe, batches, device, result_path=None, names=None, rank=0, world=1, resume=True, round_batches=None,
                            record_fn=None, depth=2):
     """`evaluate_pairs` over `world` ranks (one process per GPU, torch.distributed initialised by the caller:
@@ -415,7 +447,33 @@ def main(argv=None):
     ap.add_argument("--method", choices=["ours", "fgs", "gs", "cgs"], default="ours",
                     help="fgs = the reference's fast global registration baseline (baselines.py:83-106), gs = its RANSAC global registration "
                          "baseline (baselines.py:52-81), cgs = gs refined by coloured ICP (baselines.py:110-168), all on the observed clouds: no network")
+    ap.add_argument("--descriptor-eval", action="store_true",
+                    help="the reference's descriptor metric instead of poses (evalDLDescriptor, mainPanoCompletion2view.py:383-414): one JSON "
+                         "line with metric, pairs, valid_pairs, ratio_obs, ratio_unobs, seconds")
     args = ap.parse_args(argv)
+
+    if args.descriptor_eval:
+        if args.gpus > 1:
+            raise SystemExit("--descriptor-eval runs on one GPU (--gpus 1): the metric is not sharded")
+        import torch
+        from types import SimpleNamespace
+        from . import _lib, weights
+        from .model import SCNet
+        dev = _lib.require_gpu()
+        ds = args.dataset
+        mm, S, tanh = ("kinect", 21, 0) if ds == "scannet" else ("second", 21 if ds == "matterport" else 15, 1)
+        net = SCNet(SimpleNamespace(batchnorm=1, useTanh=tanh, skipLayer=1, outputType="rgbdnsf", snumclass=S))
+        net.load_state_dict(weights.make_state_dict(7, S))
+        net.set_precision(args.precision)
+        bs = min(args.batch, 32)
+        batches = [SyntheticBatch(min(bs, args.pairs - k), args.seed + k, ds, mm, 1) for k in range(0, args.pairs, bs)]
+        t0 = time.perf_counter()
+        r = evaluate_descriptors(batches, net, dev, ds, mm, seed=args.seed)
+        torch.cuda.synchronize()
+        print(json.dumps({"metric": "descriptor_rank", "pairs": r["pairs"], "valid_pairs": r["valid_pairs"], "ratio_obs": r["ratio_obs"],
+                          "ratio_unobs": r["ratio_unobs"], "seconds": time.perf_counter() - t0, "dataset": ds, "precision": args.precision}),
+              flush=True)
+        return
 
     if args.method in ("fgs", "gs", "cgs"):
         m = args.method

@@ -32,6 +32,8 @@ Operator                    replaces (reference file:line)
   global_registration       the gs baseline: FPFH + RANSAC over feature matches, baselines.py:52-81 (batched over pairs)
   colored_icp               the three coloured ICP levels of the cgs baseline from a given pose, baselines.py:141-166 (batched over pairs)
   color_registration        the cgs baseline: the gs RANSAC result refined by coloured ICP, baselines.py:110-168 (batched over pairs)
+  dense_nn                  the KDTree query of the loaders' dense correspondences, datasets/SUNCG.py:323-332 (batched, with index)
+  descriptor_rank           the rank counts of evalDLDescriptor, mainPanoCompletion2view.py:401-405 (batched over pairs)
   affinity_topk             rpmodule.py:342-379
   match_pairs               RelativePoseEstimation_helper, rpmodule.py:317-508
 """
@@ -70,6 +72,11 @@ _lib.define("global_registration(Tensor pc, Tensor valid, int max_points=32768, 
 # color f64 [2B,P,3]; init f64 [B,4,4] (T p_src ~ p_tgt) -> pose [B,4,4] f64, status [B] i32
 _lib.define("colored_icp(Tensor pc, Tensor color, Tensor valid, Tensor init, float lambda_geometric=0.968, int max_points=32768) -> (Tensor, Tensor)")
 _lib.define("color_registration(Tensor pc, Tensor color, Tensor valid, int max_points=32768, int seed=0, float lambda_geometric=0.968) -> (Tensor, Tensor)")
+# pc f64 [2B,3,P], valid u8 [2B,P] (pano2pc's layout), to_world f64 [2B,4,4], query i32 [B,nq] -> nn_index, nn_dist, hit [B,nq], idx_src, idx_tgt [B,nq,2]
+_lib.define("dense_nn(Tensor pc, Tensor valid, Tensor to_world, Tensor query, float max_dist=0.08) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
+# f f32 [2B,Ct,h,4h]; idx_src, idx_tgt i32 [B,K,2]; sel i32 [B,E], pair_valid u8 [B], mask f32 [2B,1,h,4h] (optional) -> count, thr, type [B,E]
+_lib.define("descriptor_rank(Tensor f, int feat_off, int channels, Tensor idx_src, Tensor idx_tgt, Tensor? sel=None, Tensor? pair_valid=None, "
+            "Tensor? mask=None) -> (Tensor, Tensor, Tensor)")
 _lib.define("affinity_topk(Tensor feat_s, Tensor weight_s, Tensor feat_t, Tensor weight_t, Tensor ns, Tensor nt, "
             "float[] params, int topK, bool want_wij) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("match_pairs(Tensor pc_s, Tensor normal_s, Tensor feat_s, Tensor weight_s, Tensor pc_t, Tensor normal_t, "
@@ -176,6 +183,16 @@ def _color_registration(pc, color, valid, max_points=32768, seed=0, lambda_geome
     return pose, status
 
 
+def _dense_nn(pc, valid, to_world, query, max_dist=0.08):
+    from . import descriptor as _d
+    return _d.dense_nn_dev(pc, valid, to_world, query, float(max_dist))
+
+
+def _descriptor_rank(f, feat_off, channels, idx_src, idx_tgt, sel=None, pair_valid=None, mask=None):
+    from . import descriptor as _d
+    return _d.descriptor_rank_dev(f.contiguous(), int(feat_off), int(channels), idx_src, idx_tgt, sel, pair_valid, mask)
+
+
 def _affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     wij, cj, cw, keff = _rp.affinity_topk(feat_s.contiguous(), weight_s.contiguous(), feat_t.contiguous(), weight_t.contiguous(),
                                           ns.contiguous(), nt.contiguous(), _para(params, topK), want_wij=bool(want_wij))
@@ -195,7 +212,8 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("warp_pairs_", _warp_pairs_), ("pano2pc", _pano2pc), ("pose_inverse", _pose_inverse),
                    ("sample_primitives", _sample_primitives), ("keypoints_reference", _keypoints_reference), ("affinity_topk", _affinity_topk), ("match_pairs", _match_pairs),
                    ("sift_detect", _sift_detect), ("fast_global_registration", _fast_global_registration),
-                   ("global_registration", _global_registration), ("colored_icp", _colored_icp), ("color_registration", _color_registration)):
+                   ("global_registration", _global_registration), ("colored_icp", _colored_icp), ("color_registration", _color_registration),
+                   ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -271,6 +289,17 @@ def _m_color_registration(pc, color, valid, max_points=32768, seed=0, lambda_geo
     return pc.new_empty(B, 4, 4, dtype=torch.float64), pc.new_empty(B, dtype=torch.int32)
 
 
+def _m_dense_nn(pc, valid, to_world, query, max_dist=0.08):
+    B, nq = query.shape
+    return (pc.new_empty(B, nq, dtype=torch.int32), pc.new_empty(B, nq, dtype=torch.float64), pc.new_empty(B, nq, dtype=torch.uint8),
+            pc.new_empty(B, nq, 2, dtype=torch.int32), pc.new_empty(B, nq, 2, dtype=torch.int32))
+
+
+def _m_descriptor_rank(f, feat_off, channels, idx_src, idx_tgt, sel=None, pair_valid=None, mask=None):
+    B, E = idx_src.shape[0], (idx_src.shape[1] if sel is None else sel.shape[1])
+    return f.new_empty(B, E, dtype=torch.int32), f.new_empty(B, E, dtype=torch.float32), f.new_empty(B, E, dtype=torch.int32)
+
+
 def _m_affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     B, ns_max, nt_max = feat_s.shape[0], feat_s.shape[1], feat_t.shape[1]
     wij = feat_s.new_empty(B, ns_max, nt_max, dtype=torch.float32) if want_wij else feat_s.new_empty(0)
@@ -287,9 +316,10 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("warp", _m_warp), ("warp_pairs_", _m_warp_pairs_), ("pano2pc", _m_pano2pc), ("pose_inverse", _m_pose_inverse),
                    ("sample_primitives", _m_sample_primitives), ("keypoints_reference", _m_keypoints_reference), ("affinity_topk", _m_affinity_topk),
                    ("match_pairs", _m_match_pairs), ("sift_detect", _m_sift_detect), ("fast_global_registration", _m_fast_global_registration),
-                   ("global_registration", _m_global_registration), ("colored_icp", _m_colored_icp), ("color_registration", _m_color_registration)):
+                   ("global_registration", _m_global_registration), ("colored_icp", _m_colored_icp), ("color_registration", _m_color_registration),
+                   ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
-       "color_registration")
+       "color_registration", "dense_nn", "descriptor_rank")
