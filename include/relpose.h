@@ -574,6 +574,72 @@ typedef struct RelposeDescRankArgs {
 } RelposeDescRankArgs;
 int relpose_descriptor_rank(const RelposeDescRankArgs* args);
 
+/* -------------------------------------------------------------------- SIFT descriptors and the SIFT baseline of the descriptor metric
+ * evalSiftDescriptor (mainPanoCompletion2view.py:353-381, the 'sift' curve of evalPlot, :342): SIFT descriptors of the sampled
+ * correspondences in both panoramas and of a step-5 grid of the target (cv2.xfeatures2d.SIFT_create().compute(gray, keypoints) with
+ * cv2.KeyPoint(x, y, 5), :365-377), then the share of grid descriptors that lie closer to the source descriptor than the true match does
+ * (:373, :378-379).  The descriptor contract is DESIGN.md 4.10.  It is the project's own, written from Lowe (IJCV 60(2), 2004) with the
+ * parameters of that call; cv2 is not a dependency and agreement with cv2's descriptors is UNTESTED.  Keypoints are on octave 0, layer 0
+ * (what cv2.KeyPoint(x, y, size) gives); descriptors for relpose_sift_detect's own keypoints (other octaves) are out of scope.
+ * Both entry points only enqueue on `stream`; invalid arguments return RELPOSE_EINVAL before anything is enqueued.
+ *
+ * relpose_sift_describe: 128-byte descriptors of given keypoints in n_views images (mainPanoCompletion2view.py:361-371, :375-377).
+ *   images, img_h, img_w, channels, crop_*   as relpose_sift_detect (uint8 BGR or gray, cv2's 14-bit gray weights); 1 <= crop side <=
+ *                    RELPOSE_SIFT_MAX_SIDE
+ *   kp               [n_views, n_kp, 4] f32 (x, y, size, angle in degrees; cv2.KeyPoint's default angle is -1) in the crop's frame
+ *   kp_count         [n_views] i32 or NULL (all n_kp): slots at or past a view's count are unused
+ *   grid_step        > 0: dense grid mode -- kp and kp_count must be NULL and n_kp = ceil(crop_w / step) * ceil(crop_h / step); keypoint
+ *                    k is x = (k mod nx) step, y = (k / nx) step, size = step, angle = -1, generated on the device (:375-376)
+ *   desc             [n_views, n_kp, 128] u8, bin order (row * 4 + col) * 8 + orientation; may be NULL when n_kp = 0
+ *   desc_f32         [n_views, n_kp, 128] f32 or NULL: the values before rounding (desc = clamp(round_half_even(desc_f32), 0, 255))
+ *   base             [n_views, crop_h, crop_w] f32 or NULL: the blurred gray image the gradients are taken on
+ *   workspace        relpose_sift_describe_workspace_bytes(n_views, crop_h, crop_w); not needed (may be NULL) when `base` is given
+ * An unused slot (past the count, a non-finite coordinate, size or angle, size <= 0) reads zeros.  Two launches, whatever n_views is.
+ * The sum into every bin runs in an order fixed by the keypoint alone: results do not depend on the batch, the slot or the run. */
+typedef struct RelposeSiftDescArgs {
+    uint32_t struct_size;       /* sizeof(RelposeSiftDescArgs) as the caller compiled it */
+    int32_t n_views;
+    const uint8_t* images;
+    int32_t img_h, img_w, channels;
+    int32_t crop_x, crop_y, crop_w, crop_h;
+    int32_t n_kp;
+    int32_t grid_step;
+    int32_t reserved0;
+    const float* kp;
+    const int32_t* kp_count;
+    uint8_t* desc;
+    float* desc_f32;
+    float* base;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeSiftDescArgs;
+size_t relpose_sift_describe_workspace_bytes(int32_t n_views, int32_t h, int32_t w);
+int relpose_sift_describe(const RelposeSiftDescArgs* args);
+
+/* relpose_sift_rank: the counts behind evalSiftDescriptor's ratio (mainPanoCompletion2view.py:373, :378-379), in integers.
+ *   src, tgt         [n_pairs, n_slots, 128] u8 (16-byte aligned): the descriptors of the correspondences in the source and the target
+ *   dense            [n_pairs, n_points, 128] u8 (16-byte aligned): the target's grid descriptors
+ *   pair_valid       [n_pairs] u8 or NULL (all valid)
+ *   thr              [n_pairs, n_slots] i32 = sum_k (src - tgt)^2
+ *   count            [n_pairs, n_slots] i32 = #{p : sum_k (src[b, e] - dense[b, p])^2 < thr[b, e]} (a tie is not counted)
+ * thr and count are -1 for every slot of a pair with pair_valid 0.  All arithmetic is integer (the products on the int8 matrix pipe), so
+ * the counts are exact; the reference's float32 expression is exact on these values too (128 * 255^2 < 2^24). */
+typedef struct RelposeSiftRankArgs {
+    uint32_t struct_size;       /* sizeof(RelposeSiftRankArgs) as the caller compiled it */
+    int32_t n_pairs;
+    int32_t n_slots;
+    int32_t n_points;
+    const uint8_t* src;
+    const uint8_t* tgt;
+    const uint8_t* dense;
+    const uint8_t* pair_valid;
+    int32_t* thr;
+    int32_t* count;
+    void* stream;
+} RelposeSiftRankArgs;
+int relpose_sift_rank(const RelposeSiftRankArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

@@ -129,6 +129,20 @@ class DescRankArgs(C.Structure):
 DESC_MAX_CHANNELS = 64              # RELPOSE_DESC_MAX_CHANNELS
 
 
+class SiftDescArgs(C.Structure):
+    """RelposeSiftDescArgs (include/relpose.h): the argument block of relpose_sift_describe."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_views", c_int), ("images", c_void_p), ("img_h", c_int), ("img_w", c_int), ("channels", c_int),
+                ("crop_x", c_int), ("crop_y", c_int), ("crop_w", c_int), ("crop_h", c_int), ("n_kp", c_int), ("grid_step", c_int),
+                ("reserved0", c_int), ("kp", c_void_p), ("kp_count", c_void_p), ("desc", c_void_p), ("desc_f32", c_void_p), ("base", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
+class SiftRankArgs(C.Structure):
+    """RelposeSiftRankArgs (include/relpose.h): the argument block of relpose_sift_rank."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_pairs", c_int), ("n_slots", c_int), ("n_points", c_int), ("src", c_void_p), ("tgt", c_void_p),
+                ("dense", c_void_p), ("pair_valid", c_void_p), ("thr", c_void_p), ("count", c_void_p), ("stream", c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -171,6 +185,9 @@ SIGNATURES = {
     "relpose_cicp": (c_int, [C.POINTER(CicpArgs)]),
     "relpose_dense_nn": (c_int, [C.POINTER(DenseNnArgs)]),
     "relpose_descriptor_rank": (c_int, [C.POINTER(DescRankArgs)]),
+    "relpose_sift_describe_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "relpose_sift_describe": (c_int, [C.POINTER(SiftDescArgs)]),
+    "relpose_sift_rank": (c_int, [C.POINTER(SiftRankArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

@@ -20,6 +20,7 @@ SOURCES = [
     ("ransac.hip", ["-ffp-contract=off"]),        # RANSAC: draws, Horn and the validation sums must agree with tests/ransac_model.py
     ("cicp.hip", ["-ffp-contract=off"]),          # coloured ICP: voxels, correspondences and the reductions must agree with tests/cicp_model.py
     ("descriptor.hip", ["-ffp-contract=off"]),    # descriptor evaluation: the thresholds and counts must agree with tests/descriptor_model.py
+    ("siftdesc.hip", ["-ffp-contract=off"]),      # SIFT descriptors: the base blur must agree with tests/sift_model.py bit for bit
     ("scnet.hip", []),
 ]
 

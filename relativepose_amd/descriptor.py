@@ -5,8 +5,10 @@
                            source descriptor than the true match (mainPanoCompletion2view.py:401-405)
   dense_correspondences    the loaders' `denseCorres` branch for a batch (datasets/SUNCG.py:315-341)
   evalDLDescriptor         mainPanoCompletion2view.py:383-414 with the classes of :535-542
+  sift_rank_dev            relpose_sift_rank (csrc/siftdesc.hip): the same count over 128-byte SIFT descriptors, in integers
+  evalSiftDescriptor       mainPanoCompletion2view.py:353-381, the SIFT baseline of the metric (descriptors: rputil.sift_describe_dev)
 
-Out of scope: evalSiftDescriptor (needs SIFT descriptors; csrc/sift.hip is the detector only), contrast_loss and the training scripts.
+Out of scope: contrast_loss and the training scripts.
 There is no CPU path: every function needs the GPU."""
 import ctypes as C
 
@@ -156,3 +158,68 @@ def evalDLDescriptor(f, feat_off, C_, denseCorres, mask, rng, n_eval=100):
         if (typ[b] < 2).sum() > 0:
             ratiosUnobs.append(ratio[typ[b] < 2].mean())
     return ratiosObs, ratiosUnobs
+
+
+def sift_rank_dev(src, tgt, dense, pair_valid=None):
+    """src, tgt [B,E,128] u8 (the SIFT descriptors of E correspondences in the source and the target), dense [B,P,128] u8 (the target's grid
+    descriptors), pair_valid [B] u8 or None -> (count [B,E] i32, thr [B,E] i32): thr = sum (src - tgt)^2 and count = the number of grid
+    descriptors with sum (src - dense)^2 strictly below it (mainPanoCompletion2view.py:373, :378-379), exact; -1 for invalid pairs."""
+    import torch
+    dev = _lib.require_gpu()
+    u8 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.uint8).contiguous()
+    src, tgt, dense = u8(src), u8(tgt), u8(dense)
+    if src.dim() != 3 or src.shape[2] != 128 or src.shape[1] < 1 or tgt.shape != src.shape:
+        raise ValueError("src and tgt must be [B, E, 128] with E >= 1")
+    if dense.dim() != 3 or dense.shape[0] != src.shape[0] or dense.shape[2] != 128 or dense.shape[1] < 1:
+        raise ValueError("dense must be [B, P, 128] with P >= 1")
+    B, E, P = int(src.shape[0]), int(src.shape[1]), int(dense.shape[1])
+    if pair_valid is not None:
+        pair_valid = u8(pair_valid)
+        if tuple(pair_valid.shape) != (B,):
+            raise ValueError("pair_valid must be [B]")
+    count = torch.empty(B, E, dtype=torch.int32, device=dev)
+    thr = torch.empty(B, E, dtype=torch.int32, device=dev)
+    a = _lib.SiftRankArgs()
+    a.struct_size = C.sizeof(a)
+    a.n_pairs, a.n_slots, a.n_points = B, E, P
+    a.src, a.tgt, a.dense = src.data_ptr(), tgt.data_ptr(), dense.data_ptr()
+    a.pair_valid = pair_valid.data_ptr() if pair_valid is not None else None
+    a.thr, a.count = thr.data_ptr(), count.data_ptr()
+    a.stream = _lib.stream_ptr()
+    _lib.check(_lib.lib().relpose_sift_rank(C.byref(a)), "relpose_sift_rank")
+    return count, thr
+
+
+def evalSiftDescriptor(rgb, denseCorres, rng, n_eval=100, step_size=5):
+    """mainPanoCompletion2view.py:353-381 for a batch: rgb [B,2,3,h,4h] float (numpy or torch; channel 0 is weighted as cv2's B, like the
+    reference's cvtColor call on it), denseCorres as dense_correspondences returns it, rng a np.random.RandomState -> ratios: per valid
+    pair in order, rng.choice(range(K), n_eval) correspondences; SIFT descriptors (size step_size, angle -1) at their source pixels in
+    the source panorama, at their target pixels in the target panorama and on the target's grid range(0, 4h, step_size) x
+    range(0, h, step_size) -- ONE describe call for the batch -- then ONE rank call; ratio = count / P in float64 and its mean over the
+    n_eval correspondences is appended.  The images are rputil.sift_images(rgb, 'second'): trunc(clip(rgb * 255, 0, 255)); the reference's
+    unclipped astype('uint8') differs only for values outside [0, 1]."""
+    import torch
+    from . import rputil
+    u8, _ = rputil.sift_images(rgb, "second")            # [2B, h, 4h, 3]; the metric describes the whole panorama: no crop
+    dev = u8.device
+    B, h, w = int(u8.shape[0]) // 2, int(u8.shape[1]), int(u8.shape[2])
+    K = denseCorres["idxSrc"].shape[1]
+    pv = np.asarray(denseCorres["valid"]).reshape(B) != 0
+    E = int(n_eval)
+    grid = rputil.sift_grid_keypoints(w, h, step_size)
+    P = len(grid)
+    kp = np.zeros((2 * B, E + P, 4), np.float32)
+    kp[:, :, 2], kp[:, :, 3] = step_size, -1
+    kp[1::2, E:] = grid
+    cnt = np.zeros(2 * B, np.int32)
+    for b in range(B):
+        if not pv[b]:
+            continue
+        idx = rng.choice(range(K), E)
+        kp[2 * b, :E, :2] = np.asarray(denseCorres["idxSrc"][b])[idx]
+        kp[2 * b + 1, :E, :2] = np.asarray(denseCorres["idxTgt"][b])[idx]
+        cnt[2 * b], cnt[2 * b + 1] = E, E + P
+    desc = rputil.sift_describe_dev(u8, None, torch.from_numpy(kp).to(dev), torch.from_numpy(cnt).to(dev))["desc"]
+    count, _ = sift_rank_dev(desc[0::2, :E], desc[1::2, :E], desc[1::2, E:], torch.from_numpy(pv.astype(np.uint8)))
+    count = count.cpu().numpy()
+    return [(count[b].astype(np.float64) / P).mean() for b in range(B) if pv[b]]

@@ -259,19 +259,23 @@ def _evaluate_baseline(batches, device, dataset, register, result_path, with_col
     return stats
 
 
-def evaluate_descriptors(batches, net, device, dataset, mask_method, seed=0, n_eval=100, **corres):
+def evaluate_descriptors(batches, net, device, dataset, mask_method, seed=0, n_eval=100, sift_baseline=False, **corres):
     """The reference's descriptor metric (evalDLDescriptor, mainPanoCompletion2view.py:383-414) over batches of pairs with ground-truth
     poses: per batch the level-0 forward the pipeline builds (masked own view, zero warped view), the descriptor = the feature channels
     at the pipeline's feat_off, dense correspondences from the batch's depth and poses (descriptor.dense_correspondences; batch["R"] is
     camera-to-world and is passed as is; `corres` = its keyword overrides) and the rank ratios.  One np.random.RandomState(seed) serves
     every draw, batch after batch.  -> {"pairs", "valid_pairs", "ratiosObs", "ratiosUnobs" (one entry per valid pair with a non-empty
-    class), "ratio_obs", "ratio_unobs" (their means; NaN when empty)}."""
+    class), "ratio_obs", "ratio_unobs" (their means; NaN when empty)}.
+    sift_baseline: also the reference's SIFT baseline on the same correspondences (descriptor.evalSiftDescriptor,
+    mainPanoCompletion2view.py:353-381): the result gains "ratiosSift" (one entry per valid pair) and "ratio_sift".  Its draws come from a
+    second np.random.RandomState(seed + 1), so the other numbers are the same with and without it."""
     import torch
     from . import descriptor, util
     from .pipeline import RelativePosePipeline
     pipe = RelativePosePipeline(net, dataset, mask_method, alter_steps=1)
     rng = np.random.RandomState(seed)
-    obs, unobs, pairs, valid = [], [], 0, 0
+    rng_sift = np.random.RandomState(seed + 1)
+    obs, unobs, sift, pairs, valid = [], [], [], 0, 0
     for batch in batches:
         n = _batch_size(batch)
         sub = _batch_take(batch, np.arange(n))
@@ -285,10 +289,15 @@ def evaluate_descriptors(batches, net, device, dataset, mask_method, seed=0, n_e
         o, u = descriptor.evalDLDescriptor(f, pipe.feat_off, net.out_channels - pipe.feat_off, dc, mask, rng, n_eval=n_eval)
         obs += o
         unobs += u
+        if sift_baseline:
+            sift += descriptor.evalSiftDescriptor(sub["rgb"], dc, rng_sift, n_eval=n_eval)
         pairs += n
         valid += int(dc["valid"].sum())
     mean = lambda v: float(np.mean(v)) if v else float("nan")
-    return {"pairs": pairs, "valid_pairs": valid, "ratiosObs": obs, "ratiosUnobs": unobs, "ratio_obs": mean(obs), "ratio_unobs": mean(unobs)}
+    res = {"pairs": pairs, "valid_pairs": valid, "ratiosObs": obs, "ratiosUnobs": unobs, "ratio_obs": mean(obs), "ratio_unobs": mean(unobs)}
+    if sift_baseline:
+        res["ratiosSift"], res["ratio_sift"] = sift, mean(sift)
+    return res
 
 
 def evaluate_pairs_sharded(pipe, batches, device, result_path=None, names=None, rank=0, world=1, resume=True, round_batches=None,
@@ -414,17 +423,9 @@ def evaluate_pairs_sharded(pipe, batches, device, result_path=None, names=None, 
     return stats if rank == 0 else None
 
 
-def main(argv=None):
-    """python -m relativepose_amd.evaluation --gpus N ...: the sharded evaluation over seeded synthetic scan pairs (no dataset ships with
-    the reference) -- BASELINE configs[3]: a "val split" of --pairs pairs in global batches of --batch, sharded over N GPUs, one pose
-    all_gather, one <exp>.result.npy.  Launched plainly it spawns its N ranks (one per GPU, RCCL); under torchrun it uses the launcher's
-    environment.  Rank 0 prints one JSON line: pairs, seconds, per-overlap-bucket statistics (evaluation.py:321-327)."""
+def _cli_parser():
+    """The argument parser of main()."""
     import argparse
-    import json
-    import os
-    import socket
-    import sys
-    import time
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--dataset", default="scannet", choices=["suncg", "matterport", "scannet"])
@@ -450,7 +451,23 @@ def main(argv=None):
     ap.add_argument("--descriptor-eval", action="store_true",
                     help="the reference's descriptor metric instead of poses (evalDLDescriptor, mainPanoCompletion2view.py:383-414): one JSON "
                          "line with metric, pairs, valid_pairs, ratio_obs, ratio_unobs, seconds")
-    args = ap.parse_args(argv)
+    ap.add_argument("--sift-baseline", action="store_true",
+                    help="--descriptor-eval: also the reference's SIFT baseline of the metric (evalSiftDescriptor, "
+                         "mainPanoCompletion2view.py:353-381): the JSON line gains ratio_sift")
+    return ap
+
+
+def main(argv=None):
+    """python -m relativepose_amd.evaluation --gpus N ...: the sharded evaluation over seeded synthetic scan pairs (no dataset ships with
+    the reference) -- BASELINE configs[3]: a "val split" of --pairs pairs in global batches of --batch, sharded over N GPUs, one pose
+    all_gather, one <exp>.result.npy.  Launched plainly it spawns its N ranks (one per GPU, RCCL); under torchrun it uses the launcher's
+    environment.  Rank 0 prints one JSON line: pairs, seconds, per-overlap-bucket statistics (evaluation.py:321-327)."""
+    import json
+    import os
+    import socket
+    import sys
+    import time
+    args = _cli_parser().parse_args(argv)
 
     if args.descriptor_eval:
         if args.gpus > 1:
@@ -468,11 +485,13 @@ def main(argv=None):
         bs = min(args.batch, 32)
         batches = [SyntheticBatch(min(bs, args.pairs - k), args.seed + k, ds, mm, 1) for k in range(0, args.pairs, bs)]
         t0 = time.perf_counter()
-        r = evaluate_descriptors(batches, net, dev, ds, mm, seed=args.seed)
+        r = evaluate_descriptors(batches, net, dev, ds, mm, seed=args.seed, sift_baseline=args.sift_baseline)
         torch.cuda.synchronize()
-        print(json.dumps({"metric": "descriptor_rank", "pairs": r["pairs"], "valid_pairs": r["valid_pairs"], "ratio_obs": r["ratio_obs"],
-                          "ratio_unobs": r["ratio_unobs"], "seconds": time.perf_counter() - t0, "dataset": ds, "precision": args.precision}),
-              flush=True)
+        line = {"metric": "descriptor_rank", "pairs": r["pairs"], "valid_pairs": r["valid_pairs"], "ratio_obs": r["ratio_obs"],
+                "ratio_unobs": r["ratio_unobs"], "seconds": time.perf_counter() - t0, "dataset": ds, "precision": args.precision}
+        if args.sift_baseline:
+            line["ratio_sift"] = r["ratio_sift"]
+        print(json.dumps(line), flush=True)
         return
 
     if args.method in ("fgs", "gs", "cgs"):

@@ -34,6 +34,8 @@ Operator                    replaces (reference file:line)
   color_registration        the cgs baseline: the gs RANSAC result refined by coloured ICP, baselines.py:110-168 (batched over pairs)
   dense_nn                  the KDTree query of the loaders' dense correspondences, datasets/SUNCG.py:323-332 (batched, with index)
   descriptor_rank           the rank counts of evalDLDescriptor, mainPanoCompletion2view.py:401-405 (batched over pairs)
+  sift_describe             SIFT descriptors of given keypoints: cv2 SIFT_create().compute(gray, keypoints), mainPanoCompletion2view.py:365-377
+  sift_rank                 the rank counts of evalSiftDescriptor, mainPanoCompletion2view.py:373, :378-379 (batched over pairs, exact)
   affinity_topk             rpmodule.py:342-379
   match_pairs               RelativePoseEstimation_helper, rpmodule.py:317-508
 """
@@ -77,6 +79,11 @@ _lib.define("dense_nn(Tensor pc, Tensor valid, Tensor to_world, Tensor query, fl
 # f f32 [2B,Ct,h,4h]; idx_src, idx_tgt i32 [B,K,2]; sel i32 [B,E], pair_valid u8 [B], mask f32 [2B,1,h,4h] (optional) -> count, thr, type [B,E]
 _lib.define("descriptor_rank(Tensor f, int feat_off, int channels, Tensor idx_src, Tensor idx_tgt, Tensor? sel=None, Tensor? pair_valid=None, "
             "Tensor? mask=None) -> (Tensor, Tensor, Tensor)")
+# images / crop as sift_detect; kp f32 [V,n_kp,4] (x, y, size, angle), count i32 [V] (optional); grid_step > 0: the dense grid instead of kp
+# (pass an empty kp) -> desc u8 [V,n_kp,128], desc_f32 f32 [V,n_kp,128] (the values before rounding)
+_lib.define("sift_describe(Tensor images, int[] crop, Tensor kp, Tensor? count=None, int grid_step=0) -> (Tensor, Tensor)")
+# src, tgt u8 [B,E,128], dense u8 [B,P,128], pair_valid u8 [B] (optional) -> count, thr i32 [B,E]
+_lib.define("sift_rank(Tensor src, Tensor tgt, Tensor dense, Tensor? pair_valid=None) -> (Tensor, Tensor)")
 _lib.define("affinity_topk(Tensor feat_s, Tensor weight_s, Tensor feat_t, Tensor weight_t, Tensor ns, Tensor nt, "
             "float[] params, int topK, bool want_wij) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("match_pairs(Tensor pc_s, Tensor normal_s, Tensor feat_s, Tensor weight_s, Tensor pc_t, Tensor normal_t, "
@@ -193,6 +200,20 @@ def _descriptor_rank(f, feat_off, channels, idx_src, idx_tgt, sel=None, pair_val
     return _d.descriptor_rank_dev(f.contiguous(), int(feat_off), int(channels), idx_src, idx_tgt, sel, pair_valid, mask)
 
 
+def _sift_describe(images, crop, kp, count=None, grid_step=0):
+    from . import rputil as _ru
+    if int(grid_step) > 0:
+        r = _ru.sift_describe_grid_dev(images, list(crop) or None, int(grid_step), want_f32=True)
+    else:
+        r = _ru.sift_describe_dev(images, list(crop) or None, kp, count, want_f32=True)
+    return r["desc"], r["desc_f32"]
+
+
+def _sift_rank(src, tgt, dense, pair_valid=None):
+    from . import descriptor as _d
+    return _d.sift_rank_dev(src, tgt, dense, pair_valid)
+
+
 def _affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     wij, cj, cw, keff = _rp.affinity_topk(feat_s.contiguous(), weight_s.contiguous(), feat_t.contiguous(), weight_t.contiguous(),
                                           ns.contiguous(), nt.contiguous(), _para(params, topK), want_wij=bool(want_wij))
@@ -213,7 +234,7 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("sample_primitives", _sample_primitives), ("keypoints_reference", _keypoints_reference), ("affinity_topk", _affinity_topk), ("match_pairs", _match_pairs),
                    ("sift_detect", _sift_detect), ("fast_global_registration", _fast_global_registration),
                    ("global_registration", _global_registration), ("colored_icp", _colored_icp), ("color_registration", _color_registration),
-                   ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank)):
+                   ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -300,6 +321,21 @@ def _m_descriptor_rank(f, feat_off, channels, idx_src, idx_tgt, sel=None, pair_v
     return f.new_empty(B, E, dtype=torch.int32), f.new_empty(B, E, dtype=torch.float32), f.new_empty(B, E, dtype=torch.int32)
 
 
+def _m_sift_describe(images, crop, kp, count=None, grid_step=0):
+    V = images.shape[0]
+    if int(grid_step) > 0:
+        cw, ch = (int(crop[2]), int(crop[3])) if len(crop) else (images.shape[2], images.shape[1])
+        n_kp = len(range(0, cw, int(grid_step))) * len(range(0, ch, int(grid_step)))
+    else:
+        n_kp = kp.shape[1]
+    return images.new_empty(V, n_kp, 128, dtype=torch.uint8), images.new_empty(V, n_kp, 128, dtype=torch.float32)
+
+
+def _m_sift_rank(src, tgt, dense, pair_valid=None):
+    B, E = src.shape[0], src.shape[1]
+    return src.new_empty(B, E, dtype=torch.int32), src.new_empty(B, E, dtype=torch.int32)
+
+
 def _m_affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     B, ns_max, nt_max = feat_s.shape[0], feat_s.shape[1], feat_t.shape[1]
     wij = feat_s.new_empty(B, ns_max, nt_max, dtype=torch.float32) if want_wij else feat_s.new_empty(0)
@@ -317,9 +353,9 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("sample_primitives", _m_sample_primitives), ("keypoints_reference", _m_keypoints_reference), ("affinity_topk", _m_affinity_topk),
                    ("match_pairs", _m_match_pairs), ("sift_detect", _m_sift_detect), ("fast_global_registration", _m_fast_global_registration),
                    ("global_registration", _m_global_registration), ("colored_icp", _m_colored_icp), ("color_registration", _m_color_registration),
-                   ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank)):
+                   ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
-       "color_registration", "dense_nn", "descriptor_rank")
+       "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank")

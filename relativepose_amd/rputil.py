@@ -16,7 +16,9 @@
 
 SIFT detection itself (cv2.xfeatures2d, third-party) is a hook: set_sift_detector(fn), fn(gray uint8 [h,w]) -> [[x, y], ...]; when
 cv2 with xfeatures2d is importable it is the default.  The project's own detector (csrc/sift.hip, batched over views) is
-sift_detect_dev; gpu_sift_detector is a ready-made hook around it: set_sift_detector(rputil.gpu_sift_detector)."""
+sift_detect_dev; gpu_sift_detector is a ready-made hook around it: set_sift_detector(rputil.gpu_sift_detector).
+SIFT descriptors of given keypoints (csrc/siftdesc.hip; what descriptor.evalSiftDescriptor runs on):
+sift_describe_dev / sift_describe_grid_dev."""
 import ctypes as C
 
 import numpy as np
@@ -183,6 +185,83 @@ def gpu_sift_detector(gray):
     """A set_sift_detector hook backed by the HIP detector: gray uint8 [h, w] -> [n, 2] float64 (x, y)."""
     g = np.ascontiguousarray(gray, dtype=np.uint8)
     return sift_detect_dev(g[None], None)[0]
+
+
+def _sift_describe(images, crop, kp, count, step, want_f32, want_base):
+    import torch
+    dev = _lib.require_gpu()
+    if isinstance(images, np.ndarray):
+        images = torch.from_numpy(np.ascontiguousarray(images))
+    if images.dtype != torch.uint8 or images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[3] != 3):
+        raise ValueError("sift_describe: images must be uint8 [V, h, w, 3] (BGR) or [V, h, w] (gray)")
+    images = images.to(dev).contiguous()
+    V, ih, iw = (int(s) for s in images.shape[:3])
+    ch = 3 if images.dim() == 4 else 1
+    x0, y0, cw, chh = (0, 0, iw, ih) if crop is None else (int(c) for c in crop)
+    if V < 1 or not (1 <= cw <= _lib.SIFT_MAX_SIDE and 1 <= chh <= _lib.SIFT_MAX_SIDE) or x0 < 0 or y0 < 0 or x0 + cw > iw or y0 + chh > ih:
+        raise ValueError(f"sift_describe: unsupported crop {cw}x{chh} at ({x0}, {y0}) of {iw}x{ih} (1 <= side <= {_lib.SIFT_MAX_SIDE})")
+    grid = step is not None
+    if grid:
+        step = int(step)
+        if step < 1:
+            raise ValueError("sift_describe_grid: step must be positive")
+        n_kp = len(range(0, cw, step)) * len(range(0, chh, step))
+    else:
+        if isinstance(kp, np.ndarray):
+            kp = torch.from_numpy(np.ascontiguousarray(kp))
+        if kp.dim() != 3 or kp.shape[0] != V or kp.shape[2] != 4:
+            raise ValueError("sift_describe: kp must be [V, n_kp, 4] (x, y, size, angle)")
+        kp = kp.to(device=dev, dtype=torch.float32).contiguous()
+        n_kp = int(kp.shape[1])
+        if count is not None:
+            count = torch.as_tensor(count).to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(count.shape) != (V,):
+                raise ValueError("sift_describe: count must be [V]")
+    out = {"desc": torch.empty(V, n_kp, 128, dtype=torch.uint8, device=dev)}
+    if want_f32:
+        out["desc_f32"] = torch.empty(V, n_kp, 128, dtype=torch.float32, device=dev)
+    if want_base:
+        out["base"] = torch.empty(V, chh, cw, dtype=torch.float32, device=dev)
+    ws = None
+    if not want_base:
+        ws = torch.empty(_lib.lib().relpose_sift_describe_workspace_bytes(V, chh, cw), dtype=torch.uint8, device=dev)
+    a = _lib.SiftDescArgs()
+    a.struct_size = C.sizeof(a)
+    a.n_views, a.images, a.img_h, a.img_w, a.channels = V, images.data_ptr(), ih, iw, ch
+    a.crop_x, a.crop_y, a.crop_w, a.crop_h, a.n_kp, a.grid_step = x0, y0, cw, chh, n_kp, step if grid else 0
+    a.kp = kp.data_ptr() if not grid and n_kp else None
+    a.kp_count = count.data_ptr() if not grid and count is not None else None
+    a.desc = out["desc"].data_ptr() if n_kp else None
+    a.desc_f32 = out["desc_f32"].data_ptr() if want_f32 and n_kp else None
+    a.base = out["base"].data_ptr() if want_base else None
+    a.workspace, a.workspace_bytes = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
+    a.stream = _lib.stream_ptr()
+    _lib.check(_lib.lib().relpose_sift_describe(C.byref(a)), "relpose_sift_describe")
+    return out
+
+
+def sift_describe_dev(images, crop, kp, count=None, want_f32=False, want_base=False):
+    """SIFT descriptors of given keypoints (relpose_sift_describe, csrc/siftdesc.hip): what the reference's
+    cv2.xfeatures2d.SIFT_create().compute(gray, [cv2.KeyPoint(x, y, size)]) returns (mainPanoCompletion2view.py:365-371), by the project's
+    own contract (agreement with cv2 is untested).  images / crop as sift_detect_tensors; kp [V, n_kp, 4] float (x, y, size, angle;
+    cv2.KeyPoint's default angle is -1) in the crop's frame, count [V] or None (all n_kp); tensors or numpy.
+    Returns {"desc": [V, n_kp, 128] u8, and when asked for "desc_f32": [V, n_kp, 128] f32 (the values before rounding),
+    "base": [V, ch, cw] f32 (the blurred gray image)} on the device.  Unused slots read zeros."""
+    return _sift_describe(images, crop, kp, count, None, want_f32, want_base)
+
+
+def sift_grid_keypoints(w, h, step):
+    """The reference's dense grid (mainPanoCompletion2view.py:375-376) as [n, 4] float32 (x, y, size = step, angle = -1), y-major."""
+    xs, ys = np.arange(0, w, step), np.arange(0, h, step)
+    g = np.empty((len(ys), len(xs), 4), np.float32)
+    g[..., 0], g[..., 1], g[..., 2], g[..., 3] = xs[None, :], ys[:, None], step, -1
+    return g.reshape(-1, 4)
+
+
+def sift_describe_grid_dev(images, crop, step, want_f32=False, want_base=False):
+    """sift_describe_dev on the dense grid x in range(0, cw, step), y in range(0, ch, step), y-major, size = step, angle = -1
+    (mainPanoCompletion2view.py:375-377); the keypoints are generated on the device (sift_grid_keypoints lists them)."""
+    return _sift_describe(images, crop, None, None, step, want_f32, want_base)
 
 
 def sift_images(rgb, kind, rgb_full=None):
