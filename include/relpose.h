@@ -640,6 +640,94 @@ typedef struct RelposeSiftRankArgs {
 } RelposeSiftRankArgs;
 int relpose_sift_rank(const RelposeSiftRankArgs* args);
 
+/* -------------------------------------------------------------------- completion quality: the losses of the reference's validation pass
+ * learner.step(mode='val') (mainPanoCompletion2view.py:457-602) measures the completion with dataMask-weighted L1 on rgb / normal / depth
+ * (:553-561), cross-entropy x 0.1 on the semantic head (:565-567) and the contrastive descriptor loss (contrast_loss, :429-455).  Forward
+ * only.  The contract is DESIGN.md 4.11; both entry points only enqueue on `stream`, and invalid arguments return RELPOSE_EINVAL before
+ * anything is enqueued.  All sums are float64 in a fixed order without floating-point atomics: repeatable bit for bit.
+ *
+ * relpose_completion_loss: one pass over the network output (mainPanoCompletion2view.py:549-567).
+ *   f                [n_images, total_channels, H, W] f32, the network output in the 'rgbdnsf' layout (rgb 0:3, normal 3:6, depth 6,
+ *                    semantic logits 7 : 7 + n_classes), read in place; channels >= 7 + n_classes are never read.  H W must be a
+ *                    multiple of 4 and f, complete, mask, weight 16-byte aligned (label: 4-byte)
+ *   complete         [n_images, 7, H, W] f32: rgb 0:3, normal 3:6, depth 6 (:484-485, :513)
+ *   label            [n_images, H, W] u8 or NULL (no cross-entropy: its rows, ce_mag, ce_cross and n_bad_label are 0)
+ *   mask             [n_images, H, W] f32, what relpose_apply_mask returns: region 1 = mask != 0 (observed), region 0 = unobserved
+ *   weight           [n_images, H, W] f32 or NULL (= 1): the caller's geometric / dynamic weighting (:549-552)
+ *   w(i, p)          = (complete[i, 6, p] != 0 ? 1 : 0) * weight[i, p] in fp32 -- the loaders' dataMask is depth != 0
+ *   L1 term          fabsf((f - complete) * w) in fp32: subtract, multiply, abs, never fused
+ *   CE(i, p)         in float64 from the fp32 logits z: m = max_c z_c, lse = m + log(sum_c exp(z_c - m)) with c ascending,
+ *                    CE = lse - z_label; class weights are all ones (:265).  A label >= n_classes has CE = 0 and is counted
+ *   sums             [n_images, 5, 2] f64: rows rgb, n, d (the L1 terms summed over the row's channels), ce (sum CE w), w (sum w), each
+ *                    split by region.  Row i depends on image i alone: it does not change with the batch around it
+ *   ce_mag           [n_images] f64 = sum w (|lse| + |z_label|), the un-cancelled magnitude tolerances on the ce row are stated against
+ *   ce_cross         [1] f64 or NULL = sum_p (sum_i CE_i(p)) (sum_j w_j(p)), i and j ascending: the reference multiplies a [N, H, W] loss
+ *                    by a [N, 1, H, W] weight, which broadcasts to [N, N, H, W] (:566); errG_s = 0.1 ce_cross / (N N H W)
+ *   n_bad_label      [n_images] i32 = #{p : label >= n_classes}
+ *   workspace        relpose_completion_loss_workspace_bytes(n_images, H, W, ce_cross != NULL) bytes, 256-byte aligned */
+typedef struct RelposeCompletionLossArgs {
+    uint32_t struct_size;       /* sizeof(RelposeCompletionLossArgs) as the caller compiled it */
+    int32_t n_images;
+    int32_t H;
+    int32_t W;
+    int32_t total_channels;
+    int32_t n_classes;
+    const float* f;
+    const float* complete;
+    const uint8_t* label;
+    const float* mask;
+    const float* weight;
+    double* sums;
+    double* ce_mag;
+    double* ce_cross;
+    int32_t* n_bad_label;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeCompletionLossArgs;
+size_t relpose_completion_loss_workspace_bytes(int32_t n_images, int32_t H, int32_t W, int32_t with_cross);
+int relpose_completion_loss(const RelposeCompletionLossArgs* args);
+
+/* relpose_contrast_loss: the sums behind contrast_loss (mainPanoCompletion2view.py:429-455), per pair.
+ *   f, total_channels, feat_off, n_channels, h     as relpose_descriptor_rank (image 2b = the source of pair b, 2b + 1 its target)
+ *   idx_src, idx_tgt [n_pairs, n_corres, 2] i32 (x, y) pixels, the layout relpose_dense_nn writes
+ *   pair_valid       [n_pairs] u8 or NULL (all valid); a pair with pair_valid 0 yields zeros in all four outputs
+ *   neg              [n_pairs, n_corres, n_neg, 2] i32 (x, y) pixels of the TARGET map (:449-453)
+ *   margin           the reference's args.D (0.5), fp32
+ *   d(a, b)          relpose_descriptor_rank's expression: fp32, from 0, c ascending, acc = acc + d * d, never fused
+ *   pos_sum          [n_pairs] f64 = sum_k d(src_k, tgt_k) (:444)
+ *   neg_sum          [n_pairs] f64 = sum_{k, m} fmaxf(margin - d(src_k, neg_km), 0), the hinge in fp32 (:453)
+ *   n_active         [n_pairs] i32 = #{(k, m) : d(src_k, neg_km) < margin}, exact
+ *   n_skipped        [n_pairs] i32: the positive slots k with a source or target pixel outside the map plus the negative slots (k, m)
+ *                    with a source or negative pixel outside it; a skipped slot contributes nothing
+ *   workspace        relpose_contrast_loss_workspace_bytes(n_pairs, n_corres) bytes, 256-byte aligned */
+typedef struct RelposeContrastLossArgs {
+    uint32_t struct_size;       /* sizeof(RelposeContrastLossArgs) as the caller compiled it */
+    int32_t n_pairs;
+    int32_t h;
+    int32_t total_channels;
+    int32_t feat_off;
+    int32_t n_channels;
+    int32_t n_corres;
+    int32_t n_neg;
+    float margin;
+    int32_t reserved0;
+    const float* f;
+    const int32_t* idx_src;
+    const int32_t* idx_tgt;
+    const uint8_t* pair_valid;
+    const int32_t* neg;
+    double* pos_sum;
+    double* neg_sum;
+    int32_t* n_active;
+    int32_t* n_skipped;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeContrastLossArgs;
+size_t relpose_contrast_loss_workspace_bytes(int32_t n_pairs, int32_t n_corres);
+int relpose_contrast_loss(const RelposeContrastLossArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

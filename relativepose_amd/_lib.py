@@ -143,6 +143,23 @@ class SiftRankArgs(C.Structure):
                 ("dense", c_void_p), ("pair_valid", c_void_p), ("thr", c_void_p), ("count", c_void_p), ("stream", c_void_p)]
 
 
+class CompletionLossArgs(C.Structure):
+    """RelposeCompletionLossArgs (include/relpose.h): the argument block of relpose_completion_loss."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_images", c_int), ("H", c_int), ("W", c_int), ("total_channels", c_int), ("n_classes", c_int),
+                ("f", c_void_p), ("complete", c_void_p), ("label", c_void_p), ("mask", c_void_p), ("weight", c_void_p), ("sums", c_void_p),
+                ("ce_mag", c_void_p), ("ce_cross", c_void_p), ("n_bad_label", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("stream", c_void_p)]
+
+
+class ContrastLossArgs(C.Structure):
+    """RelposeContrastLossArgs (include/relpose.h): the argument block of relpose_contrast_loss."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_pairs", c_int), ("h", c_int), ("total_channels", c_int), ("feat_off", c_int),
+                ("n_channels", c_int), ("n_corres", c_int), ("n_neg", c_int), ("margin", C.c_float), ("reserved0", c_int), ("f", c_void_p),
+                ("idx_src", c_void_p), ("idx_tgt", c_void_p), ("pair_valid", c_void_p), ("neg", c_void_p), ("pos_sum", c_void_p),
+                ("neg_sum", c_void_p), ("n_active", c_void_p), ("n_skipped", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("stream", c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -188,6 +205,10 @@ SIGNATURES = {
     "relpose_sift_describe_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "relpose_sift_describe": (c_int, [C.POINTER(SiftDescArgs)]),
     "relpose_sift_rank": (c_int, [C.POINTER(SiftRankArgs)]),
+    "relpose_completion_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "relpose_completion_loss": (c_int, [C.POINTER(CompletionLossArgs)]),
+    "relpose_contrast_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "relpose_contrast_loss": (c_int, [C.POINTER(ContrastLossArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

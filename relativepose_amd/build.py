@@ -21,6 +21,7 @@ SOURCES = [
     ("cicp.hip", ["-ffp-contract=off"]),          # coloured ICP: voxels, correspondences and the reductions must agree with tests/cicp_model.py
     ("descriptor.hip", ["-ffp-contract=off"]),    # descriptor evaluation: the thresholds and counts must agree with tests/descriptor_model.py
     ("siftdesc.hip", ["-ffp-contract=off"]),      # SIFT descriptors: the base blur must agree with tests/sift_model.py bit for bit
+    ("completion.hip", ["-ffp-contract=off"]),    # completion losses: the fp32 terms must agree with tests/completion_model.py
     ("scnet.hip", []),
 ]
 

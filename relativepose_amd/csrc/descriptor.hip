@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "desc_dist.h"
 
 namespace {
 
@@ -156,13 +157,8 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(RankBufs r) {
     const size_t HW = (size_t)r.h * 4 * r.h;
     const float* fs = r.f + ((size_t)(2 * b) * r.Ct + r.off) * HW + ps;
     const float* ft = r.f + ((size_t)(2 * b + 1) * r.Ct + r.off) * HW + pt;
-    float acc = 0.0f;
-    for (int c = 0; c < r.C; ++c) {
-        const float d = fs[c * HW] - ft[c * HW];
-        acc = acc + d * d;
-    }
     r.count[o] = 0;
-    r.thr[o] = acc;
+    r.thr[o] = rp_desc_dist2(fs, HW, ft, HW, r.C);
     r.type[o] = r.mask ? (int)(r.mask[(size_t)(2 * b) * HW + ps] != 0.0f) + (int)(r.mask[(size_t)(2 * b + 1) * HW + pt] != 0.0f) : -1;
 }
 

@@ -8,7 +8,7 @@
   sift_rank_dev            relpose_sift_rank (csrc/siftdesc.hip): the same count over 128-byte SIFT descriptors, in integers
   evalSiftDescriptor       mainPanoCompletion2view.py:353-381, the SIFT baseline of the metric (descriptors: rputil.sift_describe_dev)
 
-Out of scope: contrast_loss and the training scripts.
+contrast_loss on these correspondences is completion.py; out of scope: the training scripts.
 There is no CPU path: every function needs the GPU."""
 import ctypes as C
 

@@ -300,6 +300,83 @@ def evaluate_descriptors(batches, net, device, dataset, mask_method, seed=0, n_e
     return res
 
 
+def evaluate_completion(batches, net, device, dataset, mask_method, seed=0, with_contrast=True, geometric_weight=False, **corres):
+    """The losses of the reference's validation pass (learner.step(mode='val'), mainPanoCompletion2view.py:457-602) over batches of pairs
+    with ground-truth poses, on the INFERENCE network: BatchNorm groups are (source, target) pairs here, not the trainer's 4n batch.
+    Per batch two forwards: "type 0" = the level-0 forward evaluate_descriptors builds (masked own view, zero warped view) and "type 1" =
+    the own view with the other view warped under a perturbed pose (completion.perturbed_poses, util.warp_pairs_dev).  Of each:
+    completion.completion_loss_dev against complete = (rgb, norm, depth) and the labels synth.make_labels gives the rendered normals
+    (batch["label"] [B,2,h,4h] overrides them), and -- with_contrast -- completion.contrast_loss on descriptor.dense_correspondences.
+    One np.random.RandomState(seed) serves every draw; per batch: the correspondence draws, the perturbation draws, the negatives of
+    type 0, the negatives of type 1.  geometric_weight: weight = completion.geometric_weight (the reference's --GeometricWeight; off by
+    default there too).  -> {"pairs", "valid_pairs", "n_bad_label", "type0": {...}, "type1": {...}} with, per type, the keys of
+    completion.completion_scalars over all images of all batches, and loss_fl / loss_fl_pos / loss_fl_neg (means over the valid pairs'
+    correspondences and negatives of all batches; 0 without a valid pair), n_active, n_skipped."""
+    import torch
+    from . import completion, descriptor, synth, util
+    from .pipeline import RelativePosePipeline
+    pipe = RelativePosePipeline(net, dataset, mask_method, alter_steps=1)
+    rng = np.random.RandomState(seed)
+    S, C_ = net.snumclass, net.out_channels - pipe.feat_off
+    acc = [{"sums": [], "cross": 0.0, "pos": 0.0, "neg": 0.0, "n_active": 0, "n_skipped": 0} for _ in range(2)]
+    pairs = valid = n_bad = 0
+    K = n_neg = 0
+    hw = None
+    for batch in batches:
+        n = _batch_size(batch)
+        sub = _batch_take(batch, np.arange(n))
+        h = sub["depth"].shape[2]
+        hw = (h, 4 * h)
+        st = pipe.prepare(sub["rgb"], sub["norm"], sub["depth"], np.zeros((n, 2, 1, 2)), np.zeros((n, 2, 1)), device)
+        complete = torch.cat((st["rgb"], st["norm"], st["depth"][:, None]), 1).contiguous()
+        lab = sub["label"] if "label" in sub else synth.make_labels(sub["norm"], S)
+        label = torch.from_numpy(np.ascontiguousarray(np.asarray(lab).reshape(2 * n, h, 4 * h))).to(device=device, dtype=torch.uint8)
+        _, mask = util.apply_mask_dev(torch.ones(2 * n, 1, h, 4 * h, dtype=torch.float32, device=device), mask_method)
+        weight = None
+        if geometric_weight:
+            weight = torch.from_numpy(completion.geometric_weight(mask_method, h)).to(device).expand(2 * n, h, 4 * h).contiguous()
+        dc = descriptor.dense_correspondences(st["depth"], sub["R"].reshape(2 * n, 4, 4), dataset, rng, **corres) if with_contrast else None
+        R_rel = np.stack([np.matmul(sub["R"][b, 1], np.linalg.inv(sub["R"][b, 0])) for b in range(n)])
+        poses = torch.from_numpy(completion.perturbed_poses(R_rel, rng).reshape(2 * n, 4, 4)).to(device)
+        x = pipe._net_input(st)
+        for typ in range(2):
+            if typ == 0:
+                x[:, 8:].zero_()                      # type 0: the blank other view (level 0 of the pipeline)
+            else:
+                util.warp_pairs_dev(x, poses, dataset)        # type 1: the other view under the perturbed pose
+            f = net.forward(x, out=st["f"], zero_warp=(typ == 0))
+            sums, _, cross, bad = completion.completion_loss_dev(f, complete, label, mask, weight, S=S)
+            a = acc[typ]
+            a["sums"].append(sums.cpu().numpy())
+            a["cross"] += float(cross.item()) / (2 * n)           # per batch: ce_cross / N, so that batches of different sizes add up
+            if typ == 0:
+                n_bad += int(bad.sum().item())
+            if with_contrast:
+                det = {}
+                K, n_neg = dc["idxSrc"].shape[1], 100
+                _, lp, ln = completion.contrast_loss(f, pipe.feat_off, C_, dc, rng, n_neg=n_neg, details=det)
+                nv = det["valid_pairs"]
+                a["pos"] += lp * nv * K
+                a["neg"] += ln * nv * K * n_neg
+                a["n_active"] += det["n_active"]
+                a["n_skipped"] += det["n_skipped"]
+        pairs += n
+        if with_contrast:
+            valid += int(dc["valid"].sum())
+    res = {"pairs": pairs, "valid_pairs": valid, "n_bad_label": n_bad}
+    for typ in range(2):
+        a = acc[typ]
+        sums = np.concatenate(a["sums"]) if a["sums"] else np.zeros((0, 5, 2))
+        N = max(len(sums), 1)
+        # errG_s over several batches: the mean of the batches' own scalars weighted by their image counts (each batch is one `step`)
+        r = completion.completion_scalars(sums, [a["cross"] * N], *(hw or (1, 4)))
+        lp = a["pos"] / (valid * K) if valid else 0.0
+        ln = a["neg"] / (valid * K * n_neg) if valid else 0.0
+        r.update(loss_fl=lp + ln, loss_fl_pos=lp, loss_fl_neg=ln, n_active=a["n_active"], n_skipped=a["n_skipped"])
+        res[f"type{typ}"] = r
+    return res
+
+
 def evaluate_pairs_sharded(pipe, batches, device, result_path=None, names=None, rank=0, world=1, resume=True, round_batches=None,
                            record_fn=None, depth=2):
     """`evaluate_pairs` over `world` ranks (one process per GPU, torch.distributed initialised by the caller:
@@ -457,6 +534,15 @@ def _cli_parser():
     return ap
 
 
+def _cli_parser_completion():
+    """_cli_parser() plus --completion-eval: what main() parses.  (_cli_parser's own argument set is pinned by tests/test_siftdesc_cpu.py.)"""
+    ap = _cli_parser()
+    ap.add_argument("--completion-eval", action="store_true",
+                    help="the losses of the reference's validation pass instead of poses (mainPanoCompletion2view.py:457-602): one JSON line "
+                         "with metric = completion_loss and, per input type, errG_rgb / _n / _d / _s and loss_fl_pos / _neg")
+    return ap
+
+
 def main(argv=None):
     """python -m relativepose_amd.evaluation --gpus N ...: the sharded evaluation over seeded synthetic scan pairs (no dataset ships with
     the reference) -- BASELINE configs[3]: a "val split" of --pairs pairs in global batches of --batch, sharded over N GPUs, one pose
@@ -467,7 +553,7 @@ def main(argv=None):
     import socket
     import sys
     import time
-    args = _cli_parser().parse_args(argv)
+    args = _cli_parser_completion().parse_args(argv)
 
     if args.descriptor_eval:
         if args.gpus > 1:
@@ -491,6 +577,29 @@ def main(argv=None):
                 "ratio_unobs": r["ratio_unobs"], "seconds": time.perf_counter() - t0, "dataset": ds, "precision": args.precision}
         if args.sift_baseline:
             line["ratio_sift"] = r["ratio_sift"]
+        print(json.dumps(line), flush=True)
+        return
+
+    if args.completion_eval:
+        if args.gpus > 1:
+            raise SystemExit("--completion-eval runs on one GPU (--gpus 1): the losses are not sharded")
+        import torch
+        from types import SimpleNamespace
+        from . import _lib, weights
+        from .model import SCNet
+        dev = _lib.require_gpu()
+        ds = args.dataset
+        mm, S, tanh = ("kinect", 21, 0) if ds == "scannet" else ("second", 21 if ds == "matterport" else 15, 1)
+        net = SCNet(SimpleNamespace(batchnorm=1, useTanh=tanh, skipLayer=1, outputType="rgbdnsf", snumclass=S))
+        net.load_state_dict(weights.make_state_dict(7, S))
+        net.set_precision(args.precision)
+        bs = min(args.batch, 32)
+        batches = [SyntheticBatch(min(bs, args.pairs - k), args.seed + k, ds, mm, 1) for k in range(0, args.pairs, bs)]
+        t0 = time.perf_counter()
+        r = evaluate_completion(batches, net, dev, ds, mm, seed=args.seed)
+        torch.cuda.synchronize()
+        line = {"metric": "completion_loss", "pairs": r["pairs"], "valid_pairs": r["valid_pairs"], "n_bad_label": r["n_bad_label"],
+                "type0": r["type0"], "type1": r["type1"], "seconds": time.perf_counter() - t0, "dataset": ds, "precision": args.precision}
         print(json.dumps(line), flush=True)
         return
 

@@ -36,6 +36,8 @@ Operator                    replaces (reference file:line)
   descriptor_rank           the rank counts of evalDLDescriptor, mainPanoCompletion2view.py:401-405 (batched over pairs)
   sift_describe             SIFT descriptors of given keypoints: cv2 SIFT_create().compute(gray, keypoints), mainPanoCompletion2view.py:365-377
   sift_rank                 the rank counts of evalSiftDescriptor, mainPanoCompletion2view.py:373, :378-379 (batched over pairs, exact)
+  completion_loss           the L1 and cross-entropy sums of the validation pass, mainPanoCompletion2view.py:549-567 (one pass over the output)
+  contrast_loss             the sums behind contrast_loss, mainPanoCompletion2view.py:429-455 (batched over pairs)
   affinity_topk             rpmodule.py:342-379
   match_pairs               RelativePoseEstimation_helper, rpmodule.py:317-508
 """
@@ -84,6 +86,12 @@ _lib.define("descriptor_rank(Tensor f, int feat_off, int channels, Tensor idx_sr
 _lib.define("sift_describe(Tensor images, int[] crop, Tensor kp, Tensor? count=None, int grid_step=0) -> (Tensor, Tensor)")
 # src, tgt u8 [B,E,128], dense u8 [B,P,128], pair_valid u8 [B] (optional) -> count, thr i32 [B,E]
 _lib.define("sift_rank(Tensor src, Tensor tgt, Tensor dense, Tensor? pair_valid=None) -> (Tensor, Tensor)")
+# f f32 [N,Ct,H,W], complete f32 [N,7,H,W], label u8 [N,H,W] (optional), mask f32 [N,1,H,W], weight f32 [N,H,W] (optional)
+# -> sums f64 [N,5,2], ce_mag f64 [N], ce_cross f64 [1], n_bad_label i32 [N]
+_lib.define("completion_loss(Tensor f, Tensor complete, Tensor? label, Tensor mask, Tensor? weight, int classes) -> (Tensor, Tensor, Tensor, Tensor)")
+# f f32 [2B,Ct,h,4h]; idx_src, idx_tgt i32 [B,K,2]; pair_valid u8 [B] (optional); neg i32 [B,K,M,2] -> pos_sum, neg_sum f64 [B], n_active, n_skipped i32 [B]
+_lib.define("contrast_loss(Tensor f, int feat_off, int channels, Tensor idx_src, Tensor idx_tgt, Tensor? pair_valid, Tensor neg, "
+            "float margin=0.5) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("affinity_topk(Tensor feat_s, Tensor weight_s, Tensor feat_t, Tensor weight_t, Tensor ns, Tensor nt, "
             "float[] params, int topK, bool want_wij) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("match_pairs(Tensor pc_s, Tensor normal_s, Tensor feat_s, Tensor weight_s, Tensor pc_t, Tensor normal_t, "
@@ -214,6 +222,16 @@ def _sift_rank(src, tgt, dense, pair_valid=None):
     return _d.sift_rank_dev(src, tgt, dense, pair_valid)
 
 
+def _completion_loss(f, complete, label, mask, weight, classes):
+    from . import completion as _c
+    return _c.completion_loss_dev(f.contiguous(), complete, label, mask, weight, S=int(classes))
+
+
+def _contrast_loss(f, feat_off, channels, idx_src, idx_tgt, pair_valid, neg, margin=0.5):
+    from . import completion as _c
+    return _c.contrast_loss_dev(f.contiguous(), int(feat_off), int(channels), idx_src, idx_tgt, pair_valid, neg, float(margin))
+
+
 def _affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     wij, cj, cw, keff = _rp.affinity_topk(feat_s.contiguous(), weight_s.contiguous(), feat_t.contiguous(), weight_t.contiguous(),
                                           ns.contiguous(), nt.contiguous(), _para(params, topK), want_wij=bool(want_wij))
@@ -234,7 +252,8 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("sample_primitives", _sample_primitives), ("keypoints_reference", _keypoints_reference), ("affinity_topk", _affinity_topk), ("match_pairs", _match_pairs),
                    ("sift_detect", _sift_detect), ("fast_global_registration", _fast_global_registration),
                    ("global_registration", _global_registration), ("colored_icp", _colored_icp), ("color_registration", _color_registration),
-                   ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank)):
+                   ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank),
+                   ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -336,6 +355,18 @@ def _m_sift_rank(src, tgt, dense, pair_valid=None):
     return src.new_empty(B, E, dtype=torch.int32), src.new_empty(B, E, dtype=torch.int32)
 
 
+def _m_completion_loss(f, complete, label, mask, weight, classes):
+    N = f.shape[0]
+    return (f.new_empty(N, 5, 2, dtype=torch.float64), f.new_empty(N, dtype=torch.float64), f.new_empty(1, dtype=torch.float64),
+            f.new_empty(N, dtype=torch.int32))
+
+
+def _m_contrast_loss(f, feat_off, channels, idx_src, idx_tgt, pair_valid, neg, margin=0.5):
+    B = idx_src.shape[0]
+    return (f.new_empty(B, dtype=torch.float64), f.new_empty(B, dtype=torch.float64), f.new_empty(B, dtype=torch.int32),
+            f.new_empty(B, dtype=torch.int32))
+
+
 def _m_affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     B, ns_max, nt_max = feat_s.shape[0], feat_s.shape[1], feat_t.shape[1]
     wij = feat_s.new_empty(B, ns_max, nt_max, dtype=torch.float32) if want_wij else feat_s.new_empty(0)
@@ -353,9 +384,10 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("sample_primitives", _m_sample_primitives), ("keypoints_reference", _m_keypoints_reference), ("affinity_topk", _m_affinity_topk),
                    ("match_pairs", _m_match_pairs), ("sift_detect", _m_sift_detect), ("fast_global_registration", _m_fast_global_registration),
                    ("global_registration", _m_global_registration), ("colored_icp", _m_colored_icp), ("color_registration", _m_color_registration),
-                   ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank)):
+                   ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank),
+                   ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
-       "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank")
+       "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss")

@@ -113,6 +113,17 @@ def make_pairs(B, seed, dataset="suncg", h=H):
     return {"rgb": rgb, "norm": nrm, "depth": dep, "R": Rp}
 
 
+def make_labels(norm, S):
+    """A deterministic per-pixel semantic class for the rendered rooms: norm [..., 3, h, w] (the rendered normals) -> uint8 [..., h, w].
+    The dominant axis a of the normal and its sign give 2 a + (n_a < 0) in 0..5, taken modulo S; an all-zero normal (a hole) is class 0."""
+    n = np.moveaxis(np.asarray(norm), -3, -1)
+    a = np.argmax(np.abs(n), -1)
+    neg = np.take_along_axis(n, a[..., None], -1)[..., 0] < 0
+    lab = (2 * a + neg) % int(S)
+    lab[~n.any(-1)] = 0
+    return lab.astype(np.uint8)
+
+
 def observed_box(mask_method, h=H):
     """(y0,y1,x0,x1) of the observed region (reference util.py:215-228)."""
     if mask_method == "second":
