@@ -88,8 +88,10 @@ void relpose_default_params(RelposeParams* p_host);
  *                                   one knob whose settings agree to round-off only (both converge to 1e-13; the number of Lanczos
  *                                   steps differs)
  *   RELPOSE_TUNE_HEADS_KERNEL       0 = SCNet's heads on the streamed kernel (default), 1 = on the lane-per-pixel kernel (same bits)
- *   RELPOSE_TUNE_DECONV_STRIP       0 = SCNet's split-K deconv4 / deconv5 on the phase strip kernel (default), 1 = on the implicit-GEMM
- *                                   kernel (same K split, same bits); read when a forward looks up its plan: each value has plans of its own */
+ *   RELPOSE_TUNE_DECONV_STRIP       0 = SCNet's deconv4 / deconv5 on the phase strip kernel (default): the split-K launches, and deconv4's
+ *                                   unsplit launch of the three-piece bf16 modes (direct stores, fused BatchNorm records), 1 = on the
+ *                                   implicit-GEMM kernel (same K split, same order of every sum, same bits); read when a forward looks
+ *                                   up its plan: each value has plans of its own */
 enum { RELPOSE_TUNE_AFFINITY_KERNEL = 0, RELPOSE_TUNE_FIT_MAX_PRODUCTS = 1, RELPOSE_TUNE_FIT_CLUSTER = 2,
        RELPOSE_TUNE_FIT_GLOBAL_VECTORS = 3, RELPOSE_TUNE_FIT_FIXED_CHECKS = 4, RELPOSE_TUNE_HEADS_KERNEL = 5, RELPOSE_TUNE_DECONV_STRIP = 6,
        RELPOSE_TUNE_COUNT = 8 };
@@ -861,6 +863,12 @@ int relpose_stream_destroy(void* stream);
  * model/mymodel.py:259-380; the level-0 plan and the self-stream cache count what they really launch.  bench.py divides the two for
  * its plan-aware in-loop roofline ("roofline.in_loop"). */
 int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n_images, int32_t flags, int32_t self_cached, double* macs_host);
+
+/* Which kernel the plain plan of n_images runs `layer` ("deconv4", ...) on under the current precision and tuning knobs (host-only, a dry-run
+ * plan build): 1 = the phase strip kernel (deconv_strip_kernel) as a split-K launch, 2 = that kernel unsplit (direct stores and fused
+ * BatchNorm records), 0 = another kernel, <0 = invalid argument or unknown layer.  For tests that
+ * compare the two arms of RELPOSE_TUNE_DECONV_STRIP. */
+int relpose_scnet_layer_kernel(RelposeSCNet* net, const char* layer, int32_t n_images);
 
 /* Debug: copy a raw (pre-BatchNorm) layer output of the last forward, NHWC float32, to out (device).
  * Returns the number of floats written (or needed if out is NULL), <0 if unknown. */

@@ -220,6 +220,7 @@ SIGNATURES = {
     "relpose_scnet_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "relpose_scnet_forward_ex": (c_int, [c_void_p, C.POINTER(ForwardArgs)]),
     "relpose_scnet_plan_macs": (c_int, [c_void_p, c_int, c_int, c_int, C.POINTER(c_double)]),
+    "relpose_scnet_layer_kernel": (c_int, [c_void_p, c_char_p, c_int]),
     "relpose_scnet_read_tap": (c_int64, [c_void_p, c_char_p, c_void_p, c_void_p, c_void_p]),
     "relpose_scnet_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int,
                                       C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_int64), c_void_p]),

@@ -1452,7 +1452,9 @@ __global__ __launch_bounds__(256, SPLIT >= 4 ? 2 : 3) void conv_s2_strip_kernel(
 // inner; slices cut at the same k-tiles), products and transforms are the same expressions: every accumulator receives the same MFMAs
 // in the same order and the partial sums [ks][M][cout_pad] are bitwise those of the implicit GEMM (tests/test_gpu_deconv_strip.py).
 // descs: the 4 phase descriptors of head blockIdx.z; blockIdx.x: conv_igemm_kernel's ninner == 4 order (the four phases of a spatial
-// tile back to back on one XCD: they read the same input lines); blockIdx.y = (K slice, N tile).  Split-K launches only.
+// tile back to back on one XCD: they read the same input lines); blockIdx.y = (K slice, N tile).
+// Epilogues: the partial sums of a K slice (split-K launches), or -- three-piece bf16 instantiations, ksplit == 1: deconv4 there -- direct
+// stores to the phase's output pixels with the fused BatchNorm records added in conv_igemm_kernel<2, 2, 2, 2>'s order (same bits).
 // Workgroups per CU: 3 with fp32 products (<= 168 VGPRs), 2 in the 16-bit modes (the f16 modes spill 14-31 registers at 168; the
 // three-piece bf16 rows take 65 KB of LDS).
 template <int NI, int SPLIT = 0>
@@ -1619,6 +1621,88 @@ __global__ __launch_bounds__(256, SPLIT == 0 ? 3 : 2) void deconv_strip_kernel(c
 #undef RP_DS_STORE_A
 #undef RP_DS_LOAD_B
 #undef RP_DS_STORE_B
+    if constexpr (S3) {
+        if (d.ksplit == 1) {
+            // Direct-store epilogue (one slice covering all of K: deconv4 in the three-piece bf16 modes; no weight pre-scale to undo there).
+            // BatchNorm records [mtile][2 slots][cout_pad][2], bitwise those of conv_igemm_kernel<2, 2, 2, 2>: there a lane adds the 16
+            // rows of 32-row block 2 wm, then those of block 2 wm + 1, into ONE float64 chain per column and slot (sums of squares are
+            // not exact, so the order counts).  Here a wave owns one 32-row block: waves 1 / 3 continue the per-lane chains of waves
+            // 0 / 2 (handed over through LDS: same lane, same columns), then lane pair (xor 32) and 0 + wm 0 + wm 1 as there.
+            if (d.stat_part) {
+                static_assert(SMAX * LD * 4 >= (2 * 2 * 128 * 2 + 2 * NI * 4 * 64) * 8, "statistics scratch fits the A strip");
+                double* red = reinterpret_cast<double*>(At);                  // [2 slots][2 wm][128][2]; the main loop ended with a barrier
+                double* chain = red + 2 * 2 * 128 * 2;                        // [2 wm][NI][4][64 lanes]
+                const int wm = wave >> 1;
+                const int gb = 2 * (g0 + 1) * hw;                             // first row of the tile's second group slot
+                double s0[NI], q0s[NI], s1[NI], q1s[NI];
+#pragma unroll
+                for (int pass = 0; pass < 2; ++pass) {
+                    if ((wave & 1) == pass) {
+#pragma unroll
+                        for (int j = 0; j < NI; ++j) {
+                            if (pass == 0) { s0[j] = 0; q0s[j] = 0; s1[j] = 0; q1s[j] = 0; }
+                            else {
+                                const double* c = chain + ((wm * NI + j) * 4) * 64 + lane;
+                                s0[j] = c[0]; q0s[j] = c[64]; s1[j] = c[128]; q1s[j] = c[192];
+                            }
+                        }
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int m = m0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h;
+                            const int sl = m >= d.M ? -1 : (m >= gb ? 1 : 0);          // = min((img >> 1) - g0, 1); rows past M: neither slot
+#pragma unroll
+                            for (int j = 0; j < NI; ++j) {
+                                const double v = (double)acc[0][j][r];
+                                const double v0 = sl == 0 ? v : 0.0, v1 = sl == 1 ? v : 0.0;   // branch-free: the other slot adds +0
+                                // (the same expressions as in conv_igemm_kernel: the compiler must contract q += v v the same way in both
+                                // kernels -- an fma here and a mul + add there would differ in the last bit; the GPU test compares the bits)
+                                s0[j] += v0; q0s[j] += v0 * v0; s1[j] += v1; q1s[j] += v1 * v1;
+                            }
+                        }
+#pragma unroll
+                        for (int j = 0; j < NI; ++j) {
+                            if (pass == 0) {
+                                double* c = chain + ((wm * NI + j) * 4) * 64 + lane;
+                                c[0] = s0[j]; c[64] = q0s[j]; c[128] = s1[j]; c[192] = q1s[j];
+                            } else {
+                                s0[j] += rp_shfl_xor_d(s0[j], 32); q0s[j] += rp_shfl_xor_d(q0s[j], 32);
+                                s1[j] += rp_shfl_xor_d(s1[j], 32); q1s[j] += rp_shfl_xor_d(q1s[j], 32);
+                                if (lane < 32) {
+                                    const int cl = j * 32 + lane;
+                                    red[((0 * 2 + wm) * 128 + cl) * 2 + 0] = s0[j]; red[((0 * 2 + wm) * 128 + cl) * 2 + 1] = q0s[j];
+                                    red[((1 * 2 + wm) * 128 + cl) * 2 + 0] = s1[j]; red[((1 * 2 + wm) * 128 + cl) * 2 + 1] = q1s[j];
+                                }
+                            }
+                        }
+                    }
+                    __syncthreads();
+                }
+                {
+                    const int sl = tid >> 7, cl = tid & 127;                   // 256 threads = 2 slots x 128 columns
+                    double a = 0, b = 0;
+#pragma unroll
+                    for (int w = 0; w < 2; ++w) { a += red[((sl * 2 + w) * 128 + cl) * 2]; b += red[((sl * 2 + w) * 128 + cl) * 2 + 1]; }
+                    double* o = d.stat_part + (((size_t)mtile * 2 + sl) * d.cout_pad + n0 + cl) * 2;
+                    rp_stg(o, a); rp_stg(o + 1, b);
+                }
+            }
+            // each row to its phase's output pixel (rows past M hold copies of row M - 1: not stored)
+            const int col0 = n0 + l31;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (m >= d.M) continue;
+                const int img = m / hw, rem = m - img * hw;
+                const int yp = rem / d.Win, xp = rem - yp * d.Win;
+                const int pix = (img * d.Hout + yp * d.osy + d.py) * d.Wout + xp * d.osx + d.px;
+                float* yo = d.y + (size_t)pix * d.ycstride + d.ychoff + col0;
+#pragma unroll
+                for (int j = 0; j < NI; ++j)
+                    if (col0 + j * 32 < d.Cout) rp_stg(yo + j * 32, acc[0][j][r]);
+            }
+            return;
+        }
+    }
     // partial sums of this K slice (an empty slice writes zeros): reduced in fixed order by splitk_reduce_kernel
     const float wsc = (SPLIT == 2 || SPLIT == 3) ? d.wscale : 1.f;             // (16-bit modes: the power-of-two weight pre-scale, exact)
     float* po = d.partial + (size_t)ks * d.M * d.cout_pad;
@@ -2867,6 +2951,8 @@ struct Builder {
     int force_ksplit = 0, shared_slices = 0;   // conv4: 6 K slices = the six 128-channel stream blocks of A3 (in EVERY plan: same numerics);
                                                 // zero-warp plans mark the warped streams' slices shared (ConvDesc::shared_slices)
     int nimg = 0;               // images of the members added by conv() (0 = n): RELPOSE_FWD_ZERO_WARP plans run the warped streams on 2
+    std::string probe_layer;    // relpose_scnet_layer_kernel: the layer asked about and the index of its first descriptor
+    int probe_desc = -1;
 
     float* buf(const std::string& b);
     float2* ssb(const std::string& b);
@@ -2934,6 +3020,7 @@ void Builder::conv(const std::string& layer, Src s0, const Src* s1, int Hin, con
     const Layer& L = net->layers[layer];
     const Buf& O = net->bufs[out];
     const int Hout = O.H;
+    if (probe_desc < 0 && !probe_layer.empty() && layer == probe_layer) probe_desc = (int)plan->descs.size();
     for (const Phase& P : L.phases) {
         ConvDesc d;
         memset(&d, 0, sizeof(d));
@@ -3077,17 +3164,19 @@ void Builder::end_group() {
     while (!dtile && s2_cfg < 0 && tiles * ksplit < want_tiles && ksplit < 64 && min_kt / (ksplit * 2) >= min_slice) ksplit *= 2;
     if (force_ksplit && !dtile && s2_cfg < 0) ksplit = force_ksplit;
     // Phase strip kernel (deconv_strip_kernel): the 4 phases of stride-2 4x4 transposed convs with Cout a multiple of 128 whose input grid
-    // does not tile into patches (deconv4: 28 x 28, deconv5: 14 x 14), split-K launches.  RELPOSE_TUNE_DECONV_STRIP: 0 = that kernel,
-    // 1 = conv_igemm_kernel (the arms differ in the kernel only: same split, same partial sums, same reduce pass, same bits).
-    // The split rule above is not touched: a layer it leaves whole (deconv4 in the three-piece bf16 modes) stays on conv_igemm_kernel --
-    // run as two slices on this kernel it is 160 us faster per forward (profiles/deconv_strip_layers.txt), but its sums are then added
-    // in another order than before, and the poses bench.py dumps for its random-weight network moved with them.
+    // does not tile into patches (deconv4: 28 x 28, deconv5: 14 x 14).  RELPOSE_TUNE_DECONV_STRIP: 0 = that kernel, 1 = conv_igemm_kernel
+    // (the arms differ in the kernel only: same split, same partial sums and reduce pass or same BatchNorm records, same bits).
+    // The split rule above is not touched.  A layer it leaves whole (deconv4 in the three-piece bf16 modes, 1568 tiles against the 1500
+    // wanted) runs the kernel's direct-store epilogue: the rows go straight to their output pixels and the fused BatchNorm records
+    // (stat_part, stat_bm = 128, bn_finalize_fused_kernel) are added in conv_igemm_kernel<2, 2, 2, 2>'s order, so there is no reduce
+    // pass and every bit stays (profiles/deconv_strip_direct_layers.txt).  Only the three-piece instantiations carry that epilogue (the
+    // other modes split deconv4).  deconv6 (7 x 7: a tile spans three BatchNorm groups) stays on conv_igemm_kernel: DESIGN.md.
     const int ds_sel = g_rp_tune[RELPOSE_TUNE_DECONV_STRIP];
-    bool dstrip = ksplit > 1 && !dtile && s2_cfg < 0 && !force_ksplit && cfg == 0 && net->prec != 1 && count % 4 == 0 && cp % 128 == 0;
+    bool dstrip = (ksplit > 1 || net->prec >= RELPOSE_PREC_BF16X9) && !dtile && s2_cfg < 0 && !force_ksplit && cfg == 0 && net->prec != 1 && count % 4 == 0 && cp % 128 == 0;
     for (int i = first; i < first + count && dstrip; ++i) {
         const ConvDesc& d = plan->descs[i];
         const ConvDesc& d0 = plan->descs[first + ((i - first) & ~3)];
-        dstrip = d.osy == 2 && d.osx == 2 && d.sy == 1 && d.sx == 1 && d.ntaps == 4 && d.Hp == d.Hin && d.Wp == d.Win && d.Hin * d.Win >= 128 && !d.bias &&
+        dstrip = d.osy == 2 && d.osx == 2 && d.sy == 1 && d.sx == 1 && d.ntaps == 4 && d.Hp == d.Hin && d.Wp == d.Win && d.Hin * d.Win >= 128 && !d.bias && !d.tanh_out &&
                  d.src[0].sstride != 0 && (d.nsrc == 1 || d.src[1].sstride != 0) && d.nsrc == d0.nsrc && d.src[0].x == d0.src[0].x &&
                  (d.nsrc == 1 || d.src[1].x == d0.src[1].x) && d.Cin == d0.Cin && d.y == d0.y && d.ychoff == d0.ychoff && d.M == plan->descs[first].M &&
                  // taps t = 2 ty + tx at offsets {-1, 0} or {0, +1} per axis: one pad row and one pad column per image
@@ -3180,6 +3269,7 @@ void Builder::end_group() {
         Op o; o.type = OP_CONV_STRIP; o.first = first; o.count = count; o.cfg = 1; o.split = net->prec; o.mt_max = mt;
         o.grid = dim3((unsigned)(((mt + 7) / 8) * 8 * 4), (cp / 128) * ksplit, count / 4);
         plan->ops.push_back(o);
+        if (ksplit == 1) return;                 // direct stores and fused BatchNorm records: nothing to reduce
         Op r; r.type = OP_REDUCE; r.first = first; r.count = count; r.cfg = 0; r.grid = dim3(256, 1, count);
         plan->ops.push_back(r);
         pend_reduce = (int)plan->ops.size() - 1;
@@ -3988,6 +4078,24 @@ int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n, int32_t flags, int32_t
     }
     *macs_out = macs;
     return 0;
+}
+
+// Which kernel the plain plan of n images runs `layer` on under the current precision and tuning knobs: 1 = deconv_strip_kernel as a
+// split-K launch, 2 = deconv_strip_kernel unsplit (direct stores, fused BatchNorm records), 0 = any other kernel, < 0 = error (unknown
+// layer included).  Host-only (a dry-run plan build), for tests that compare kernel arms.
+int relpose_scnet_layer_kernel(RelposeSCNet* net, const char* layer, int32_t n) {
+    if (!net || !net->finalized || !layer || n <= 0 || (n & 1)) return RELPOSE_EINVAL;
+    Plan dry;
+    Builder B; B.net = net; B.n = n; B.G = n / 2; B.act = nullptr; B.ss = nullptr; B.splitk = nullptr; B.statp = nullptr; B.plan = &dry;
+    B.probe_layer = layer;
+    build_plan(net, n, B);
+    if (B.rc) return B.rc;
+    if (B.probe_desc < 0) return RELPOSE_EINVAL;
+    for (const Op& op : dry.ops)
+        if ((op.type == OP_CONV || op.type == OP_CONV_S2 || op.type == OP_CONV_STRIP || op.type == OP_DECONV_TILE) && B.probe_desc >= op.first &&
+            B.probe_desc < op.first + op.count)
+            return (op.type == OP_CONV_STRIP && op.cfg == 1) ? (dry.descs[B.probe_desc].ksplit == 1 ? 2 : 1) : 0;
+    return RELPOSE_EINVAL;
 }
 
 int64_t relpose_scnet_read_tap(RelposeSCNet* net, const char* name, float* out, void* workspace, void* stream) {

@@ -244,6 +244,18 @@ class SCNet(torch.nn.Module):
         _lib.check(_lib.lib().relpose_scnet_plan_macs(self._h, int(n), int(flags), 1 if self_cached else 0, C.byref(v)), "relpose_scnet_plan_macs")
         return v.value
 
+    def layer_kernel(self, layer, n):
+        """Kernel the plain plan of n images runs ``layer`` on under the current precision and tuning knobs (relpose_scnet_layer_kernel;
+        host-only): 1 = deconv_strip_kernel split-K, 2 = deconv_strip_kernel unsplit (direct stores), 0 = another kernel."""
+        r = _lib.lib().relpose_scnet_layer_kernel(self._h, layer.encode(), int(n))
+        if r < 0:
+            raise KeyError(layer)
+        return r
+
+    def layer_on_strip_kernel(self, layer, n):
+        """True if ``layer`` runs on deconv_strip_kernel (either launch form)."""
+        return self.layer_kernel(layer, n) in (1, 2)
+
     def read_tap(self, name):
         """Raw (pre-BatchNorm) NHWC activations of buffer ``name`` from the last forward: [n,H,H,C]."""
         import torch
