@@ -828,7 +828,7 @@ int relpose_scnet_forward(RelposeSCNet* net, const float* x, float* out, int32_t
  *                         sent with every call: the self-stream cache is used only when the previous forward on the pointer carried the
  *                         same generation -- a workspace re-created at a recycled address is never mistaken for the old one, whichever call
  *                         touches it first (RELPOSE_FWD_NEW_WORKSPACE needs the first call to carry the flag).  0 = not tracked.
- *   reserved1             must be NULL (the experiments build -- RP_EXPERIMENTS -- reads a third stream here, see below).
+ *   reserved1             must be NULL (a non-NULL value, like an unknown flag bit, returns RELPOSE_EINVAL before anything is enqueued).
  * Error behaviour: a call that returns != 0 leaves no self-stream record on the workspace (the next forward recomputes everything); a
  * self-cached plan that cannot be built falls back to the full forward (same output) instead of failing. */
 enum { RELPOSE_FWD_ZERO_WARP = 1, RELPOSE_FWD_POSE_OUTPUTS = 2, RELPOSE_FWD_NEW_WORKSPACE = 4 };
@@ -847,16 +847,6 @@ typedef struct RelposeForwardArgs {
     void* reserved1;
 } RelposeForwardArgs;
 int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args);
-
-#ifdef RP_EXPERIMENTS
-/* Experiments build only (tools/build_variant.py xp -DRP_EXPERIMENTS): scheduling variants of the serving loop that were measured in round 5
- * and LOST (profiles/r05_loop_experiments.txt); they are not part of the product ABI.
- * RELPOSE_FWD_PART_FRONT / _BACK: one forward enqueued by two calls cut behind the bottleneck chain (conv4's split-K reduction .. deconv6),
- * the chain on the stream in RelposeForwardArgs::reserved1.  relpose_stream_create_cu_limited: a HIP stream confined to the first n_cus compute units. */
-enum { RELPOSE_FWD_PART_FRONT = 8, RELPOSE_FWD_PART_BACK = 16 };
-int relpose_stream_create_cu_limited(void** stream_out, int32_t n_cus);
-int relpose_stream_destroy(void* stream);
-#endif
 
 /* Multiply-accumulates one forward of a plan family executes (host-only, no device access): flags as above, self_cached != 0 = the plan
  * a forward takes when it finds its self_tag on the workspace.  The full forward (flags 0, self_cached 0) counts every member of

@@ -382,20 +382,17 @@ __device__ __forceinline__ void corr_geom(const FitCtx& f, int c, double* sp, do
 // (rpmodule.py:273), where round 1 ran a capped power iteration.  Rounds 2..5 start from the previous round's
 // eigenvector.  A pair that is still not converged after RP_LZ_MAXPROD products gets RELPOSE_NOT_CONVERGED.
 // All reductions have a fixed order: results are bitwise reproducible and independent of the batch.
-#define RP_FIT1_THREADS 1024      // (the rounds 2-5 size of the large kernel: experiments build only since round 6)
 #define RP_LZ_M 24              // Lanczos steps per cycle (basis size)
 #define RP_LZ_CHECK 8           // convergence test every 8 steps
 #define RP_LZ_MAXPROD 192       // products per eigen-solve before giving up
 #define RP_LZ_TOL 1e-13
-#ifndef RP_TRI_ROUNDS
 #define RP_TRI_ROUNDS 4         // 64-way multisection rounds of the tridiagonal eigenvalue (6 bits each) before the Newton polish (>= 9: no polish)
-#endif
 #define RP_FIT1_MAXC 4500       // LDS: 3 vectors of C doubles + 2 x (C + 1) ints
 #define RP_FIT1_MAXC_HU 1024    // ... + the {h, u} pairs of the products (16 bytes per correspondence more): the 512-thread kernel's sizes.  (Measured at
                                 // Cmax = 2000 / 1024 threads: the pairs take the LDS of the basis vectors and buy nothing there: 5.63 -> 5.69 ms.)
 
 struct Fit1 {                   // LDS layout + per-pair pointers of the single-workgroup fit
-    long long* prof;            // optional [16] cycle counters of block 0 (RELPOSE_FIT_PROF=1, experiments build)
+    long long* prof;            // optional [16] cycle counters of block 0; the library passes null (the stamps stay: removing them changes this kernel's registers)
     double* vec;                // [C] current Lanczos vector / eigenvector (gather source of the products)
     double* hh;                 // [C] h = relu(50 - r)
     double* yy;                 // [C] product output
@@ -456,14 +453,11 @@ __device__ __forceinline__ void rp_drain_stores() { asm volatile("s_waitcnt vmcn
 // Formal side of the protocol (HSA memory model): every flag store / read-modify-write that publishes data is preceded by an agent-scope
 // RELEASE fence, every flag observation that licenses reading such data is followed by an agent-scope ACQUIRE fence (fences rather than
 // ordered atomics: the polls stay relaxed, one invalidate per observation instead of one per poll).  The write-through payload and
-// vmcnt(0) drains above are what makes it work on gfx950; the fences are what makes it a data-race-free program.  RP_FIT_FENCES=0 builds
-// without them (A/B, matcher alone at B=32, same box: leader + 3 helpers 2.87 -> 3.00-3.07 ms at N=200, 4.81 -> 4.96 at N=400; leader + 7: 3.14 ->
+// vmcnt(0) drains above are what makes it work on gfx950; the fences are what makes it a data-race-free program.  A build
+// without them measured (A/B, matcher alone at B=32, same box: leader + 3 helpers 2.87 -> 3.00-3.07 ms at N=200, 4.81 -> 4.96 at N=400; leader + 7: 3.14 ->
 // 3.37-3.44 and 4.50 -> 4.83; one workgroup per pair -- the throughput configurations -- unchanged: no flag is touched).
-#ifndef RP_FIT_FENCES
-#define RP_FIT_FENCES 1
-#endif
-__device__ __forceinline__ void rp_release_agent() { if (RP_FIT_FENCES) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); }
-__device__ __forceinline__ void rp_acquire_agent() { if (RP_FIT_FENCES) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
+__device__ __forceinline__ void rp_release_agent() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); }
+__device__ __forceinline__ void rp_acquire_agent() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
 // (chunk geometry of the distributed products: rp_fit_chunk_size / _count / _begin in rp_math.h, CPU-tested)
 
 // One pass over the pair's edges: thread <-> segment (<= 32 edges of one row, read with stride 64 so that a wave's loads
@@ -1156,9 +1150,7 @@ __device__ __forceinline__ void write_pose_lds(double* out, const double* Rt) {
     }
 }
 
-#ifndef RP_FIT_EPT
 #define RP_FIT_EPT(T_) ((T_) == 512 ? 1 : 0)
-#endif
 // LAYOUT 0: everything in LDS incl. the {h, u} pairs of the products (Cmax <= RP_FIT1_MAXC_HU); 2: the same without the pairs (up to RP_FIT1_MAXC: they
 // would not fit); 1 = GVEC: the three per-correspondence vectors + row / segment pointers in global memory
 template <int THREADS, int LAYOUT>
@@ -1174,12 +1166,8 @@ __global__ __launch_bounds__(THREADS) void fit_pair_kernel(RelposeKeypoints kp, 
     __shared__ double Rt[12];
     __shared__ int st_s;
     __shared__ unsigned cl_s[4];        // helper-workgroup protocol: leader [0] products / [1] h versions published; helper [0] / [1] the control word as polled (high / low half); [2] claimed chunk; leader [3] helpers given up on (a claimed chunk did not arrive in time)
-#ifndef RP_SEG_GQ
 #define RP_SEG_GQ(T_) ((T_) == 512 ? 4 : 2)      // measured (matcher alone, B=32): N=200 3.63 ms with per-edge gathers, 3.48 / 3.45 with 8 / 4 together; N=400 6.47, 6.63 / 6.41 / 6.34 with 8 / 4 / 2
-#endif
-#ifndef RP_SEG_NB
 #define RP_SEG_NB(T_) 2
-#endif
     constexpr int DEPTH = RP_SEG_NB(THREADS) | (RP_SEG_GQ(THREADS) << 4);      // seg_body's RP_SEG_CFG (depth 4 = the whole segment in flight: measured 13 % slower at 512 threads, spills at 1024)
     const int b = blockIdx.y, tid = threadIdx.x;
     const int G = gridDim.x;            // workgroups per scan pair: 1 leader + G - 1 helpers for the matrix-vector products
@@ -1340,9 +1328,7 @@ __global__ __launch_bounds__(THREADS) void fit_pair_kernel(RelposeKeypoints kp, 
             __syncthreads();
             if (G > 1) fit_publish_h(f);
             int conv = 1;
-#ifndef RP_FIT_VB
 #define RP_FIT_VB(T_) ((T_) == 512 ? 16 : 8)
-#endif
             const int np = lanczos_top<DEPTH, RP_FIT_VB(THREADS), HUL>(f, (!sm && round > 0) ? kc.mu : 0.0, &conv, &lrate);       // rounds > 0: warm start from f.vec
             all_converged &= conv;
             if (eig_iters_out && tid == 0) eig_iters_out[b * 5 + round] = np;
@@ -1389,13 +1375,11 @@ static int fit_meta_cap(int32_t Cmax, int32_t seg_cap, bool in_lds) {
     return want < 0 ? 0 : (int)want;
 }
 // Lanczos basis vectors kept in LDS behind that (round 6): whatever the CU's 160 KB still hold, a multiple of 4, at most the whole basis.
-// N = 200 (Cmax = 1000): 12 of a cycle's <= 24 vectors; N = 400 (Cmax = 2000): 4.  RELPOSE_FIT_BASIS_LDS=0 (experiments build) = the round-5 layout.
+// N = 200 (Cmax = 1000): 12 of a cycle's <= 24 vectors; N = 400 (Cmax = 2000): 4.  (None in LDS = the round-5 layout.)
 static int fit_basis_lds(int32_t Cmax, int meta_cap, bool in_lds) {
     if (!in_lds) return 0;
-    static const int cap_env = RP_ENV("RELPOSE_FIT_BASIS_LDS") ? atoi(RP_ENV("RELPOSE_FIT_BASIS_LDS")) : RP_LZ_M;
     const long long room = 160 * 1024 - 2048 - (long long)fit_lds_bytes(Cmax, true) - (long long)meta_cap * 12;
     long long k = room / ((long long)Cmax * 8);
-    if (k > cap_env) k = cap_env;
     if (k > RP_LZ_M) k = RP_LZ_M;
     k &= ~3ll;
     return k < 0 ? 0 : (int)k;
@@ -1465,35 +1449,6 @@ void relpose_default_params(RelposeParams* p) {
 }
 
 const char* relpose_version(void) { return "relpose-hip 0.1 (gfx950)"; }
-
-#ifdef RP_EXPERIMENTS
-int relpose_stream_create_cu_limited(void** stream_out, int32_t n_cus) {
-    if (!stream_out) return RELPOSE_EINVAL;
-    int dev = 0, ncu = 0;
-    RP_HIP(hipGetDevice(&dev));
-    RP_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    hipStream_t s = nullptr;
-    if (n_cus <= 0 || n_cus >= ncu) {
-        RP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    } else {
-        uint32_t mask[32];
-        const int words = std::min(32, (ncu + 31) / 32);
-        for (int w = 0; w < words; ++w) {
-            const int lo = 32 * w;
-            mask[w] = n_cus >= lo + 32 ? 0xffffffffu : (n_cus > lo ? ((1u << (n_cus - lo)) - 1u) : 0u);
-        }
-        RP_HIP(hipExtStreamCreateWithCUMask(&s, (uint32_t)words, mask));
-    }
-    *stream_out = (void*)s;
-    return 0;
-}
-
-int relpose_stream_destroy(void* stream) {
-    if (!stream) return RELPOSE_EINVAL;
-    RP_HIP(hipStreamDestroy((hipStream_t)stream));
-    return 0;
-}
-#endif
 
 size_t relpose_match_workspace_bytes(int32_t B, int32_t ns_max, int32_t nt_max, int32_t topK, int64_t max_edges) {
     if (nt_max > RELPOSE_MAX_TARGETS) return 0;
@@ -1574,21 +1529,15 @@ int relpose_match_pairs_ex(const RelposeMatchArgs* args) {
         const int basis_lds = fit_basis_lds(L.Cmax, meta_cap, in_lds);
         const size_t lds = fit_lds_bytes(L.Cmax, in_lds) + (size_t)meta_cap * 12 + (size_t)basis_lds * L.Cmax * 8;
         double* gvec = in_lds ? nullptr : (double*)(ws + L.gvec);
-        static long long* prof = nullptr;
-        if (RP_ENV("RELPOSE_FIT_PROF")) {
-            if (!prof) RP_HIP(hipMalloc((void**)&prof, 128));
-            RP_HIP(hipMemsetAsync(prof, 0, 128, s));
-        }
         // (multisection rounds | product budget << 8); RELPOSE_TUNE_FIT_MAX_PRODUCTS is a test hook: a tiny budget forces RELPOSE_NOT_CONVERGED
-        const int tri_rounds = (RP_ENV("RELPOSE_TRI_ROUNDS") ? atoi(RP_ENV("RELPOSE_TRI_ROUNDS")) : RP_TRI_ROUNDS) |
+        const int tri_rounds = RP_TRI_ROUNDS |
                                ((g_rp_tune[RELPOSE_TUNE_FIT_MAX_PRODUCTS] > 0 ? g_rp_tune[RELPOSE_TUNE_FIT_MAX_PRODUCTS] : RP_LZ_MAXPROD) << 8) |
                                ((g_rp_tune[RELPOSE_TUNE_FIT_FIXED_CHECKS] != 0 ? 1 : 0) << 24);
         // workgroup size: 512 threads (no register spills: IRLS twice as fast) while every thread still owns at most two correspondences; beyond,
         // 768 in the LDS layout (round 6: three waves per SIMD and a 170-register budget -- measured at N = 400, B = 32, same box: 640 threads 5.56 ms,
         // 768 5.38, 896 5.76, 1024 5.66: the edge passes are no slower than with 16 waves and the IRLS spills less; at N = 200: 384 threads 3.12,
-        // 512 2.82, 640 2.97, 768 2.98), in the global layout too (N = 400 forced into it: 12.83 vs 13.15 ms at 1024).  RELPOSE_FIT_THREADS = 1024
-        // brings the rounds 2-5 kernel back (experiments build).
-        const int fit_threads = RP_ENV("RELPOSE_FIT_THREADS") ? atoi(RP_ENV("RELPOSE_FIT_THREADS")) : (L.Cmax <= 1024 ? 512 : 768);
+        // 512 2.82, 640 2.97, 768 2.98), in the global layout too (N = 400 forced into it: 12.83 vs 13.15 ms at 1024).
+        const int fit_threads = L.Cmax <= 1024 ? 512 : 768;
         // helper workgroups per pair for the matrix-vector products (see FitCtl): a LATENCY tool.  Alone on the chip the matcher of 32
         // N = 400 pairs drops from 7.7 to 5.1 ms with 7 helpers per pair, but helpers sit on a CU each for the whole fit, mostly
         // polling, and inside the pipeline they take those CUs from the SCNet kernels of the other slot: configs[2] 462 -> 400 pairs/s,
@@ -1607,24 +1556,15 @@ int relpose_match_pairs_ex(const RelposeMatchArgs* args) {
         {                                                                                                                              \
             RP_HIP(hipFuncSetAttribute((const void*)fit_pair_kernel<T_, G_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
             hipLaunchKernelGGL((fit_pair_kernel<T_, G_>), dim3(G, kp->B), dim3(T_), lds, s, *kp, g, kc, p->topK, m, (double*)(ws + L.lz), gvec,  \
-                               status, pose, trace, dbg ? dbg->counts : nullptr, eig_iters, prof, tri_rounds, (FitCtl*)(ws + L.ctl),      \
+                               status, pose, trace, dbg ? dbg->counts : nullptr, eig_iters, (long long*)nullptr, tri_rounds, (FitCtl*)(ws + L.ctl),      \
                                (double*)(ws + L.xu), meta_cap, basis_lds);                                                              \
         }
-        // (512 threads <=> Cmax <= 1024 <=> the {h, u} pairs when in LDS: layout 0; the 1024-thread kernel's LDS layout is 2, without them)
+        // (512 threads <=> Cmax <= 1024 <=> the {h, u} pairs when in LDS: layout 0; the 768-thread kernel's LDS layout is 2, without them)
         if (fit_threads == 512 && (fit_hu(L.Cmax, in_lds) || !in_lds)) { if (in_lds) RP_FIT_LAUNCH(512, 0) else RP_FIT_LAUNCH(512, 1) }
-#ifdef RP_EXPERIMENTS
-        else if (fit_threads == 1024) { if (in_lds) RP_FIT_LAUNCH(1024, 2) else RP_FIT_LAUNCH(1024, 1) }
-#endif
         else if (!in_lds) RP_FIT_LAUNCH(768, 1)
         else RP_FIT_LAUNCH(768, 2)
 #undef RP_FIT_LAUNCH
         RP_CHECK_LAUNCH();
-        if (prof) {       // experiments build only: synchronises
-            long long h[16];
-            RP_HIP(hipStreamSynchronize(s));
-            RP_HIP(hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[fit prof, pair 0, cycles] products %lld (%lld calls) reorth+norm %lld tridiag %lld irls %lld finish %lld setup %lld | with helpers: publish %lld own chunks %lld wait %lld row sums %lld | edge passes of one workgroup: thread 0's segments %lld barrier %lld row sums %lld | tridiagonal: multisection %lld newton %lld (= 'wait' column without helpers) inverse iteration %lld\n", h[0], h[6], h[1], h[2], h[4], h[5], h[7], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[3], h[10], h[15]);
-        }
     }
     if (dbg && dbg->corres_j)
         RP_HIP(hipMemcpyAsync(dbg->corres_j, cj, (size_t)kp->B * kp->ns_max * p->topK * 4, hipMemcpyDeviceToDevice, s));

@@ -6,17 +6,21 @@
 //    companion per-(group,channel) {scale,shift} table: float64 statistics written by the producing
 //    kernel's epilogue + a fixed-order finalize (BatchNorm uses batch statistics over each group of
 //    2 images, mymodel.py:19,32);
-//  * one implicit-GEMM kernel for every conv / transposed conv: M = output pixels, N = Cout,
+//  * the general conv / transposed conv is one implicit-GEMM kernel (conv_igemm_kernel): M = output pixels, N = Cout,
 //    K = taps x Cin, k-tiles of 32.  The A-tile loader gathers the im2col slice from up to two NHWC
 //    sources (skip concatenations are never materialised), applies scale/shift + LeakyReLU(0.1)
 //    on the fly and zero-pads; B = weights pre-packed [Cout][K].  Tiles are staged through LDS
 //    (row stride 36 floats: conflict-free ds_read_b128) and contracted with
-//    v_mfma_f32_32x32x2_f32 (exact fp32, 64 lanes) -- or, opt-in, with three bf16 MFMA products per
-//    fp32 product (relpose_scnet_set_precision);
+//    v_mfma_f32_32x32x2_f32 (exact fp32, 64 lanes) -- or with 16-bit MFMA products of split operands
+//    (relpose_scnet_set_precision: bf16x3 / f16x3 / f16 / bf16x9 / bf16x6).  The large layers run on tile kernels that stage each
+//    input pixel once for all taps: deconv_tile_kernel (deconv2, deconv3), conv_s2_tile_kernel (conv2, conv3), conv_s2_strip_kernel
+//    (conv4, conv5) and deconv_strip_kernel (deconv4, deconv5); Builder::end_group chooses;
 //  * stride-2 transposed convs are decomposed into their sub-pixel phases (4 members of a 2x2-tap
 //    conv, launched phase-interleaved so one XCD's L2 serves all four) so no multiply-by-zero work
 //    is issued; shared-weight encoder streams (self / warped view) are channel blocks of one
-//    concatenated buffer; conv1 (K = 18/36) and the five 1x1 heads have their own direct kernels;
+//    concatenated buffer; conv1 (K = 18/36, conv1_mfma_kernel) and the five 1x1 heads (heads_kernel) have kernels of their own;
+//  * every kernel and every plan rule here is the one the product runs: the variants that lost their A/Bs (profiles/) are
+//    in the history, not behind switches;
 //  * bilinear resize kernels (align_corners=False) in and out.
 #include "common.h"
 #include "matcher_internal.h"      // g_rp_tune
@@ -30,11 +34,6 @@
 #include <type_traits>
 #include <stdlib.h>
 #include <stddef.h>
-
-#ifndef RP_EXPERIMENTS
-// (the two-part forward exists in the experiments build only, include/relpose.h; the product build rejects these flag bits)
-enum { RELPOSE_FWD_PART_FRONT = 8, RELPOSE_FWD_PART_BACK = 16 };
-#endif
 
 namespace {
 
@@ -53,45 +52,12 @@ template <> struct SplitT<3> { typedef f16x8 v8; typedef f16x4 v4; };     // pla
 // (the two larger ones <= 2^-24 |a b| each: together at most 2^-23 |a b|, rms 2^-27.4 -- the size of one fp32 rounding, of which the accumulation that follows makes one per product).
 typedef float rp_f4v __attribute__((ext_vector_type(4)));
 
-#ifndef RP_ABLATE
-#define RP_ABLATE 0
-#endif
-#ifndef RP_C1_ABLATE
-#define RP_C1_ABLATE 0
-#endif
-#ifndef RP_BK
-#define RP_BK 32
-#endif
-#ifndef RP_AGPR
-#define RP_AGPR 0               // 1 = fp32 MFMA accumulators in AccVGPRs through inline asm (experiment)
-#endif
-#ifndef RP_TILE_ABLATE
-#define RP_TILE_ABLATE 0
-#endif
-#ifndef RP_TILE_TIMING
-#define RP_TILE_TIMING 0
-#endif
-#if RP_TILE_TIMING
-__device__ unsigned long long g_tile_timing[8];
-extern "C" int relpose_debug_tile_timing(unsigned long long* out8_host, int reset) {
-    if (out8_host && hipMemcpyFromSymbol(out8_host, HIP_SYMBOL(g_tile_timing), 64) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_tile_timing), z, 64) != hipSuccess) return -1; }
-    return 0;
-}
-#endif
-#ifndef RP_STAGGER
-#define RP_STAGGER 0            // 0 = off; n = workgroups (blockIdx.x / n) % 3 get a start offset (see the k-loop prologue)
-#endif
-#ifndef RP_STAGGER_SLEEP
-#define RP_STAGGER_SLEEP 64     // s_sleep units of 64 cycles
-#endif
-constexpr int BK = RP_BK;       // K-tile (floats): 16 (double-buffered LDS) or 32 (whole 128-B lines per row, single LDS buffer)
-constexpr int LDK = BK + 4;     // LDS row stride in floats (80 / 144 B: 16-B aligned, conflict-free b128 reads)
+constexpr int BK = 32;          // K-tile (floats): whole 128-B lines per row, single LDS buffer
+constexpr int LDK = BK + 4;     // LDS row stride in floats (144 B: 16-B aligned, conflict-free b128 reads)
 constexpr int KQ = BK / 4;      // float4 slots per tile row
 constexpr int LDK3 = 52;        // LDS row stride (floats) of the three-piece bf16 rows [32 hi | 32 mid | 32 lo | pad]: 208 B, an odd multiple of 16 B
 template <int SPLIT> struct RowLd { static constexpr int v = SPLIT >= 4 ? LDK3 : LDK; };
 constexpr bool rp_split3(int split) { return split >= 4; }
-constexpr int NBUF = (BK == 16) ? 2 : 1;
 constexpr float LRELU = 0.1f;
 constexpr double BN_EPS = 1e-5;
 constexpr int RS = 224;         // internal resolution (mymodel.py:261)
@@ -231,8 +197,8 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
     constexpr int A_IT = BM / RPI;                      // float4 slots per thread for the A tile
     constexpr int B_IT = (BN + RPI - 1) / RPI;
     constexpr int SS_CAP = (WN == 2) ? 2048 : 512;      // float2 entries of the LDS scale/shift table (16 / 4 KB: still 3 blocks per CU)
-    __shared__ __attribute__((aligned(16))) float As[NBUF][BM * LD];
-    __shared__ __attribute__((aligned(16))) float Bs[NBUF][BN * LD];
+    __shared__ __attribute__((aligned(16))) float As[BM * LD];
+    __shared__ __attribute__((aligned(16))) float Bs[BN * LD];
     __shared__ __attribute__((aligned(16))) float sstab[SSLDS ? 2 * SS_CAP : 8];   // per 4 channels: 4 scales, then 4 shifts
     __shared__ __attribute__((aligned(16))) int rowpix[BM];
     __shared__ signed char rowslot[BM];        // BatchNorm group of the row relative to the tile's first group
@@ -249,7 +215,7 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
     // of the taps that fall inside the image (everything else is zero padding) packed with the BatchNorm
     // group, the output pixel and the group slot.  The loader table lives in the (not yet used) A buffer.
     const int kq = tid % KQ, lrow = tid / KQ;
-    int* rtab = reinterpret_cast<int*>(&As[0][0]);      // [BM][2] {base, mask | grp << 16}
+    int* rtab = reinterpret_cast<int*>(&As[0]);      // [BM][2] {base, mask | grp << 16}
     for (int row_ = tid; row_ < BM; row_ += NT) {
         const int m = m0 + row_;
         int pix = -1, base = 0, mg = 0, slot = -1;
@@ -290,16 +256,6 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
         for (int j = 0; j < NI; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#if RP_STAGGER
-    // Phase-stagger the workgroups that share a CU (experiment): identical blocks launched together run their k loops in
-    // lockstep, so their MFMA-free phases (transform + LDS store + barriers) coincide on every SIMD and the matrix pipe
-    // idles; a one-time offset of 1/3 and 2/3 of a k-tile period de-phases the three resident blocks.
-    {
-        const int ph = (blockIdx.x / RP_STAGGER) % 3;
-        if (ph >= 1) __builtin_amdgcn_s_sleep(RP_STAGGER_SLEEP);
-        if (ph >= 2) __builtin_amdgcn_s_sleep(RP_STAGGER_SLEEP);
-    }
-#endif
 
     // B rows of this thread (BN < 64: rows are clamped, the extra threads re-load row BN-1 and never store)
     const float* b_src[B_IT];
@@ -347,7 +303,7 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
         _Pragma("unroll") for (int it = 0; it < A_IT; ++it) {                                                     \
             const bool ok_ = UNI ? ((r_mg[it >> 1] >> (tap + 16 * (it & 1))) & 1) : ((r_mg[UNI ? 0 : it] >> tap) & 1);                                                             \
             okm |= ok_ ? (1 << it) : 0;                                                                           \
-            const int pix_ = (RP_ABLATE == 6) ? (it * 8) : (RP_ABLATE == 7) ? ((r_base[it] + td_) & 0xfff) : ok_ ? r_base[it] + td_ : 0;   \
+            const int pix_ = ok_ ? r_base[it] + td_ : 0;                                                          \
             ra[it] = rp_ldg4(sx_ + (size_t)pix_ * scs_ + cc_);                                                    \
             if (!SSLDS && !UNI) {                                                                                 \
                 const float2* sss_ = s1_ ? d.src[1].ss : d.src[0].ss;                                             \
@@ -371,7 +327,7 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
         else { c0 += BK; if (c0 == d.Cin) { c0 = 0; ++tap; } }                                                    \
     }
 
-#define RP_STORE_TILE(BUF)                                                                                        \
+#define RP_STORE_TILE()                                                                                           \
     {                                                                                                             \
         /* BatchNorm scale/shift + LeakyReLU + zero padding as packed fp32 ops (v_pk_fma / v_pk_mul): u0_ = the   \
            4 scales, u1_ = the 4 shifts of this thread's channels */                                             \
@@ -399,26 +355,26 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
             const rp_v2f mk_ = {okf_, okf_};                                                                      \
             v01 = (rp_v2f){fmaxf(v01.x, t01.x), fmaxf(v01.y, t01.y)} * mk_;                                       \
             v23 = (rp_v2f){fmaxf(v23.x, t23.x), fmaxf(v23.y, t23.y)} * mk_;                                       \
-            if (!SPLIT) *reinterpret_cast<float4*>(&As[BUF][(lrow + it * RPI) * LD + kq * 4]) = make_float4(v01.x, v01.y, v23.x, v23.y); \
+            if (!SPLIT) *reinterpret_cast<float4*>(&As[(lrow + it * RPI) * LD + kq * 4]) = make_float4(v01.x, v01.y, v23.x, v23.y); \
             else {   /* row = [32 x 16-bit hi | 32 x 16-bit lo]: v = hi + lo to 2^-16 (bf16) / ~2^-22 (f16); S3: [hi | mid | lo], exact */ \
                 typedef typename SplitT<SPLIT>::v4 h4_;                                                           \
                 const rp_f4v vf_ = {v01.x, v01.y, v23.x, v23.y};                                                  \
                 const h4_ hi_ = __builtin_convertvector(vf_, h4_);                                                \
                 const rp_f4v r1_ = vf_ - __builtin_convertvector(hi_, rp_f4v);                                    \
                 const h4_ lo_ = __builtin_convertvector(r1_, h4_);                                                \
-                h4_* ar_ = reinterpret_cast<h4_*>(&As[BUF][(lrow + it * RPI) * LD]);                              \
+                h4_* ar_ = reinterpret_cast<h4_*>(&As[(lrow + it * RPI) * LD]);                              \
                 ar_[kq] = hi_;                                                                                    \
                 if (SPLIT != 3) ar_[8 + kq] = lo_;                                                                \
                 if (S3) ar_[16 + kq] = __builtin_convertvector(r1_ - __builtin_convertvector(lo_, rp_f4v), h4_);  \
             }                                                                                                     \
         }                                                                                                         \
         if (BN >= RPI || lrow < BN) {                                                                             \
-            *reinterpret_cast<float4*>(&Bs[BUF][lrow * LD + kq * 4]) = rb[0];                                     \
-            if (S3) *reinterpret_cast<float2*>(&Bs[BUF][lrow * LD + 32 + kq * 2]) = rbl[0];                       \
+            *reinterpret_cast<float4*>(&Bs[lrow * LD + kq * 4]) = rb[0];                                     \
+            if (S3) *reinterpret_cast<float2*>(&Bs[lrow * LD + 32 + kq * 2]) = rbl[0];                       \
         }                                                                                                         \
         _Pragma("unroll") for (int it = 1; it < B_IT; ++it) {                                                     \
-            *reinterpret_cast<float4*>(&Bs[BUF][(lrow + it * RPI) * LD + kq * 4]) = rb[it];                       \
-            if (S3) *reinterpret_cast<float2*>(&Bs[BUF][(lrow + it * RPI) * LD + 32 + kq * 2]) = rbl[S3 ? it : 0]; \
+            *reinterpret_cast<float4*>(&Bs[(lrow + it * RPI) * LD + kq * 4]) = rb[it];                       \
+            if (S3) *reinterpret_cast<float2*>(&Bs[(lrow + it * RPI) * LD + 32 + kq * 2]) = rbl[S3 ? it : 0]; \
         }                                                                                                         \
     }
 
@@ -427,15 +383,12 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
     float4 qu0 = make_float4(0.f, 0.f, 0.f, 0.f), qu1 = qu0;
     RP_ISSUE_LOADS(kt_begin)
     __syncthreads();       // every thread has its rtab rows in registers: the A buffer may be overwritten
-    RP_STORE_TILE(0)
+    RP_STORE_TILE()
     __syncthreads();
     const int arow = (wm * MI * 32 + (lane & 31)) * LD + (lane >> 5) * 4;
     const int brow = (wn * NI * 32 + (lane & 31)) * LD + (lane >> 5) * 4;
     for (int kt = kt_begin; kt < nkt; ++kt) {
-        const int buf = (NBUF == 2) ? ((kt - kt_begin) & 1) : 0;
-#if RP_ABLATE != 2 && RP_ABLATE != 5
         if (kt + 1 < nkt) RP_ISSUE_LOADS(kt + 1)
-#endif
         if constexpr (SPLIT != 0) {
             // split-operand modes: 3 / 1 / 9 / 6 16-bit MFMA terms per product and 16-channel step (rp_split_mma: no two consecutive MFMAs share an accumulator)
             int ar_[MI], br_[NI];
@@ -443,69 +396,28 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
             for (int i = 0; i < MI; ++i) ar_[i] = arow + i * 32 * LD;
 #pragma unroll
             for (int j = 0; j < NI; ++j) br_[j] = brow + j * 32 * LD;
-            rp_split_mma<SPLIT, MI, NI>(acc, &As[buf][0], ar_, &Bs[buf][0], br_);
+            rp_split_mma<SPLIT, MI, NI>(acc, &As[0], ar_, &Bs[0], br_);
         } else
-#if RP_AGPR
-        {   // experiment: accumulators pinned to AccVGPRs (the compiler picks the ArchVGPR form of the MFMA); fragments of step
-            // kc + 1 are read from LDS before the MFMAs of step kc are issued; k-major MFMA order (4 accumulators in rotation)
-            float4 a[2][MI], b[2][NI];
-#pragma unroll
-            for (int i = 0; i < MI; ++i) a[0][i] = *reinterpret_cast<const float4*>(&As[buf][arow + i * 32 * LDK]);
-#pragma unroll
-            for (int j = 0; j < NI; ++j) b[0][j] = *reinterpret_cast<const float4*>(&Bs[buf][brow + j * 32 * LDK]);
-#pragma unroll
-            for (int kc = 0; kc < BK / 8; ++kc) {
-                const int cur = kc & 1, nxt = cur ^ 1;
-                if (kc + 1 < BK / 8) {
-#pragma unroll
-                    for (int i = 0; i < MI; ++i) a[nxt][i] = *reinterpret_cast<const float4*>(&As[buf][arow + i * 32 * LDK + (kc + 1) * 8]);
-#pragma unroll
-                    for (int j = 0; j < NI; ++j) b[nxt][j] = *reinterpret_cast<const float4*>(&Bs[buf][brow + j * 32 * LDK + (kc + 1) * 8]);
-                }
-#define RP_MFMA_A(C_) \
-                _Pragma("unroll") for (int i = 0; i < MI; ++i) _Pragma("unroll") for (int j = 0; j < NI; ++j) \
-                    asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(a[cur][i].C_), "v"(b[cur][j].C_));
-                RP_MFMA_A(x) RP_MFMA_A(y) RP_MFMA_A(z) RP_MFMA_A(w)
-#undef RP_MFMA_A
-            }
-        }
-#else
 #pragma unroll
         for (int kc = 0; kc < BK / 8; ++kc) {
             float4 a[MI], b[NI];
-#if RP_ABLATE == 3 || RP_ABLATE == 5
 #pragma unroll
-            for (int i = 0; i < MI; ++i) a[i] = make_float4(1.f + kt, 2.f, 3.f, 4.f + lane);
+            for (int i = 0; i < MI; ++i) a[i] = *reinterpret_cast<const float4*>(&As[arow + i * 32 * LDK + kc * 8]);
 #pragma unroll
-            for (int j = 0; j < NI; ++j) b[j] = make_float4(0.5f, 0.25f + kt, 0.125f, 1.f);
-#else
-#pragma unroll
-            for (int i = 0; i < MI; ++i) a[i] = *reinterpret_cast<const float4*>(&As[buf][arow + i * 32 * LDK + kc * 8]);
-#pragma unroll
-            for (int j = 0; j < NI; ++j) b[j] = *reinterpret_cast<const float4*>(&Bs[buf][brow + j * 32 * LDK + kc * 8]);
-#endif
+            for (int j = 0; j < NI; ++j) b[j] = *reinterpret_cast<const float4*>(&Bs[brow + j * 32 * LDK + kc * 8]);
 #pragma unroll
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < NI; ++j) {
-#if RP_ABLATE == 1
-                    acc[i][j][0] += a[i].x * b[j].x + a[i].y * b[j].y + a[i].z * b[j].z + a[i].w * b[j].w;
-#else
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
-#endif
                 }
         }
-#endif
-#if RP_ABLATE != 5
-        if (NBUF == 1) __syncthreads();                 // single buffer: every wave is done reading tile kt
-        if (kt + 1 < nkt) RP_STORE_TILE(NBUF == 2 ? (buf ^ 1) : 0)
-#endif
-#if RP_ABLATE != 4 && RP_ABLATE != 5
+        __syncthreads();                                // single buffer: every wave is done reading tile kt
+        if (kt + 1 < nkt) RP_STORE_TILE()
         __syncthreads();
-#endif
     }
 #undef RP_ISSUE_LOADS
 #undef RP_STORE_TILE
@@ -536,7 +448,7 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
         // Fused BatchNorm statistics: float64 sum / sum of squares of this tile's raw outputs per column and
         // per group slot (a tile spans at most two groups here), reduced in a fixed order:
         // lane rows -> lane pair (xor 32) -> the WM waves of a column (LDS, in order) -> one record per tile.
-        double* red = reinterpret_cast<double*>(&As[0][0]);       // main loop is over (it ended with a barrier)
+        double* red = reinterpret_cast<double*>(&As[0]);       // main loop is over (it ended with a barrier)
         double s0[NI], q0s[NI], s1[NI], q1s[NI];
 #pragma unroll
         for (int j = 0; j < NI; ++j) { s0[j] = 0; q0s[j] = 0; s1[j] = 0; q1s[j] = 0; }
@@ -680,9 +592,7 @@ __device__ __forceinline__ void rp_tile_mma(floatx16 (&acc)[MI][NI], const float
 // blockIdx.z = N tile of NI * 32 output columns (Cout 64 as two tiles of 32: three workgroups per CU instead of two).
 // PAIR (TC == 8, 4 waves): the workgroup takes TWO 8 x 8 patches (consecutive in patch order, possibly in the two images of one
 // BatchNorm group) with separate 10 x 10 halo tiles -- 56-wide grids tile into 8 x 8 but not into 8 x 16 (deconv3).
-#ifndef RP_DT_SPLIT_OCC
 #define RP_DT_SPLIT_OCC 2
-#endif
 // (16-bit modes of the paired 8 x 8 variant -- deconv3 -- spill 44 registers at the 168 of 3 workgroups per CU: 2 per CU there, -9 %)
 #define RP_DT_OCC(MI_, NI_, NW_, SP_, PAIR_) ((SP_) >= 4 ? 2 : ((MI_) * (NI_) == 1 ? ((NW_) == 4 ? (((SP_) && (PAIR_)) ? RP_DT_SPLIT_OCC : 3) : 2) : 2))   /* three-piece rows: 68 KB of LDS */
 template <int MI, int NI, int NW, int TC, bool PAIR = false, int SPLIT = 0>
@@ -915,17 +825,6 @@ __global__ __launch_bounds__(NW * 64, RP_DT_OCC(MI, NI, NW, SPLIT, PAIR)) void d
             if (snap_mode == 1 && ch + 1 == nch1) snap_store();     // the skip source is done: the accumulators for the self-cached forwards
         }
     } else {
-#if RP_TILE_TIMING
-        // experiment (tools/build_variant.py tt -DRP_TILE_TIMING=1): s_memtime stamps around the segments of the main loop, summed over the waves of
-        // the launch in g_tile_timing: [0] load issue, [1] MFMAs + fragment reads, [2] first barrier, [3] LDS stores (+ A transform), [4] second barrier,
-        // [5] prologue, [6] whole kernel, [7] waves
-        unsigned long long tt_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const unsigned long long tt_start_ = __builtin_readcyclecounter();
-        unsigned long long tt_prev_ = tt_start_;
-#define RP_TT(i_) { const unsigned long long n_ = __builtin_readcyclecounter(); tt_[i_] += n_ - tt_prev_; tt_prev_ = n_; }
-#else
-#define RP_TT(i_)
-#endif
         if (snap_mode == 2) snap_load();        // the accumulators as the full forward left them after the skip source's chunks
         RP_DT_LOAD_A(c0_of(k_first))
         RP_DT_LOAD_B(0, c0_of(k_first))
@@ -933,7 +832,6 @@ __global__ __launch_bounds__(NW * 64, RP_DT_OCC(MI, NI, NW, SPLIT, PAIR)) void d
         RP_DT_STORE_A(c0_of(k_first))
         RP_DT_STORE_B()
         __syncthreads();
-        RP_TT(5)
         for (int ch = k_first; ch < nchunk; ++ch) {
             const int c0 = c0_of(ch), c0n = c0_of(ch + 1 < nchunk ? ch + 1 : ch);
 #pragma unroll
@@ -942,7 +840,6 @@ __global__ __launch_bounds__(NW * 64, RP_DT_OCC(MI, NI, NW, SPLIT, PAIR)) void d
                 const bool last = (ch + 1 == nchunk);
                 if (p < 3) RP_DT_LOAD_B(p + 1, c0)
                 else if (!last) { RP_DT_LOAD_B(0, c0n) RP_DT_LOAD_A(c0n) }
-                RP_TT(0)
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int aoff = aoffs[p][t];
@@ -953,22 +850,13 @@ __global__ __launch_bounds__(NW * 64, RP_DT_OCC(MI, NI, NW, SPLIT, PAIR)) void d
                     for (int j = 0; j < NI; ++j) br_[j] = brow + (t * NI + j) * 32 * LD;
                     rp_tile_mma<SPLIT, MI, NI>(acc[p], At, ar_, Bt, br_);
                 }
-                RP_TT(1)
                 __syncthreads();                                          // every wave is done with this phase's weights (and, p == 3, the halo tile)
-                RP_TT(2)
                 if (p < 3 || !last) RP_DT_STORE_B()
                 if (p == 3 && !last) RP_DT_STORE_A(c0n)
-                RP_TT(3)
                 __syncthreads();
-                RP_TT(4)
             }
             if (snap_mode == 1 && ch + 1 == nch1) snap_store();         // the skip source is done: the accumulators for the self-cached forwards
         }
-#if RP_TILE_TIMING
-        tt_[6] = __builtin_readcyclecounter() - tt_start_; tt_[7] = 1;
-        if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_tile_timing[i], tt_[i]);
-#endif
-#undef RP_TT
     }
 #undef RP_DT_LOAD_B2
 #undef RP_DT_STORE_B2
@@ -1188,12 +1076,10 @@ __global__ __launch_bounds__(256, SPLIT >= 4 ? 2 : (MI * NI <= 2 ? 4 : 3)) void 
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt) {
             const int sidx = cp * 4 + tt;
-            // (RP_TILE_ABLATE: timing decomposition of this loop, experiments only -- 1 = no MFMAs / fragment reads, 2 = no staging (global loads,
-            // transforms, LDS stores), 3 = no barriers, 4 = weights staged but the A tile never re-staged; results are wrong in every one of them)
-            if (RP_TILE_ABLATE != 2) { if (sidx + 1 < nstep) RP_S2_LOAD_B(sidx + 1) }
-            if (RP_TILE_ABLATE != 2 && RP_TILE_ABLATE != 4) { if (tt == 0 && !lastp) RP_S2_LOAD_A((cp + 1) >> 2, (cp + 1) & 3) }
+            if (sidx + 1 < nstep) RP_S2_LOAD_B(sidx + 1)
+            if (tt == 0 && !lastp) RP_S2_LOAD_A((cp + 1) >> 2, (cp + 1) & 3)
             const int aoff = ((tt >> 1) * HW1 + (tt & 1)) * LD;
-            if (RP_TILE_ABLATE != 1) {
+            {
                 int ar_[MI], br_[NI];
 #pragma unroll
                 for (int i = 0; i < MI; ++i) ar_[i] = arow[i] + aoff;
@@ -1201,10 +1087,10 @@ __global__ __launch_bounds__(256, SPLIT >= 4 ? 2 : (MI * NI <= 2 ? 4 : 3)) void 
                 for (int j = 0; j < NI; ++j) br_[j] = brow + j * 32 * LD;
                 rp_tile_mma<SPLIT, MI, NI>(acc, At, ar_, Bt, br_);
             }
-            if (RP_TILE_ABLATE != 3) __syncthreads();
-            if (RP_TILE_ABLATE != 2) { if (sidx + 1 < nstep) RP_S2_STORE_B() }
-            if (RP_TILE_ABLATE != 2 && RP_TILE_ABLATE != 4) { if (tt == 3 && !lastp) RP_S2_STORE_A((cp + 1) >> 2, (cp + 1) & 3) }
-            if (RP_TILE_ABLATE != 3) __syncthreads();
+            __syncthreads();
+            if (sidx + 1 < nstep) RP_S2_STORE_B()
+            if (tt == 3 && !lastp) RP_S2_STORE_A((cp + 1) >> 2, (cp + 1) & 3)
+            __syncthreads();
         }
         (void)ch; (void)pl;
     }
@@ -1738,134 +1624,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvDesc* __re
     }
 }
 
-// ---- conv1{rgb,n,d} x {self, warped}: direct 3x3 convolution (mymodel.py:151,155,159 / :266-286) ------------
-// Six tiny convs (Cin 4/4/2 -> 32) of the resized 16-channel input.  K is 36 or 18, far too small for an
-// implicit GEMM; one wave handles 64 pixels of one (modality, stream) block so the weights are wave-uniform
-// (scalar loads, SGPR operands) and every lane accumulates its 32 outputs in registers.
+// ---- conv1{rgb,n,d} x {self, warped} on the matrix pipe (mymodel.py:151,155,159 / :266-286) ------------------
+// Six tiny 3x3 convs (Cin 4/4/2 -> 32) of the resized 16-channel input, K = 36 or 18: far too small for the implicit GEMM.
 // w1: [6][9 taps][4 ch][32 out] (zero rows for the 2-channel depth block).
 // BatchNorm statistics of A1 are fused: each pass (256 pixels of ONE image) leaves a float64 {sum, sum of squares}
-// record per output channel in stat[group][pass in group][192][2], consumed by bn_finalize_kernel in pass order.
+// record per output channel in stat[group][pass in group][192][2], consumed by bn_finalize_parts_kernel in pass order.
 constexpr int C1_PASSES_PER_GROUP = 2 * RS * RS / 256;      // 392
-__global__ __launch_bounds__(256, 2) void conv1_direct_kernel(const float* __restrict__ x0, const float* __restrict__ w1,
-                                                            float* __restrict__ a1, double* __restrict__ stat, int n) {
-    const size_t total = (size_t)n * RS * RS;      // multiple of 256 (224*224 = 196*256): a wave's pass never straddles the end
-    __shared__ __attribute__((aligned(16))) float wl[6 * 9 * 4 * 32];  // all six blocks' weights, read as LDS broadcasts
-    __shared__ __attribute__((aligned(16))) float tile[4 * 64 * 36];
-    for (int i = threadIdx.x; i < 6 * 9 * 4 * 32; i += 256) wl[i] = w1[i];
-    __syncthreads();
-    // The six (modality, stream) blocks q = 2*m + s of a pixel run are computed back to back by the SAME wave: the
-    // 16-channel input lines are fetched from HBM once (6 separate sweeps re-read X0 ~18x: 4.2 GB vs 0.2 GB, PMC)
-    // and a pixel's 768-byte output row is completed within one pass.
-    // A wave takes 256 consecutive pixels per pass, lane l the 4 horizontal neighbours base + 4l .. 4l+3 (224 is a
-    // multiple of 4: they share a row).  Per kernel row the lane fetches its 6 input columns ONCE (the 3x3 windows
-    // of the 4 pixels overlap) and only the channel quads this block needs; every weight quad read from LDS (a
-    // broadcast, but still 1 KB of register writes) feeds 4 pixels; the 32 outputs of a pixel are 16 pairs
-    // accumulated with packed FMAs (v_pk_fma_f32: two fp32 FMAs per lane per issue).
-    constexpr int PX = 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* tw = tile + wave * 64 * 36;
-    for (size_t base = ((size_t)blockIdx.x * 4 + wave) * (64 * PX); base < total; base += (size_t)gridDim.x * 4 * (64 * PX)) {
-        const size_t pix = base + lane * PX;             // first of the lane's 4 pixels
-        const int x = (int)(pix % RS), y = (int)((pix / RS) % RS);
-        rp_v2f acc[PX][16];
-        float nx[PX + 2][4];                             // the 4 input channels of the 6 columns of the NEXT (q, ty) step
-        // Software pipeline over the 18 (block q, kernel row ty) steps: the loads of step it+1 are in flight while
-        // step it runs its 768 packed FMAs (two waves per SIMD cannot hide an HBM round trip per step otherwise).
-        // Only the channels the block needs are loaded: {rgb|n}: 3 + mask, depth: 1 + mask (mymodel.py:264-286).
-#define RP_C1_LOAD(IT)                                                                                           \
-        {                                                                                                        \
-            const int q_ = (IT) / 3, ty_ = (IT) - q_ * 3, m_ = q_ >> 1, sft_ = (q_ & 1) * 8;                     \
-            const int iy_ = y + ty_ - 1;                                                                         \
-            const bool oky_ = (iy_ >= 0) & (iy_ < RS);                                                           \
-            _Pragma("unroll") for (int cx = 0; cx < PX + 2; ++cx) {                                              \
-                const int ix_ = x + cx - 1;                                                                      \
-                const bool ok_ = oky_ & (ix_ >= 0) & (ix_ < RS);                                                 \
-                const float* p_ = x0 + (pix + (ok_ ? (ptrdiff_t)(ty_ - 1) * RS + (cx - 1) : 0)) * 16 + sft_;     \
-                if (m_ == 0) { nx[cx][0] = p_[0]; nx[cx][1] = p_[1]; nx[cx][2] = p_[2]; nx[cx][3] = p_[7]; }     \
-                else if (m_ == 1) { nx[cx][0] = p_[3]; nx[cx][1] = p_[4]; nx[cx][2] = p_[5]; nx[cx][3] = p_[7]; } \
-                else { nx[cx][0] = p_[6]; nx[cx][1] = p_[7]; nx[cx][2] = 0.f; nx[cx][3] = 0.f; }                 \
-            }                                                                                                    \
-        }
-        RP_C1_LOAD(0)
-#pragma unroll 1
-        for (int it = 0; it < 18; ++it) {
-            const int q = it / 3, ty = it - q * 3;           // block q = 2*modality + stream
-            const int iy = y + ty - 1;
-            const bool oky = (iy >= 0) & (iy < RS);
-            float in[PX + 2][4];
-#pragma unroll
-            for (int cx = 0; cx < PX + 2; ++cx) {
-                const int ix = x + cx - 1;
-                const bool ok = oky & (ix >= 0) & (ix < RS);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) in[cx][c] = ok ? nx[cx][c] : 0.f;       // zero padding
-            }
-            if (it + 1 < 18) RP_C1_LOAD(it + 1)
-            if (ty == 0) {
-#pragma unroll
-                for (int k = 0; k < PX; ++k)
-#pragma unroll
-                    for (int o = 0; o < 16; ++o) acc[k][o] = (rp_v2f){0.f, 0.f};
-            }
-#pragma unroll
-            for (int tx = 0; tx < 3; ++tx)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    rp_v2f vv[PX];
-#pragma unroll
-                    for (int k = 0; k < PX; ++k) vv[k] = (rp_v2f){in[k + tx][c], in[k + tx][c]};
-                    const float* wrow = &wl[((it * 3 + tx) * 4 + c) * 32];      // [q][ty][tx][c][32 out]
-#pragma unroll
-                    for (int o4 = 0; o4 < 8; ++o4) {
-                        const float4 wv = *reinterpret_cast<const float4*>(wrow + o4 * 4);   // wave-uniform address
-                        const rp_v2f w01 = {wv.x, wv.y}, w23 = {wv.z, wv.w};
-#pragma unroll
-                        for (int k = 0; k < PX; ++k) {
-                            acc[k][o4 * 2 + 0] = vv[k] * w01 + acc[k][o4 * 2 + 0];
-                            acc[k][o4 * 2 + 1] = vv[k] * w23 + acc[k][o4 * 2 + 1];
-                        }
-                    }
-                }
-            if (ty != 2) continue;
-            // block q done.  Transpose through LDS: lane l first holds pixel 4l+k (32 channels); it then writes chunk
-            // (l&7) of the pixels 4*((l>>3)+8j)+k, so every store instruction covers 8 full 128-B lines
-            double ssum = 0.0, ssq = 0.0;                   // channel lane&31, pixel half lane>>5 of every 64-pixel run
-#pragma unroll
-            for (int k = 0; k < PX; ++k) {
-#pragma unroll
-                for (int o = 0; o < 8; ++o)
-                    *reinterpret_cast<float4*>(tw + lane * 36 + o * 4) = make_float4(acc[k][2 * o].x, acc[k][2 * o].y, acc[k][2 * o + 1].x, acc[k][2 * o + 1].y);
-#pragma unroll 8
-                for (int i = 0; i < 32; ++i) {
-                    const double v = (double)tw[((lane >> 5) * 32 + i) * 36 + (lane & 31)];
-                    ssum += v; ssq += v * v;
-                }
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int pl = (lane >> 3) + 8 * jj;
-                    const float4 v = *reinterpret_cast<const float4*>(tw + pl * 36 + (lane & 7) * 4);
-                    *reinterpret_cast<float4*>(a1 + (base + (size_t)pl * PX + k) * 192 + q * 32 + (lane & 7) * 4) = v;
-                }
-            }
-            ssum += rp_shfl_xor_d(ssum, 32); ssq += rp_shfl_xor_d(ssq, 32);
-            if (lane < 32) {
-                const size_t pass = base / (64 * PX);        // = group * C1_PASSES_PER_GROUP + pass in group
-                double* o = stat + (pass * 192 + q * 32 + lane) * 2;
-                o[0] = ssum; o[1] = ssq;
-            }
-        }
-#undef RP_C1_LOAD
-    }
-}
-
-// ---- conv1 on the matrix pipe ---------------------------------------------------------------------------------
-// Same six 3x3 convs as conv1_direct_kernel, as per-block GEMMs M = pixels, N = 32, K = 9 taps x 4 (2 for depth) channels
+// The six convs as per-block GEMMs M = pixels, N = 32, K = 9 taps x 4 (2 for depth) channels
 // on v_mfma_f32_32x32x2_f32.  One workgroup = an 8 x 32 pixel tile of one image: the 10 x 34 halo tile of the 16-channel
 // input is staged in LDS once (pixel stride 17 floats: the A fragments of 32 neighbouring pixels hit 32 different banks), the
 // weights of all six blocks as well; wave w owns tile rows 2w, 2w+1 (two 32-pixel M tiles sharing every B fragment).
 // k = tap * 4 + c4 (depth: tap * 2 + c2): at MFMA step kk lanes 0-31 supply k = 2kk, lanes 32-63 k = 2kk + 1.
 // C layout: lane holds output channel lane & 31 of 16 pixels -> every store instruction writes two full 128-byte lines of
-// A1 and the BatchNorm sums need no transposition (the direct kernel went through LDS for both).  The VALU kernel ran
+// A1 and the BatchNorm sums need no transposition (round 1's direct VALU kernel went through LDS for both).  That kernel ran
 // 34 TFLOP/s on 44 GFLOP (1.08 ms); here the MFMA time is ~0.25 ms and the 2.47 GB of A1 stores are the bound.
 // One {sum, sum of squares} record per tile and channel: stat[group][(img & 1) * 196 + tile][192][2] (C1_PASSES_PER_GROUP).
 constexpr int C1T_PS = 17;                          // LDS pixel stride (floats)
@@ -2109,12 +1880,10 @@ __device__ __forceinline__ void rp_wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// Occupancy: 3 waves per SIMD (<= 168 VGPRs; three 51.75 KB workgroups fill a CU's LDS); -DRP_HEADS_WAVES=2 builds the 2-wave variant (240 VGPRs) for A/B
+// Occupancy: 3 waves per SIMD (<= 168 VGPRs; three 51.75 KB workgroups fill a CU's LDS).  The 2-wave variant (RP_HEADS_WAVES 2, 240 VGPRs) lost its A/B
 // runs: 949 against 901 us per call alone and 38.84 against 38.79 ms per bench step in the loop (parent 39.22; profiles/heads_stream_bench.txt) -- here the
 // lower-register kernel is the better neighbour too, unlike the round-5 experiment above heads_lanepix_kernel.
-#ifndef RP_HEADS_WAVES
 #define RP_HEADS_WAVES 3
-#endif
 template <int S, bool POSE = false>
 __global__ __launch_bounds__(256, RP_HEADS_WAVES) void heads_kernel(const HeadsDesc hd) {
     __shared__ __attribute__((aligned(16))) float wl[HEADS_W];
@@ -2640,14 +2409,11 @@ struct RelposeSCNet {
     float* d_w = nullptr;        // packed weights + biases
     float* d_gb = nullptr;       // gamma/beta per activation buffer [2][C]
     float2* d_ident = nullptr;   // 16 x {1,0}: scale/shift of the raw network input
-    size_t w1_off = 0;           // conv1 direct-kernel weights inside d_w
+    size_t w1_off = 0;           // conv1_mfma_kernel's weights inside d_w
     size_t wh_off = 0, bh_off = 0;   // fused-heads weight image and bias vector inside d_w
     std::map<std::pair<void*, int>, void*> plans;   // (workspace, n) -> Plan* (each with its own device descriptor table)
     struct SelfState { uint64_t tag = 0, gen = 0; int n = 0, H = 0, W = 0; bool pose_only = false; };
     std::map<void*, SelfState> self_state;          // workspace -> whose self-view streams it holds (relpose_scnet_forward4)
-    // workspace -> the forward whose RELPOSE_FWD_PART_FRONT half has been enqueued and whose _BACK half has not
-    struct PendingFront { void* plan = nullptr; SelfState st; const float* x = nullptr; float* out = nullptr; int flags = 0; };
-    std::map<void*, PendingFront> pending;
     std::map<std::string, Layer> layers;
     std::map<std::string, Buf> bufs;
     size_t per_image_floats = 0, ss_float2_per_group = 0;
@@ -2927,10 +2693,6 @@ struct Plan {
     int tail_first = -1;         // first op of the forward's tail (the heads; resize_out follows): relpose_scnet_forward2 moves it to a second stream
     int head_count = 0;          // ops of the forward's head (conv1 + its BatchNorm finalize; resize_in precedes): second stream as well
     hipEvent_t tail_ev = nullptr, head_ev = nullptr;
-    // the bottleneck chain (conv4's split-K reduction .. deconv6's BatchNorm finalize): ops [mid_first, mid_end) may run on a third stream, and a
-    // forward may be enqueued in two calls cut at mid_end (RELPOSE_FWD_PART_FRONT / _BACK)
-    int mid_first = -1, mid_end = -1;
-    hipEvent_t mid_ev0 = nullptr, mid_ev1 = nullptr;
 };
 
 struct Builder {
@@ -2981,8 +2743,7 @@ void Builder::stats(const std::string& b) {
         o.type = OP_STATS; o.first = o.count = 0;
         // a mixed / ineligible producer set: drop the per-tile records again (they would be written for nothing)
         if (pend_first >= 0) for (int i = pend_first; i < pend_first + pend_count; ++i) plan->descs[i].stat_part = nullptr;
-        static const bool no_rs = RP_ENV("RELPOSE_NO_REDUCE_STATS") != nullptr;
-        if (!no_rs && pend_groups == 1 && pend_reduce >= 0) {
+        if (pend_groups == 1 && pend_reduce >= 0) {
             // one split-K producer group: its reduce kernel also leaves the BatchNorm partial sums (chunk count fixed per layer,
             // independent of the batch: results stay bitwise batch-invariant)
             Op& r = plan->ops[pend_reduce];
@@ -3045,10 +2806,7 @@ void Builder::conv(const std::string& layer, Src s0, const Src* s1, int Hin, con
         d.tanh_out = (L.kind == 2 && layer == "deconv1f" && net->use_tanh) ? 1 : 0;
         d.M = d.Nimg * d.Hp * d.Wp; d.K = P.K;
         d.ksplit = 1; d.kt_per = d.K / BK; d.partial = nullptr;
-        {   // K order: tap-inner for the 2x2-tap phases of transposed convs (RELPOSE_TAP_INNER=0 none / 2 every conv: experiments)
-            static const int ti = RP_ENV("RELPOSE_TAP_INNER") ? atoi(RP_ENV("RELPOSE_TAP_INNER")) : 1;
-            d.tap_inner = (ti == 2 || (ti == 1 && d.osy == 2)) ? 1 : 0;
-        }
+        d.tap_inner = (d.osy == 2);      // K order: tap-inner for the 2x2-tap phases of transposed convs
         if (d.K != d.ntaps * d.Cin || d.Cin % BK || (s1 && s0.C % BK)) { rc = RELPOSE_EINVAL; return; }
         plan->descs.push_back(d);
     }
@@ -3064,50 +2822,39 @@ void Builder::end_group() {
     const int cp = plan->descs[first].cout_pad;
     int big_m = 0;
     for (int i = first; i < first + count; ++i) big_m = std::max(big_m, plan->descs[i].M / plan->descs[i].Nimg * 64);   // at the nominal batch
-    // tile configs: 0 = 128x128 (4 waves), 3 = 256x128 (8 waves, 4 waves/SIMD at 2 blocks/CU), 1 = 256x64, 2 = 256x32
-    // (3 measured within 1 % of 0 on conv3/conv4/deconv4-6 but needs twice the split-K: off unless RELPOSE_8WAVE is set)
-    static const bool tile128 = RP_ENV("RELPOSE_TILE128") != nullptr;      // experiment: 128-row tiles, 4 workgroups per CU
-    int cfg = cp >= 128 ? ((big_m >= 8192 && RP_ENV("RELPOSE_8WAVE")) ? 3 : 0) : (cp == 64 ? (tile128 ? 4 : 1) : (tile128 ? 5 : 2));
-    // 6 = 128 x 256 tiles (2 x 2 waves of 64 x 128: 8 accumulators per wave, 2 workgroups per CU) for Cout >= 256 (RELPOSE_TILE256N)
-    static const bool tile256n = RP_ENV("RELPOSE_TILE256N") != nullptr;
-    if (tile256n && cp >= 256 && cp % 256 == 0) cfg = 6;
+    // tile configs: 0 = 128x128 (4 waves), 1 = 256x64, 2 = 256x32, 4 = 128x64, 5 = 128x32, 7 = 64x64 (3: 256x128 on 8 waves and 6: 128x256
+    // lost their A/Bs and were removed with their kernels; the numbers of the others stay)
+    int cfg = cp >= 128 ? 0 : (cp == 64 ? 1 : 2);
     {   // 256-row tiles that would straddle BatchNorm groups where 128-row tiles would not: take the 128-row variant
         // (same throughput per tile shape, but it gets the uniform-group loader)
-        static const bool no_auto128 = RP_ENV("RELPOSE_NO_AUTO128") != nullptr;
         bool u256 = true, u128 = true;
         for (int i = first; i < first + count; ++i) {
             const int rows = 2 * plan->descs[i].Hp * plan->descs[i].Wp;
             u256 = u256 && rows % 256 == 0; u128 = u128 && rows % 128 == 0;
         }
-        if (!no_auto128 && !u256 && u128 && (cfg == 1 || cfg == 2)) cfg = cfg == 1 ? 4 : 5;
+        if (!u256 && u128 && (cfg == 1 || cfg == 2)) cfg = cfg == 1 ? 4 : 5;
     }
     // 7 = 64 x 64 tiles (2 x 2 waves of one 32 x 32 block) for the bottleneck layers (conv7-9, deconv9-7: <= 1024 output rows at the
     // nominal batch): with 128 x 128 tiles they have 1-9 M tiles and are split 64-128 ways along K -- 3 k-tiles per workgroup, 75 MB
     // of partial sums per layer for the reduce pass to add up; 64 x 64 tiles give 4x the tiles, an 8x smaller split and partial buffer
-    static const bool no_small = RP_ENV("RELPOSE_NO_TILE64") != nullptr;
-    const bool small = !no_small && cfg == 0 && big_m <= 1024 && cp % 64 == 0;
+    const bool small = cfg == 0 && big_m <= 1024 && cp % 64 == 0;
     if (small) cfg = 7;
     int BMt = cfg == 7 ? 64 : ((cfg == 0 || cfg >= 4) ? 128 : 256);
-    const int BNt = cfg == 7 ? 64 : (cfg == 6 ? 256 : ((cfg == 0 || cfg == 3) ? 128 : cp));
+    const int BNt = cfg == 7 ? 64 : (cfg == 0 ? 128 : cp);
     // Fused-phase kernel (deconv_tile_kernel): the 4 phases of stride-2 4x4 transposed convs with Cout 32 / 64 whose input grid
     // tiles into 16 x 16 (Cout 32) / 8 x 16 (Cout 64) patches -- deconv2 (112 x 112); fp32 products only.
     bool dtile = false;
     int dt_cfg = -1;
     {
-        static const bool no_dt = RP_ENV("RELPOSE_NO_DECONV_TILE") != nullptr;
-        // variants (RELPOSE_DT_VARIANT overrides; measured at 64 images, profiles/r02_conv_experiments.txt):
-        //   0: <MI 2, NI 1> 16 x 16 patches, 2 workgroups per CU      1: <1, 2> 8 x 16 patches, 2 per CU
-        //   2: <1, 1> 8 x 16 patches, 3 per CU, Cout 64 as two N tiles 3: <1, 1> 4 x 56 strips of 7 waves (56-wide grids)
-        static const int dt_var = RP_ENV("RELPOSE_DT_VARIANT") ? atoi(RP_ENV("RELPOSE_DT_VARIANT")) : -1;
-        const int Wg = plan->descs[first].Win;
-        static const bool dt_strip = RP_ENV("RELPOSE_DT_STRIP") != nullptr;   // 56-wide grids (deconv3): no gain measured (one 7-wave workgroup per CU)
-        static const bool no_pair = RP_ENV("RELPOSE_DT_NO_PAIR") != nullptr;
+        // variants (measured at 64 images, profiles/r02_conv_experiments.txt; 0: <MI 2, NI 1> 16 x 16 patches and 3: <1, 1> 4 x 56 strips of
+        // 7 waves for 56-wide grids lost and were removed):
+        //   1: <1, 2> 8 x 16 patches, 2 per CU      2: <1, 1> 8 x 16 patches, 3 per CU, Cout 64 as two N tiles
         //   4: <1, 1> pairs of 8 x 8 patches (grids that tile into 8 x 8 only: deconv3, 56 x 56), 3 per CU, Cout 64 as two N tiles
         // (three-piece bf16 rows: the <1, 2> variant's two weight tiles would need 95 KB of LDS -- Cout 64 as two N tiles of 32 there)
-        dt_cfg = Wg % 16 == 0 ? ((cp == 32 || net->prec >= RELPOSE_PREC_BF16X9) ? 2 : 1) : ((Wg == 56 && dt_strip) ? 3 : ((Wg % 8 == 0 && !no_pair) ? 4 : -1));
-        if (dt_var >= 0 && dt_var <= 2 && Wg % 16 == 0 && !(dt_var == 0 && cp != 32) && !(dt_var == 1 && cp != 64)) dt_cfg = dt_var;
-        const int PRt = dt_cfg == 0 ? 16 : (dt_cfg == 3 ? 4 : 8), PWt = dt_cfg == 3 ? 56 : (dt_cfg == 4 ? 8 : 16);
-        dtile = !no_dt && dt_cfg >= 0 && net->prec != 1 && (cp == 32 || cp == 64) && count % 4 == 0;
+        const int Wg = plan->descs[first].Win;
+        dt_cfg = Wg % 16 == 0 ? ((cp == 32 || net->prec >= RELPOSE_PREC_BF16X9) ? 2 : 1) : (Wg % 8 == 0 ? 4 : -1);
+        const int PRt = 8, PWt = dt_cfg == 4 ? 8 : 16;
+        dtile = dt_cfg >= 0 && net->prec != 1 && (cp == 32 || cp == 64) && count % 4 == 0;
         for (int i = first; i < first + count && dtile; ++i) {
             const ConvDesc& d = plan->descs[i];
             const ConvDesc& d0 = plan->descs[first + ((i - first) & ~3)];
@@ -3121,11 +2868,9 @@ void Builder::end_group() {
     // (conv2) or Cout 128 on pairs of 8 x 8 patches (conv3); fp32 products only.
     int s2_cfg = -1;
     {
-        static const bool no_s2 = RP_ENV("RELPOSE_NO_CONV_S2") != nullptr;
         const ConvDesc& d0 = plan->descs[first];
-        if (!no_s2 && !dtile && net->prec != 1) {
-            static const bool s2_small = RP_ENV("RELPOSE_S2_SMALL") != nullptr;     // experiment: 8 x 16 patches, 4 workgroups per CU
-            if (cp == 64 && d0.Hp % 16 == 0 && d0.Wp % 16 == 0) s2_cfg = s2_small ? 2 : 0;
+        if (!dtile && net->prec != 1) {
+            if (cp == 64 && d0.Hp % 16 == 0 && d0.Wp % 16 == 0) s2_cfg = 0;
             else if (cp == 128 && d0.Hp % 8 == 0 && d0.Wp % 8 == 0 && ((d0.Hp / 8) * (d0.Wp / 8) * 2) % 2 == 0 && n % 2 == 0) s2_cfg = 1;
         }
         for (int i = first; i < first + count && s2_cfg >= 0; ++i) {
@@ -3135,7 +2880,7 @@ void Builder::end_group() {
                             d.Hp == d0.Hp && d.Wp == d0.Wp && d.Cout == cp;
             if (!ok) s2_cfg = -1;
         }
-        if (s2_cfg >= 0) BMt = s2_cfg == 0 ? 256 : 128;              // (0: 16 x 16 patches; 1: pairs of 8 x 8; 2: 8 x 16)
+        if (s2_cfg >= 0) BMt = s2_cfg == 0 ? 256 : 128;              // (0: 16 x 16 patches; 1: pairs of 8 x 8)
     }
     int max_mt = 0, min_kt = 1 << 30;
     long tiles = 0;
@@ -3152,15 +2897,11 @@ void Builder::end_group() {
     // split along K until the launch has >= ~3000 tiles (>= 4 waves of resident blocks), keeping >= 8 k-tiles per slice
     int ksplit = 1;
     // (64 x 64 tiles: ~2 workgroups per CU are enough -- these launches are latency-bound chains, not throughput -- with >= 16 k-tiles each)
-    // (experiments build: RELPOSE_WANT_TILES / RELPOSE_WANT_TILES64 / RELPOSE_MIN_SLICE override the split-K rule below)
-    static const long wt_env = RP_ENV("RELPOSE_WANT_TILES") ? atol(RP_ENV("RELPOSE_WANT_TILES")) : 0;
-    static const long wt64_env = RP_ENV("RELPOSE_WANT_TILES64") ? atol(RP_ENV("RELPOSE_WANT_TILES64")) : 0;
-    static const int ms_env = RP_ENV("RELPOSE_MIN_SLICE") ? atoi(RP_ENV("RELPOSE_MIN_SLICE")) : 0;
     // (the three-piece bf16 kernels finish a tile in about 3/4 of the fp32 kernels' time, and the split-K reduction they then wait for is the same: half the
     // split pays in the loop -- configs[1], same box, 2 x 40 steps: 3000 tiles 785.3 pairs/s, 2000: 785.2, 1500: 790.5, 1000: 789.6, 700: 789.0; the 64 x 64
     // bottleneck tiles stay at 2048: 1024 / 512 / 256 / 64 give 785.9 / 784.5 / 778.1 / 741.3 against 785.5)
-    const long want_tiles = cfg == 7 ? (wt64_env > 0 ? wt64_env : 2048) : (wt_env > 0 ? wt_env : (net->prec >= RELPOSE_PREC_BF16X9 ? 1500 : 3000));
-    const int min_slice = ms_env > 0 ? ms_env : 8;
+    const long want_tiles = cfg == 7 ? 2048 : (net->prec >= RELPOSE_PREC_BF16X9 ? 1500 : 3000);
+    const int min_slice = 8;
     while (!dtile && s2_cfg < 0 && tiles * ksplit < want_tiles && ksplit < 64 && min_kt / (ksplit * 2) >= min_slice) ksplit *= 2;
     if (force_ksplit && !dtile && s2_cfg < 0) ksplit = force_ksplit;
     // Phase strip kernel (deconv_strip_kernel): the 4 phases of stride-2 4x4 transposed convs with Cout a multiple of 128 whose input grid
@@ -3227,14 +2968,13 @@ void Builder::end_group() {
     if (dtile) {
         Op o; o.type = OP_DECONV_TILE; o.first = first; o.count = count; o.cfg = dt_cfg; o.split = net->prec;
         o.grid = dim3((unsigned)(plan->descs[first].M / BMt), count / 4, dt_cfg >= 2 ? cp / 32 : 1);
-        if (dt_cfg != 3 && dt_cfg != 1) {
+        if (dt_cfg != 1) {
             // heads with a skip source (the self-view block of A3 / A2): accumulator snapshots for the self-stream cache -- the region
             // is laid out (and its offsets are the same) in every plan; only tagged forwards write it, only self-cached ones read it
-            const int mini = (dt_cfg == 0 || dt_cfg == 1) ? 2 : 1;                     // MI * NI of the variant
             for (int i = first; i < first + count; i += 4) {
                 ConvDesc& d = plan->descs[i];
                 if (d.nsrc != 2) continue;
-                const size_t nfl = (size_t)o.grid.x * o.grid.z * 256 * 64 * mini;
+                const size_t nfl = (size_t)o.grid.x * o.grid.z * 256 * 64;       // (MI * NI = 1 in variants 2 and 4)
                 d.snap = snapbuf ? snapbuf + plan->snap_floats : nullptr;
                 d.snap_mode = snapbuf ? snap_mode : 0;
                 plan->snap_floats += nfl;
@@ -3244,10 +2984,9 @@ void Builder::end_group() {
         return;
     }
     {   // split-K stride-2 4x4 convs of one source with Cout a multiple of 128 (conv4, conv5): the strip kernel
-        static const bool no_strip = RP_ENV("RELPOSE_NO_CONV_STRIP") != nullptr;
         const ConvDesc& d = plan->descs[first];
         const int hw = d.Hp * d.Wp;
-        bool ok = !no_strip && net->prec != 1 && count == 1 && ksplit > 1 && cfg == 0 && cp % 128 == 0 && d.osy == 1 && d.osx == 1 && d.sy == 2 && d.sx == 2 &&
+        bool ok = net->prec != 1 && count == 1 && ksplit > 1 && cfg == 0 && cp % 128 == 0 && d.osy == 1 && d.osx == 1 && d.sy == 2 && d.sx == 2 &&
                   d.ntaps == 16 && d.offy[0] == -1 && d.offx[0] == -1 && d.offy[15] == 2 && d.offx[15] == 2 && d.nsrc == 1 && d.src[0].sstride != 0 && !d.bias &&
                   d.Hin == 2 * d.Hp && d.Win == 2 * d.Wp && hw >= 128;
         // staged positions of a 128-pixel tile: 127 + row wraps + one image crossing + the taps' reach
@@ -3285,22 +3024,21 @@ void Builder::end_group() {
                 ph = ph && plan->descs[i + k].src[0].x == plan->descs[i].src[0].x && plan->descs[i + k].osy == 2 && plan->descs[i].osy == 2;
         // the 4 phase tiles of one spatial tile run back to back on the same XCD and share their input lines in its
         // L2 (deconv2: -10 %, deconv3: -2 %); small layers lose to the grid padding (8 tiles), so only above 512 tiles
-        static const bool no_pi = RP_ENV("RELPOSE_NO_PHASE_INTERLEAVE") != nullptr;
-        if (ph && !no_pi && max_mt >= 512) o.ninner = 4;
+        if (ph && max_mt >= 512) o.ninner = 4;
     }
     o.grid = (o.ninner == 1) ? dim3(max_mt * count, (cp / BNt) * ksplit, 1)
                              : dim3(((max_mt + 7) / 8) * 8 * count, (cp / BNt) * ksplit, 1);
     // LDS scale/shift table: every member must fit (groups spanned by a tile) x Cin entries in 1024
-    o.sslds = 1; o.uni = (cfg != 3);
+    o.sslds = 1; o.uni = 1;
     for (int i = first; i < first + count; ++i) {
         const ConvDesc& d = plan->descs[i];
         const int hw = d.Hp * d.Wp;
         const int ng = (BMt - 1) / (2 * hw) + 2;
-        if ((long)ng * d.Cin > ((cfg == 0 || cfg == 3 || cfg == 6 || cfg == 7) ? 2048 : 512) || d.src[0].sstride == 0) o.sslds = 0;
+        if ((long)ng * d.Cin > ((cfg == 0 || cfg == 7) ? 2048 : 512) || d.src[0].sstride == 0) o.sslds = 0;
         if ((2 * hw) % BMt) o.uni = 0;             // some tile would straddle two BatchNorm groups
     }
     if (!o.sslds) o.uni = 0;
-    o.split = (cfg != 3) ? net->prec : 0;
+    o.split = net->prec;
     plan->ops.push_back(o);
     if (ksplit > 1) {
         Op r; r.type = OP_REDUCE; r.first = first; r.count = count; r.cfg = 0; r.grid = dim3(256, 1, count);
@@ -3316,9 +3054,9 @@ void build_plan(RelposeSCNet* net, int n, Builder& R) {
         R.begin_group(); R.conv(layer, s0, s1, Hin, out, ochoff); R.end_group();
     };
     // encoder, three modalities x two streams in concatenated buffers (mymodel.py:266-291)
-    { Op o; o.type = OP_CONV1; o.first = o.count = o.cfg = 0; R.plan->ops.push_back(o); }   // direct kernel
+    { Op o; o.type = OP_CONV1; o.first = o.count = o.cfg = 0; R.plan->ops.push_back(o); }   // conv1_mfma_kernel
     R.stats("A1");
-    if (net->bn) R.plan->ops.back().cfg = 1;      // partial records already written by conv1_direct_kernel
+    if (net->bn) R.plan->ops.back().cfg = 1;      // partial records already written by conv1_mfma_kernel
     if (R.self_cached) R.plan->ops.back().skip_blk = 32;
     R.plan->head_count = (int)R.plan->ops.size();
     if (R.self_cached) {
@@ -3368,8 +3106,6 @@ void build_plan(RelposeSCNet* net, int n, Builder& R) {
     R.skip_slices = R.self_cached ? 0x15 : 0;
     const size_t conv4_desc = R.plan->descs.size();
     one("conv4", R.src("A3", 0, 768), nullptr, 56, "A4", 0);
-    // the bottleneck chain starts with conv4's split-K reduction (when it has one) and ends in front of deconv5
-    R.plan->mid_first = (int)R.plan->ops.size() - ((!R.plan->ops.empty() && R.plan->ops.back().type == OP_REDUCE) ? 1 : 0);
     R.stats("A4");
     R.force_ksplit = 0; R.shared_slices = 0; R.skip_slices = 0;
     // (the strip kernel took the shared slices: nothing reads the warped blocks of A3 beyond the first image pair, no copies needed)
@@ -3388,7 +3124,6 @@ void build_plan(RelposeSCNet* net, int n, Builder& R) {
     sk = R.src("A8", 0, 512); one("deconv8", R.src("D9", 0, 512), skp, 3, "D8", 0); R.stats("D8");
     sk = R.src("A7", 0, 512); one("deconv7", R.src("D8", 0, 512), skp, 3, "D7", 0); R.stats("D7");
     sk = R.src("A6", 0, 512); one("deconv6", R.src("D7", 0, 512), skp, 7, "D6", 0); R.stats("D6");
-    R.plan->mid_end = (int)R.plan->ops.size();
     sk = R.src("A5", 0, 512); one("deconv5", R.src("D6", 0, 512), skp, 14, "D5", 0); R.stats("D5");
     sk = R.src("A4", 0, 256); one("deconv4", R.src("D5", 0, 256), skp, 28, "D4", 0); R.stats("D4");
     // heads (mymodel.py:309-376): rgb/n/d with skips from the self stream, s/f without
@@ -3410,7 +3145,7 @@ void build_plan(RelposeSCNet* net, int n, Builder& R) {
     for (int m = 3; m < 5; ++m) if (wanted(m)) R.conv(std::string("deconv2") + heads[m], R.src("D3", m * 64, 64), nullptr, 112, "D2", d2off[m]);
     R.end_group(); R.stats("D2");
     R.plan->tail_first = (int)R.plan->ops.size();
-    if (RP_ENV("RELPOSE_GEMM_HEADS") || (net->S != 15 && net->S != 21)) {   // generic implicit-GEMM path (5 members)
+    if (net->S != 15 && net->S != 21) {   // generic implicit-GEMM path (5 members)
         if (R.pose_only) R.rc = RELPOSE_EINVAL;                               // (pose-only plans need the fused heads kernel: S = 15 / 21)
         const int ooff[5] = {0, 3, 6, 7, 7 + net->S};
         // a group's members share one tile config (end_group): heads of another cout_pad -- the semantic head from S = 33 on (64, the
@@ -3446,13 +3181,10 @@ void free_plan(RelposeSCNet* net) {
         if (p->d_descs) (void)hipFree(p->d_descs);
         if (p->tail_ev) (void)hipEventDestroy(p->tail_ev);
         if (p->head_ev) (void)hipEventDestroy(p->head_ev);
-        if (p->mid_ev0) (void)hipEventDestroy(p->mid_ev0);
-        if (p->mid_ev1) (void)hipEventDestroy(p->mid_ev1);
         delete p;
     }
     net->plans.clear();
     net->self_state.clear();       // (new weights / precision: nothing cached is valid)
-    net->pending.clear();          // (a half-enqueued forward loses its plan: its BACK call returns RELPOSE_EINVAL)
 }
 
 struct WsOffsets { size_t act, ss, partial, splitk, statp, persist, snap, total; };
@@ -3667,16 +3399,9 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     const uint64_t self_tag = (!variant && args->struct_size >= offsetof(RelposeForwardArgs, self_tag) + sizeof(uint64_t)) ? args->self_tag : 0;
     const uint64_t ws_gen = args->struct_size >= offsetof(RelposeForwardArgs, workspace_generation) + sizeof(uint64_t) ? args->workspace_generation : 0;
     if (!net->finalized || !x || !out || !workspace || n <= 0 || (n & 1) || H <= 0 || W <= 0 || n >= (1 << 24)) return RELPOSE_EINVAL;
-    if (flags & ~(RELPOSE_FWD_ZERO_WARP | RELPOSE_FWD_POSE_OUTPUTS | RELPOSE_FWD_NEW_WORKSPACE | RELPOSE_FWD_PART_FRONT | RELPOSE_FWD_PART_BACK)) return RELPOSE_EINVAL;
-    const int part = flags & (RELPOSE_FWD_PART_FRONT | RELPOSE_FWD_PART_BACK);
-    if (part == (RELPOSE_FWD_PART_FRONT | RELPOSE_FWD_PART_BACK)) return RELPOSE_EINVAL;
-#ifdef RP_EXPERIMENTS
-    void* mid_stream = (args->struct_size >= offsetof(RelposeForwardArgs, reserved1) + sizeof(void*) && args->reserved1) ? args->reserved1 : args->stream;
-#else
-    // product build: one call = one forward, the bottleneck chain stays on `stream` (the two-part / third-stream forms lost their A/Bs, round 5)
-    if (part || (args->struct_size >= offsetof(RelposeForwardArgs, reserved1) + sizeof(void*) && args->reserved1)) return RELPOSE_EINVAL;
-    void* mid_stream = args->stream;
-#endif
+    if (flags & ~(RELPOSE_FWD_ZERO_WARP | RELPOSE_FWD_POSE_OUTPUTS | RELPOSE_FWD_NEW_WORKSPACE)) return RELPOSE_EINVAL;
+    // one call = one forward, the bottleneck chain stays on `stream` (the two-part / third-stream forms lost their A/Bs, round 5, and were removed)
+    if (args->struct_size >= offsetof(RelposeForwardArgs, reserved1) + sizeof(void*) && args->reserved1) return RELPOSE_EINVAL;
     const int G = n / 2;
     // (nothing to share with one BatchNorm group; the tile kernels' patch pairing wants the 2-image members' patch count even as well)
     const bool zero_warp = (flags & RELPOSE_FWD_ZERO_WARP) && n > 2 && !variant;
@@ -3684,18 +3409,6 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     Plan* plan = nullptr;
     RelposeSCNet::SelfState commit;          // what the workspace holds once this forward is through
     commit.tag = self_tag; commit.n = n; commit.H = H; commit.W = W; commit.pose_only = pose_only; commit.gen = ws_gen;
-    if (part == RELPOSE_FWD_PART_BACK) {
-        // the second half of a forward whose FRONT call chose the plan (and invalidated the self-stream record): same arguments, or nothing runs
-        auto it = net->pending.find(workspace);
-        if (it == net->pending.end()) return RELPOSE_EINVAL;
-        const RelposeSCNet::PendingFront pf = it->second;
-        net->pending.erase(it);
-        if (pf.x != x || pf.out != out || pf.flags != (flags & ~(RELPOSE_FWD_PART_BACK | RELPOSE_FWD_NEW_WORKSPACE)) || pf.st.n != n || pf.st.H != H || pf.st.W != W ||
-            pf.st.tag != self_tag || pf.st.gen != ws_gen)
-            return RELPOSE_EINVAL;
-        plan = (Plan*)pf.plan;
-    } else {
-    net->pending.erase(workspace);           // (a FRONT that is never followed by its BACK: dropped by whatever forward comes next)
     if (flags & RELPOSE_FWD_NEW_WORKSPACE) net->self_state.erase(workspace);      // the memory behind this pointer is not what the last forward left
     // Self-stream cache: the previous forward on this workspace carried the same non-zero tag (and shape, and -- when the caller names its
     // allocations -- the same workspace generation) -> the self-view encoder streams it left in the workspace are what this forward would
@@ -3716,7 +3429,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         if (it != net->plans.end()) { plan = (Plan*)it->second; break; }
         const WsOffsets o = ws_offsets(net, n);
         if (workspace_bytes < o.total) return RELPOSE_ENOMEM;
-        if (net->plans.size() >= 32 && net->pending.empty()) {       // callers keep a few long-lived workspaces; bound the cache
+        if (net->plans.size() >= 32) {       // callers keep a few long-lived workspaces; bound the cache
             free_plan(net);
             self_cached = false;             // (free_plan drops every workspace's self-stream record with the plans)
             snap_mode = self_tag != 0 ? 1 : 0;
@@ -3742,13 +3455,11 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         net->plans[std::make_pair(workspace, key2)] = p;
         plan = p;
     }
-    }   // (part != BACK)
     if (!plan) return RELPOSE_EINVAL;
     net->last_n = n;
     // two-stream mode: the HBM-bound head (resize_in, conv1) and tail (heads, resize_out) run on tail_stream, the MFMA-bound middle on `stream`
-    static const bool head_side = RP_ENV("RELPOSE_NO_HEAD_OVERLAP") == nullptr;
     const bool two = tail_stream != stream;
-    hipStream_t s = (two && head_side && plan->head_count > 0) ? (hipStream_t)tail_stream : (hipStream_t)stream;
+    hipStream_t s = (two && plan->head_count > 0) ? (hipStream_t)tail_stream : (hipStream_t)stream;
     const WsOffsets o = ws_offsets(net, n);
     char* ws = (char*)workspace;
     float* act = (float*)(ws + o.act);
@@ -3759,8 +3470,6 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, s);
         net->ev.push_back(e); net->ev_kind.push_back(kind);
     };
-    const bool mid_split = plan->mid_first >= 0 && plan->mid_end > plan->mid_first && plan->mid_first >= plan->head_count && plan->mid_end <= plan->tail_first;
-    if (part && !mid_split) return RELPOSE_EINVAL;
     if (net->omask != 31) {
         // heads the net was constructed without: their blocks of D3 / D2 (and, on the generic heads path, their channels of OUT) are written by
         // nobody -- zero them so that what the heads kernel multiplies by its zero weights is finite; their output channels come out 0
@@ -3769,43 +3478,12 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
             RP_HIP(hipMemsetAsync(act + B.off * n, 0, (size_t)n * B.H * B.H * B.C * sizeof(float), s));
         }
     }
-    if (part != RELPOSE_FWD_PART_BACK) {
-        mark(3);
-        hipLaunchKernelGGL(resize_in_kernel, dim3(2048), dim3(256), 0, s, x, act + net->bufs["X0"].off * n, n, H, W, plan->self_cached ? 8 : 0);
-        mark(-3);
-    } else {
-        // the decoder continues on `stream` behind the chain (wherever FRONT enqueued it)
-        s = (hipStream_t)stream;
-        RP_HIP(hipStreamWaitEvent(s, plan->mid_ev1, 0));
-    }
+    mark(3);
+    hipLaunchKernelGGL(resize_in_kernel, dim3(2048), dim3(256), 0, s, x, act + net->bufs["X0"].off * n, n, H, W, plan->self_cached ? 8 : 0);
+    mark(-3);
     int op_index = -1;
     for (const Op& op : plan->ops) {
         ++op_index;
-        if (part == RELPOSE_FWD_PART_BACK && op_index < plan->mid_end) continue;
-        if (mid_split && op_index == plan->mid_first && part != RELPOSE_FWD_PART_BACK && (hipStream_t)mid_stream != s) {
-            if (!plan->mid_ev0) RP_HIP(hipEventCreateWithFlags(&plan->mid_ev0, hipEventDisableTiming));
-            RP_HIP(hipEventRecord(plan->mid_ev0, s));
-            s = (hipStream_t)mid_stream;
-            RP_HIP(hipStreamWaitEvent(s, plan->mid_ev0, 0));
-        }
-        if (mid_split && op_index == plan->mid_end && part != RELPOSE_FWD_PART_BACK) {
-            if (part == RELPOSE_FWD_PART_FRONT) {
-                // the first half ends here: BACK (the next call on this workspace) orders the decoder behind this event
-                if (!plan->mid_ev1) RP_HIP(hipEventCreateWithFlags(&plan->mid_ev1, hipEventDisableTiming));
-                RP_HIP(hipEventRecord(plan->mid_ev1, s));
-                RP_CHECK_LAUNCH();
-                RelposeSCNet::PendingFront pf;
-                pf.plan = plan; pf.st = commit; pf.x = x; pf.out = out; pf.flags = flags & ~(RELPOSE_FWD_PART_FRONT | RELPOSE_FWD_NEW_WORKSPACE);
-                net->pending[workspace] = pf;
-                return 0;
-            }
-            if (s != (hipStream_t)stream) {
-                if (!plan->mid_ev1) RP_HIP(hipEventCreateWithFlags(&plan->mid_ev1, hipEventDisableTiming));
-                RP_HIP(hipEventRecord(plan->mid_ev1, s));
-                s = (hipStream_t)stream;
-                RP_HIP(hipStreamWaitEvent(s, plan->mid_ev1, 0));
-            }
-        }
         if (op.type == OP_NOP) continue;
         if (op_index == plan->head_count && s != (hipStream_t)stream) {      // head done: the convolutions continue on `stream`
             if (!plan->head_ev) RP_HIP(hipEventCreateWithFlags(&plan->head_ev, hipEventDisableTiming));
@@ -3824,7 +3502,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         if (op.type == OP_CONV) {
             mark(1);
             const ConvDesc* dd = plan->d_descs + op.first;
-            // 4-wave tiles: cfg 0 = 128x128 (2x2 waves of 64x64), 1 = 256x64, 2 = 256x32, 4 = 128x64, 5 = 128x32
+            // 4-wave tiles: cfg 0 = 128x128 (2x2 waves of 64x64), 1 = 256x64, 2 = 256x32, 4 = 128x64, 5 = 128x32, 7 = 64x64
 #define RP_LAUNCH_V(WM_, WN_, MI_, NI_, SS_, UNI_, SP_) \
             hipLaunchKernelGGL((conv_igemm_kernel<WM_, WN_, MI_, NI_, SS_, UNI_, SP_>), op.grid, dim3(256), 0, s, dd, op.ninner, op.mt_max)
 #define RP_LAUNCH_T(WM_, WN_, MI_, NI_)                                                                        \
@@ -3855,15 +3533,10 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
                     else RP_LAUNCH_V(WM_, WN_, MI_, NI_, false, false, 0);                                     \
                 }                                                                                              \
             } while (0)
-            if (op.cfg == 3) {
-                if (op.sslds) hipLaunchKernelGGL((conv_igemm_kernel<4, 2, 2, 2, true>), op.grid, dim3(512), 0, s, dd, op.ninner, op.mt_max);
-                else hipLaunchKernelGGL((conv_igemm_kernel<4, 2, 2, 2, false>), op.grid, dim3(512), 0, s, dd, op.ninner, op.mt_max);
-            }
-            else if (op.cfg == 0) RP_LAUNCH_T(2, 2, 2, 2);
+            if (op.cfg == 0) RP_LAUNCH_T(2, 2, 2, 2);
             else if (op.cfg == 1) RP_LAUNCH_T(4, 1, 2, 2);
             else if (op.cfg == 2) RP_LAUNCH_T(4, 1, 2, 1);
             else if (op.cfg == 4) RP_LAUNCH_T(4, 1, 1, 2);
-            else if (op.cfg == 6) RP_LAUNCH_T(2, 2, 2, 4);
             else if (op.cfg == 7) RP_LAUNCH_T(2, 2, 1, 1);
             else RP_LAUNCH_T(4, 1, 1, 1);
 #undef RP_LAUNCH_T
@@ -3880,14 +3553,6 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
                 else if (op.split == 5) { LAUNCH_(5); }                   \
                 else { LAUNCH_(0); }                                      \
             } while (0)
-            /* (variants that exist for the experiment log only: no three-piece instantiations) */ \
-#define RP_TILE_SPLIT_X(LAUNCH_)                                          \
-            do {                                                          \
-                if (op.split == 2) { LAUNCH_(2); }                        \
-                else if (op.split == 3) { LAUNCH_(3); }                   \
-                else if (op.split >= 4) return RELPOSE_EINVAL;            \
-                else { LAUNCH_(0); }                                      \
-            } while (0)
 #define RP_L_STRIP(SP_) hipLaunchKernelGGL((conv_s2_strip_kernel<4, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
 #define RP_L_DSTRIP(SP_) hipLaunchKernelGGL((deconv_strip_kernel<4, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first, op.mt_max)
             if (op.cfg == 1) RP_TILE_SPLIT(RP_L_DSTRIP);        // the phases of a transposed conv (deconv4, deconv5)
@@ -3898,44 +3563,34 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         } else if (op.type == OP_CONV_S2) {
             mark(1);
 #define RP_L_S2A(SP_) hipLaunchKernelGGL((conv_s2_tile_kernel<2, 2, 16, false, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
-#define RP_L_S2B(SP_) hipLaunchKernelGGL((conv_s2_tile_kernel<1, 2, 16, false, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
 #define RP_L_S2C(SP_) hipLaunchKernelGGL((conv_s2_tile_kernel<1, 4, 8, true, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
             if (op.cfg == 0) RP_TILE_SPLIT(RP_L_S2A);
-            else if (op.cfg == 2) RP_TILE_SPLIT_X(RP_L_S2B);
             else RP_TILE_SPLIT(RP_L_S2C);
 #undef RP_L_S2A
-#undef RP_L_S2B
 #undef RP_L_S2C
             mark(-1);
         } else if (op.type == OP_DECONV_TILE) {
             mark(1);
-#define RP_L_DT0(SP_) hipLaunchKernelGGL((deconv_tile_kernel<2, 1, 4, 16, false, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
 #define RP_L_DT1(SP_) hipLaunchKernelGGL((deconv_tile_kernel<1, 2, 4, 16, false, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
 #define RP_L_DT2(SP_) hipLaunchKernelGGL((deconv_tile_kernel<1, 1, 4, 16, false, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
 #define RP_L_DT4(SP_) hipLaunchKernelGGL((deconv_tile_kernel<1, 1, 4, 8, true, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
-#define RP_L_DT3(SP_) hipLaunchKernelGGL((deconv_tile_kernel<1, 1, 7, 8, false, SP_>), op.grid, dim3(448), 0, s, plan->d_descs + op.first)
-            if (op.cfg == 0) RP_TILE_SPLIT_X(RP_L_DT0);
-            else if (op.cfg == 1) RP_TILE_SPLIT_X(RP_L_DT1);
+            if (op.cfg == 1) {                     // (no three-piece instantiations: those modes take variant 2)
+                if (op.split == 2) RP_L_DT1(2);
+                else if (op.split == 3) RP_L_DT1(3);
+                else if (op.split >= 4) return RELPOSE_EINVAL;
+                else RP_L_DT1(0);
+            }
             else if (op.cfg == 2) RP_TILE_SPLIT(RP_L_DT2);
-            else if (op.cfg == 4) RP_TILE_SPLIT(RP_L_DT4);
-            else RP_TILE_SPLIT_X(RP_L_DT3);
-#undef RP_L_DT0
+            else RP_TILE_SPLIT(RP_L_DT4);
 #undef RP_L_DT1
 #undef RP_L_DT2
-#undef RP_L_DT3
 #undef RP_L_DT4
 #undef RP_TILE_SPLIT
-#undef RP_TILE_SPLIT_X
             mark(-1);
         } else if (op.type == OP_CONV1) {
             mark(1);
-            static const bool c1_direct = RP_ENV("RELPOSE_CONV1_DIRECT") != nullptr;      // the round-1 VALU kernel (A/B switch)
-            if (c1_direct)
-                hipLaunchKernelGGL(conv1_direct_kernel, dim3(1024), dim3(256), 0, s, act + net->bufs["X0"].off * n, net->d_w + net->w1_off,
-                                   act + net->bufs["A1"].off * n, partial, n);
-            else
-                hipLaunchKernelGGL(conv1_mfma_kernel, dim3(196 * n), dim3(256), 0, s, act + net->bufs["X0"].off * n, net->d_w + net->w1_off,
-                                   act + net->bufs["A1"].off * n, partial, n, (plan->zero_warp ? 1 : 0) | (plan->self_cached ? 2 : 0));
+            hipLaunchKernelGGL(conv1_mfma_kernel, dim3(196 * n), dim3(256), 0, s, act + net->bufs["X0"].off * n, net->d_w + net->w1_off,
+                               act + net->bufs["A1"].off * n, partial, n, (plan->zero_warp ? 1 : 0) | (plan->self_cached ? 2 : 0));
             mark(-1);
         } else if (op.type == OP_STATS_FUSED) {
             const Buf& B = net->bufs[op.buf];
@@ -3985,7 +3640,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         } else {
             const Buf& B = net->bufs[op.buf];
             const int rows = 2 * B.H * B.H;
-            if (op.cfg == 1) {                     // A1: finalise the per-pass records of conv1_direct_kernel
+            if (op.cfg == 1) {                     // A1: finalise the per-pass records of conv1_mfma_kernel
                 mark(2);
                 hipLaunchKernelGGL(bn_finalize_parts_kernel, dim3((B.C + 31) / 32, G), dim3(1024), 0, s, partial, C1_PASSES_PER_GROUP, B.C, rows,
                                    net->d_gb + B.gb_off, net->d_gb + B.gb_off + B.C, ssp + B.ss_off * G, op.skip_blk);

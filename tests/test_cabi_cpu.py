@@ -21,7 +21,6 @@ def lib():
 def header_symbols():
     src = open(os.path.join(ROOT, "include", "relpose.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"#ifdef RP_EXPERIMENTS.*?#endif", "", src, flags=re.S)      # (lost A/Bs of the experiment log: not in the product ABI)
     return sorted(set(re.findall(r"\b(relpose_[a-z0-9_]+)\s*\(", src)))
 
 

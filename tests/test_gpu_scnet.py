@@ -359,6 +359,44 @@ def test_scnet_rejects_odd_batch_like_reference():
         net(torch.zeros(1, 16, 160, 640, device="cuda"))
 
 
+def test_scnet_forward_ex_rejects_the_removed_two_part_arguments():
+    """Flag bits 8 and 16 (round 5's two-part forward) and RelposeForwardArgs::reserved1 (its third stream) name nothing any more:
+    relpose_scnet_forward_ex returns RELPOSE_EINVAL for them like for any unknown argument, before anything is enqueued -- `out` keeps its
+    content -- and without a claim on the workspace: a plain forward on it afterwards is bitwise the forward on a fresh workspace."""
+    import ctypes as C
+    import torch
+    from relativepose_amd import _lib
+    tag, S, tanh, seed, ds, mm = SCNET_CASES[0]
+    net, _ = make_net(S, tanh, seed)
+    x = torch.from_numpy(oracle_scnet_input(602, ds, mm)).cuda().contiguous()
+    assert tuple(x.shape) == (2, 16, 160, 640)
+    ref = net.forward(x, ws_key="fresh").clone()
+    ws = net._workspace(2, 160, 640, x.device, "rejected")
+    out = torch.full_like(ref, 7.0)
+    side = torch.cuda.Stream()
+
+    def call(flags, reserved1):
+        a = _lib.ForwardArgs()
+        a.struct_size = C.sizeof(_lib.ForwardArgs)
+        a.flags = flags
+        a.x, a.out = x.data_ptr(), out.data_ptr()
+        a.n_images, a.H, a.W = 2, 160, 640
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        a.stream = a.tail_stream = torch.cuda.current_stream().cuda_stream
+        a.workspace_generation = net._ws_gen
+        a.reserved1 = reserved1
+        return _lib.lib().relpose_scnet_forward_ex(net.handle, C.byref(a))
+
+    EINVAL = -1
+    for flags in (8, 16, 24):
+        assert call(flags, None) == EINVAL, flags
+    assert side.cuda_stream != 0 and call(0, side.cuda_stream) == EINVAL
+    torch.cuda.synchronize()
+    assert float(out.min()) == 7.0 and float(out.max()) == 7.0
+    assert torch.equal(net.forward(x, ws_key="rejected"), ref)
+    log("scnet_forward_ex_rejections", bitwise=True)
+
+
 @pytest.mark.parametrize("mode,bound_max,bound_mean", [("bf16x9", 5e-4, 2e-5), ("bf16x6", 5e-4, 2e-5), ("f16x3", 5e-4, 2e-5), ("bf16x3", 2e-3, 1e-4), ("f16", 1e-1, 5e-3)])
 @pytest.mark.parametrize("hw", [(160, 640), (320, 1280)])
 def test_scnet_split_precision_options_close_to_f32_and_reversible(hw, mode, bound_max, bound_mean):

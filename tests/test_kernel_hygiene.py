@@ -6,7 +6,8 @@ only show as crashes or slow kernels.
   through the barrier -- and read the claimed chunk index -- before lane 0 had written it: a memory fault on the GPU.  Barriers and
   irreducible regions do not mix, so no kernel of the library may contain one.
 * The kernels the headline runs on keep their register budget: no VGPR spills in the fp32 tile kernels, conv1, the heads and the
-  512-thread fit; the 1024-thread fit and the affinity tile kernel stay at 128 VGPRs (4 waves per SIMD)."""
+  512-thread fit; the 768-thread fit stays at 170 VGPRs (3 waves per SIMD) and the affinity tile kernel at 128 (4 waves per SIMD).
+* The library's sources carry no laboratory: no environment switch and no preprocessor conditional beyond the header guards."""
 import os
 import re
 import shutil
@@ -117,3 +118,19 @@ def test_headline_kernels_keep_their_register_budget(device_asm):
     for parts in spill_free[:6]:
         for n in find(*parts):
             assert k[n]["vgpr_count"] <= 168 or "Li1ELi2ELi4ELi16" in n, (n, k[n])
+
+
+def test_sources_carry_no_experiment_switches():
+    """The shipped sources are the product: nothing reads the environment and no preprocessor conditional selects between variants of a
+    kernel or of the host code (the A/B arms that lost are in the history and their measurements in profiles/ and DESIGN.md).  The
+    allow-list is exact: rp_math.h is shared with host-only code, relpose.h has its include guard and its two extern "C" brackets."""
+    allowed = {"rp_math.h": ["#if defined(__HIPCC__)"], "relpose.h": ["#ifndef RELPOSE_H", "#ifdef __cplusplus", "#ifdef __cplusplus"]}
+    root = os.path.dirname(B.HERE)
+    files = sorted(os.path.join(B.CSRC, f) for f in os.listdir(B.CSRC) if f.endswith((".hip", ".h"))) + [os.path.join(root, "include", "relpose.h")]
+    assert len(files) > 10
+    for path in files:
+        txt = open(path).read()
+        for word in ("getenv", "RP_ENV", "RP_EXPERIMENTS"):
+            assert word not in txt, f"{path}: {word}"
+        conds = [re.sub(r"\s+", " ", re.sub(r"^\s*#\s*", "#", l)).strip() for l in txt.split("\n") if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", l)]
+        assert conds == allowed.get(os.path.basename(path), []), f"{path}: {conds}"

@@ -1,6 +1,7 @@
-"""Build relativepose_amd/librelpose_hip_<name>.so with extra flags on every source (experiments / ablations; e.g. -DRP_EXPERIMENTS
-turns the RELPOSE_* environment switches of the experiment log back on).  Use it with RELPOSE_LIB_PATH=<that file>.
-    python tools/build_variant.py xp -DRP_EXPERIMENTS"""
+"""Build relativepose_amd/librelpose_hip_<name>.so from the working tree, with extra compiler flags on every source if any are given:
+a second library next to the product one, for A/B comparisons (tools/gpu_evidence.sh ab).  Use it with RELPOSE_LIB_PATH=<that file>.
+The sources have no experiment switches of their own; a variant is a source change.
+    python tools/build_variant.py cand [-O2 ...]"""
 import os, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from relativepose_amd import build as b
