@@ -730,6 +730,55 @@ typedef struct RelposeContrastLossArgs {
 size_t relpose_contrast_loss_workspace_bytes(int32_t n_pairs, int32_t n_corres);
 int relpose_contrast_loss(const RelposeContrastLossArgs* args);
 
+/* -------------------------------------------------------------------- normal maps from depth panoramas
+ * The reference reads every view's normal map from disk (datasets/SUNCG.py:300-313); the tool that made those files was never published.
+ * relpose_depth_normals estimates the map from the depth panorama alone, so that RGB-D panoramas enter the pair pipeline without one.
+ * The contract is the project's own (tests/normals_model.py restates it in numpy).  One kernel launch, enqueued on
+ * `stream`; no workspace; invalid arguments return RELPOSE_EINVAL before anything is enqueued.  All arithmetic is fp32, every operation
+ * rounded on its own (no fused multiply-add), in the order written here, so count and moments are repeatable bit for bit and a view's
+ * result does not depend on the batch around it.
+ *
+ *   depth            [n_views, h, 4h] f32, 0 = no data
+ *   dataset          RELPOSE_SUNCG / _MATTERPORT / _SCANNET: which face rotation a column block has
+ *   radius           r in 1..4: the window is (2r+1)^2 pixels; h >= 2r+1
+ *   gate_scale       finite, > 0 (3.0 is the library's default)
+ *   min_neighbors    3 .. (2r+1)^2 - 1 (6 is the library's default)
+ *   P(x, y)          the point of pixel (x, y), x in 0..4h-1: slot = x / h, xf = x - slot h, z = depth,
+ *                    xn = ((float)xf / (float)h - 0.5f) * 2.0f, yn = (0.5f - (float)y / (float)h) * 2.0f, face point (xn z, yn z, -z),
+ *                    rotated by the face rotation Rs[slot] (suncg) / Rs[(slot - 1) % 4] (matterport, scannet): a signed permutation,
+ *                    exact.  The frame is relpose_pano2pc's (without its scannet focal scaling) and the one relpose_warp rotates normals in
+ *   window           columns wrap around the ring of four faces (column 4h-1 is next to column 0, windows cross the face seams: consecutive
+ *                    slots are consecutive quarter turns about the vertical axis and share the ray of their common edge); rows do not
+ *                    wrap, rows outside 0..h-1 contribute nothing
+ *   acceptance       neighbour q of centre p is used when depth_q != 0, depth_p != 0 and d2 <= g2, with d = P_q - P_p componentwise,
+ *                    d2 = d.x d.x + d.y d.y + d.z d.z left to right, g = gate_scale * (float)r * (2.0f / (float)h) * depth_p left to right,
+ *                    g2 = g g: the gate keeps a window from mixing a foreground surface with what lies behind it
+ *   count            [n_views, h, 4h] i32 or NULL: the number of accepted neighbours
+ *   moments          [n_views, 9, h, 4h] f32 or NULL: sums over the accepted neighbours, visited dy ascending (outer), dx ascending (inner),
+ *                    centre skipped, of d.x, d.y, d.z, d.x d.x, d.x d.y, d.x d.z, d.y d.y, d.y d.z, d.z d.z
+ *   C                C_ab = S_ab - s_a s_b / m with m = (float)(count + 1) (the + 1 is the centre, whose d is 0), evaluated (s_a s_b) / m
+ *   normal           [n_views, 3, h, 4h] f32: the eigenvector of C's smallest eigenvalue (six cyclic Jacobi sweeps in fp32), scaled to unit
+ *                    length, negated when n . P_p > 0 so that it faces the sensor; (0, 0, 0) where valid is 0
+ *   valid            [n_views, h, 4h] u8 or NULL: depth_p != 0 && count >= min_neighbors && l1 > 1e-6f l2 (l0 <= l1 <= l2 the eigenvalues:
+ *                    the accepted neighbours are not collinear) */
+typedef struct RelposeDepthNormalsArgs {
+    uint32_t struct_size;       /* sizeof(RelposeDepthNormalsArgs) as the caller compiled it */
+    int32_t n_views;
+    int32_t h;
+    int32_t dataset;
+    int32_t radius;
+    int32_t min_neighbors;
+    float gate_scale;
+    int32_t reserved0;
+    const float* depth;
+    float* normal;
+    uint8_t* valid;
+    int32_t* count;
+    float* moments;
+    void* stream;
+} RelposeDepthNormalsArgs;
+int relpose_depth_normals(const RelposeDepthNormalsArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

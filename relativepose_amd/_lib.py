@@ -160,6 +160,13 @@ class ContrastLossArgs(C.Structure):
                 ("stream", c_void_p)]
 
 
+class DepthNormalsArgs(C.Structure):
+    """RelposeDepthNormalsArgs (include/relpose.h): the argument block of relpose_depth_normals."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_views", c_int), ("h", c_int), ("dataset", c_int), ("radius", c_int), ("min_neighbors", c_int),
+                ("gate_scale", C.c_float), ("reserved0", c_int), ("depth", c_void_p), ("normal", c_void_p), ("valid", c_void_p),
+                ("count", c_void_p), ("moments", c_void_p), ("stream", c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -209,6 +216,7 @@ SIGNATURES = {
     "relpose_completion_loss": (c_int, [C.POINTER(CompletionLossArgs)]),
     "relpose_contrast_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
     "relpose_contrast_loss": (c_int, [C.POINTER(ContrastLossArgs)]),
+    "relpose_depth_normals": (c_int, [C.POINTER(DepthNormalsArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

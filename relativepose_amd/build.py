@@ -22,6 +22,7 @@ SOURCES = [
     ("descriptor.hip", ["-ffp-contract=off"]),    # descriptor evaluation: the thresholds and counts must agree with tests/descriptor_model.py
     ("siftdesc.hip", ["-ffp-contract=off"]),      # SIFT descriptors: the base blur must agree with tests/sift_model.py bit for bit
     ("completion.hip", ["-ffp-contract=off"]),    # completion losses: the fp32 terms must agree with tests/completion_model.py
+    ("normals.hip", ["-ffp-contract=off"]),       # depth normals: count and the nine moments must agree with tests/normals_model.py bit for bit
     ("scnet.hip", []),
 ]
 

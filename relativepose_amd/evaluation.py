@@ -82,29 +82,64 @@ def summarize(error_stats):
     return out
 
 
-def _prepare_batch(pipe, batch, device):
+NORMAL_ERR_BINS = 18000            # 0.01 degree bins over 0..180
+
+
+def normal_error_hist(est, given):
+    """Histogram (NORMAL_ERR_BINS bins over 0..180 degrees, float64 counts, on the device) of the angle between two normal maps
+    [n,3,h,w] over the pixels where both are non-zero, i.e. valid in both."""
+    import torch
+    e, g = est.double(), given.double()
+    le, lg = e.norm(dim=1), g.norm(dim=1)
+    both = (le > 0) & (lg > 0)
+    cos = ((e * g).sum(1)[both] / (le[both] * lg[both])).clamp(-1.0, 1.0)
+    return torch.histc(torch.rad2deg(torch.acos(cos)), NORMAL_ERR_BINS, 0.0, 180.0)
+
+
+def hist_quantile(hist, q):
+    """The upper edge, in degrees, of the bin in which the cumulative count of a normal_error_hist reaches the share q (nan if it is empty)."""
+    h = np.asarray(hist, np.float64)
+    if h.sum() <= 0:
+        return float("nan")
+    return float((np.searchsorted(np.cumsum(h), q * h.sum()) + 1) * 180.0 / len(h))
+
+
+def _prepare_batch(pipe, batch, device, normals="given", normal_hist=None):
     """pipe.prepare for a DataLoader-layout batch dict under either keypoint mode: keypoints="given" reads "pts" / "ptw" (injected
     keypoints), keypoints="reference" reads "sift" = [(source detections [n,2], target detections [m,2])] * B in panorama coordinates
     (rputil.map_detections of the SIFT detector's output, rputil.py:152-172) and optionally "kp_seeds" [B][levels]: every level then derives
-    its keypoints from its own feature maps, as evaluation.py:278 does through getMatchingPrimitive."""
+    its keypoints from its own feature maps, as evaluation.py:278 does through getMatchingPrimitive.
+    normals="estimated": the batch's normal maps are not used; the pipeline estimates them from the depth (prepare(rgb, None, depth, ...)).
+    normal_hist: a one-element list that then accumulates normal_error_hist of the estimate against the batch's own "norm"."""
+    if normals not in ("given", "estimated"):
+        raise ValueError("normals must be 'given' or 'estimated'")
+    norm = batch["norm"] if normals == "given" else None
     if getattr(pipe, "keypoints", "given") == "reference":
-        return pipe.prepare(batch["rgb"], batch["norm"], batch["depth"], None, None, device, sift=batch["sift"], kp_seeds=batch.get("kp_seeds"),
-                            rgb_full=batch.get("rgb_full"))
-    return pipe.prepare(batch["rgb"], batch["norm"], batch["depth"], batch["pts"], batch["ptw"], device)
+        st = pipe.prepare(batch["rgb"], norm, batch["depth"], None, None, device, sift=batch["sift"], kp_seeds=batch.get("kp_seeds"),
+                          rgb_full=batch.get("rgb_full"))
+    else:
+        st = pipe.prepare(batch["rgb"], norm, batch["depth"], batch["pts"], batch["ptw"], device)
+    if norm is None and normal_hist is not None and batch.get("norm") is not None:
+        import torch
+        given = torch.from_numpy(np.ascontiguousarray(batch["norm"], dtype=np.float32)).to(device).reshape(st["norm"].shape)
+        hist = normal_error_hist(st["norm"], given)
+        normal_hist[0] = hist if normal_hist[0] is None else normal_hist[0] + hist
+    return st
 
 
-def evaluate_pairs(pipe, batches, device, result_path=None, names=None):
+def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals="given"):
     """The reference's evaluation loop (evaluation.py:203-320) over an iterable of batches
     ``{"rgb","norm","depth","R" [B,2,4,4], "pts" [B,2,N,2], "ptw" [B,2,N]}`` (the DataLoader dict layout, batched, with the
     injected keypoints; with RelativePosePipeline(keypoints="reference") a batch carries "sift" detections instead, _prepare_batch):
     R_gt = R_t inv(R_s) (:185), overlap statistics from the observed clouds (util.parse_data +
-    point_cloud_overlap), the recurrent pipeline on the GPU, then one result record per pair."""
+    point_cloud_overlap), the recurrent pipeline on the GPU, then one result record per pair.
+    normals="estimated": a batch needs no "norm"; the normal maps are estimated from the depth panoramas (util.depth_normals_dev)."""
     from . import util
     stats = []
     k = 0
     for batch in batches:
         B = batch["rgb"].shape[0]
-        st = _prepare_batch(pipe, batch, device)
+        st = _prepare_batch(pipe, batch, device, normals)
         pose, status, _ = pipe.run(st)
         pose = pose.cpu().numpy()
         pcs, valid = util.depth2pc_dev(st["depth"], pipe.dataset)
@@ -378,7 +413,7 @@ def evaluate_completion(batches, net, device, dataset, mask_method, seed=0, with
 
 
 def evaluate_pairs_sharded(pipe, batches, device, result_path=None, names=None, rank=0, world=1, resume=True, round_batches=None,
-                           record_fn=None, depth=2):
+                           record_fn=None, depth=2, normals="given", normal_hist=None):
     """`evaluate_pairs` over `world` ranks (one process per GPU, torch.distributed initialised by the caller:
     distributed.init_from_env).  Every rank receives the same `batches` (a sequence of the DataLoader-layout dicts, B pairs each);
     of every global batch rank r takes the contiguous block distributed.shard_range(B_todo, r, world) -- BatchNorm groups are scan
@@ -391,7 +426,8 @@ def evaluate_pairs_sharded(pipe, batches, device, result_path=None, names=None, 
     A batch may be a dict of arrays or a lazy provider with `.size` and `.take(indices)` (SyntheticBatch): a rank then only
     materialises its own pairs.
     record_fn(sub_batch, local_indices, poses_host, k0) -> list of records (sub_batch = the rank's pairs of the global batch, in the
-    order of local_indices): override for callers with their own statistics (tests)."""
+    order of local_indices): override for callers with their own statistics (tests).
+    normals / normal_hist: as _prepare_batch (normal_hist accumulates this rank's pairs only)."""
     import os
     import torch
     import torch.distributed as dist
@@ -428,7 +464,7 @@ def evaluate_pairs_sharded(pipe, batches, device, result_path=None, names=None, 
             i, first = chunk[mine[q]]
             b = _batch_take(batches[i], local[mine[q]])
             subs[q] = b
-            return _prepare_batch(pipe, b, device)
+            return _prepare_batch(pipe, b, device, normals, normal_hist)
 
         def on_result(q, pose, st):
             # records of this rank's pairs of batch q, built as soon as the batch is complete (the other in-flight batch keeps the GPU busy)
@@ -540,6 +576,10 @@ def _cli_parser_completion():
     ap.add_argument("--completion-eval", action="store_true",
                     help="the losses of the reference's validation pass instead of poses (mainPanoCompletion2view.py:457-602): one JSON line "
                          "with metric = completion_loss and, per input type, errG_rgb / _n / _d / _s and loss_fl_pos / _neg")
+    ap.add_argument("--normals", choices=["given", "estimated"], default="given",
+                    help="--method ours (with --completion 0 / 1 and either --keypoint-mode): estimated = the views' normal maps are not "
+                         "read but estimated from the depth panoramas on the GPU (util.depth_normals_dev); the JSON line gains normals, "
+                         "normal_err_deg_median and normal_err_deg_p90 (the angle to the given normals over the pixels valid in both)")
     return ap
 
 
@@ -554,6 +594,10 @@ def main(argv=None):
     import sys
     import time
     args = _cli_parser_completion().parse_args(argv)
+
+    if args.normals == "estimated" and (args.descriptor_eval or args.completion_eval or args.method != "ours"):
+        raise SystemExit("--normals estimated applies to --method ours (the pose evaluation): the baselines and the descriptor / completion "
+                         "metrics do not read the views' normal maps as an input of the pipeline")
 
     if args.descriptor_eval:
         if args.gpus > 1:
@@ -651,15 +695,26 @@ def main(argv=None):
         D.barrier(world)
         t0 = time.perf_counter()
         n0 = D.COLLECTIVES["all_gather"]
+        nhist = [None] if args.normals == "estimated" else None
         stats = evaluate_pairs_sharded(pipe, batches, dev, result_path=path, rank=rank, world=world, resume=not args.rm,
-                                       round_batches=args.round_batches)
+                                       round_batches=args.round_batches, normals=args.normals, normal_hist=nhist)
         torch.cuda.synchronize()
         D.barrier(world)
         dt = time.perf_counter() - t0
+        if nhist is not None:
+            hist = nhist[0] if nhist[0] is not None else torch.zeros(NORMAL_ERR_BINS, dtype=torch.float64, device=dev)
+            if world > 1:
+                import torch.distributed as dist
+                hist = hist if dist.get_backend() == "nccl" else hist.cpu()
+                dist.all_reduce(hist)
+            hist = hist.cpu().numpy()
         if rank == 0:
-            print(json.dumps({"pairs": len(stats), "seconds": dt, "pairs_per_s_incl_host_rendering": len(stats) / dt, "n_gpus": world,
-                              "pose_all_gathers": D.COLLECTIVES["all_gather"] - n0, "result_file": path, "dataset": ds,
-                              "stats": summarize(stats)}), flush=True)
+            line = {"pairs": len(stats), "seconds": dt, "pairs_per_s_incl_host_rendering": len(stats) / dt, "n_gpus": world,
+                    "pose_all_gathers": D.COLLECTIVES["all_gather"] - n0, "result_file": path, "dataset": ds,
+                    "stats": summarize(stats)}
+            if nhist is not None:
+                line.update(normals="estimated", normal_err_deg_median=hist_quantile(hist, 0.5), normal_err_deg_p90=hist_quantile(hist, 0.9))
+            print(json.dumps(line), flush=True)
         if world > 1:
             import torch.distributed as dist
             dist.destroy_process_group()

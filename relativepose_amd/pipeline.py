@@ -63,6 +63,9 @@ class RelativePosePipeline:
     def prepare(self, rgb, norm, depth, pts, ptw, device, keep_host=False, sift=None, kp_seeds=None, rgb_full=None):
         """Host arrays (dataset dict layout: rgb/norm [B,2,3,h,4h], depth [B,2,h,4h] f32; pts [B,2,N,2],
         ptw [B,2,N] f64) -> device-resident state.  Not part of the timed region.
+        norm=None: the views come without normal maps; they are estimated on the device from the uploaded depth with the pipeline's dataset
+        convention (util.depth_normals_dev), and with keep_host=True upload_inputs re-estimates them behind the depth copy
+        instead of uploading any.
         keypoints="reference": pts / ptw are ignored (None); sift = [(source detections [n,2], target detections [m,2])] * B in panorama
         coordinates (rputil.map_detections), kp_seeds [B][alter_steps] = the np.random seed of pair b's getKeypoint call at each level
         (default: 7919 * b + level).  sift="detect": the detections come from the HIP SIFT detector run on the batch's own views
@@ -94,8 +97,12 @@ class RelativePosePipeline:
         t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)
         st = {"B": B, "h": h, "N": N}
         st["rgb"] = t(rgb.reshape(2 * B, 3, h, w), torch.float32)
-        st["norm"] = t(norm.reshape(2 * B, 3, h, w), torch.float32)
+        if norm is not None:
+            st["norm"] = t(norm.reshape(2 * B, 3, h, w), torch.float32)
         st["depth"] = t(depth.reshape(2 * B, h, w), torch.float32)
+        if norm is None:
+            st["norm"] = util.depth_normals_dev(st["depth"], self.dataset)[0]
+            st["normals_dataset"] = self.dataset         # upload_inputs: the normals follow the depth copy
         st["pts"] = t(pts.reshape(2 * B, N, 2), torch.float64)
         st["npts"] = t(npts.reshape(2 * B), torch.int32)
         st["w_s"] = t(ptw[:, 0], torch.float64)
@@ -110,8 +117,8 @@ class RelativePosePipeline:
         st["f"] = torch.empty(2 * B, self.net.out_channels, h, w, dtype=torch.float32, device=device)
         if keep_host:      # pinned host copies of the per-batch inputs, for upload_inputs (PCIe-inclusive timing)
             st["host"] = {k: torch.from_numpy(np.ascontiguousarray(a)).to(dt).pin_memory() for k, a, dt in (
-                ("rgb", rgb.reshape(2 * B, 3, h, w), torch.float32), ("norm", norm.reshape(2 * B, 3, h, w), torch.float32),
-                ("depth", depth.reshape(2 * B, h, w), torch.float32), ("pts", pts.reshape(2 * B, N, 2), torch.float64))}
+                ("rgb", rgb.reshape(2 * B, 3, h, w), torch.float32), ("norm", None if norm is None else norm.reshape(2 * B, 3, h, w), torch.float32),
+                ("depth", depth.reshape(2 * B, h, w), torch.float32), ("pts", pts.reshape(2 * B, N, 2), torch.float64)) if a is not None}
         return st
 
     def _prepare_reference(self, rgb, norm, depth, device, keep_host, sift, kp_seeds):
@@ -134,8 +141,12 @@ class RelativePosePipeline:
         t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)
         st = {"B": B, "h": h, "N": L}
         st["rgb"] = t(rgb.reshape(2 * B, 3, h, w), torch.float32)
-        st["norm"] = t(norm.reshape(2 * B, 3, h, w), torch.float32)
+        if norm is not None:
+            st["norm"] = t(norm.reshape(2 * B, 3, h, w), torch.float32)
         st["depth"] = t(depth.reshape(2 * B, h, w), torch.float32)
+        if norm is None:
+            st["norm"] = util.depth_normals_dev(st["depth"], self.dataset)[0]
+            st["normals_dataset"] = self.dataset         # upload_inputs: the normals follow the depth copy
         st["kp"] = [rputil.upload_keypoint_tables(tb, device, L) for tb in tabs]
         nb = max(_lib.lib().relpose_keypoints_reference_workspace_bytes(max(tb["nq"], 1), h, w, tb["topk"]) for tb in tabs)
         st["kp_ws"] = torch.empty(nb, dtype=torch.uint8, device=device)
@@ -144,8 +155,8 @@ class RelativePosePipeline:
         st["f"] = torch.empty(2 * B, self.net.out_channels, h, w, dtype=torch.float32, device=device)
         if keep_host:
             st["host"] = {k: torch.from_numpy(np.ascontiguousarray(a)).to(dt).pin_memory() for k, a, dt in (
-                ("rgb", rgb.reshape(2 * B, 3, h, w), torch.float32), ("norm", norm.reshape(2 * B, 3, h, w), torch.float32),
-                ("depth", depth.reshape(2 * B, h, w), torch.float32))}
+                ("rgb", rgb.reshape(2 * B, 3, h, w), torch.float32), ("norm", None if norm is None else norm.reshape(2 * B, 3, h, w), torch.float32),
+                ("depth", depth.reshape(2 * B, h, w), torch.float32)) if a is not None}
         return st
 
     def _level_keypoints(self, st, f, step):
@@ -174,11 +185,15 @@ class RelativePosePipeline:
             with torch.cuda.stream(ms):
                 for k, src in st["host"].items():
                     st[k].copy_(src, non_blocking=True)
+                if "normals_dataset" in st:             # prepare(norm=None): no normals cross PCIe, they are estimated behind the depth copy
+                    util.depth_normals_dev(st["depth"], st["normals_dataset"], out=st["norm"])
             return
         copy_stream.wait_stream(ms)
         with torch.cuda.stream(copy_stream):
             for k, src in st["host"].items():
                 st[k].copy_(src, non_blocking=True)
+            if "normals_dataset" in st:
+                util.depth_normals_dev(st["depth"], st["normals_dataset"], out=st["norm"])
         ms.wait_stream(copy_stream)
 
     def run_interleaved(self, states):

@@ -108,6 +108,33 @@ def pano2pc_dev(depth, dataset):
     return pc, valid
 
 
+def depth_normals_dev(depth, dataset, radius=3, gate_scale=3.0, min_neighbors=6, stages=False, out=None):
+    """depth [n,h,4h] f32 CUDA (0 = no data) -> (normal [n,3,h,4h] f32, valid [n,h,4h] uint8): one normal per panorama pixel from the
+    covariance of the unprojected points of its (2 radius + 1)^2 window (relpose_depth_normals; the contract is DESIGN.md §4.12).
+    stages=True: also (count [n,h,4h] i32, moments [n,9,h,4h] f32).  out: an existing [n,3,h,4h] f32 tensor to write the normals into.
+    Only enqueues on the current stream."""
+    import ctypes as C
+    import torch
+    _lib.require_gpu()
+    n, h, w = depth.shape
+    assert w == 4 * h and depth.dtype == torch.float32 and depth.is_cuda
+    depth = depth.contiguous()
+    dev = depth.device
+    if out is None:
+        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
+    assert out.shape == (n, 3, h, w) and out.dtype == torch.float32 and out.is_contiguous() and out.device == dev
+    valid = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
+    count = torch.empty(n, h, w, dtype=torch.int32, device=dev) if stages else None
+    moments = torch.empty(n, 9, h, w, dtype=torch.float32, device=dev) if stages else None
+    a = _lib.DepthNormalsArgs()
+    a.struct_size = C.sizeof(a)
+    a.n_views, a.h, a.dataset, a.radius, a.min_neighbors, a.gate_scale = n, h, dataset_id(dataset), int(radius), int(min_neighbors), float(gate_scale)
+    a.depth, a.normal, a.valid, a.count, a.moments = _lib.ptr(depth), _lib.ptr(out), _lib.ptr(valid), _lib.ptr(count), _lib.ptr(moments)
+    a.stream = _lib.stream_ptr()
+    _lib.check(_lib.lib().relpose_depth_normals(C.byref(a)), "relpose_depth_normals")
+    return (out, valid, count, moments) if stages else (out, valid)
+
+
 def sample_primitives_dev(f, feat_off, obs_norm, obs_depth, pts, npts, mask_method, dataset, compose=0):
     """f [n,cf,h,4h] net output, obs_norm [n,3,h,4h], obs_depth [n,h,4h] f32, pts [n,N,2] f64, npts [n] i32
     -> pc [n,N,3] f64, normal [n,N,3] f64, feat [n,N,32] f32.  compose: 0 = evaluation.py:250-251, 1 = rpmodule.py:633-634."""
@@ -157,6 +184,21 @@ def Pano2PointCloud(depth, dataList):
     pc, valid = pano2pc_dev(d, dataList)
     pc, valid = pc[0].cpu().numpy(), valid[0].cpu().numpy().astype(bool)
     return pc[:, valid]
+
+
+def depth_normals(depth, dataList, radius=3, gate_scale=3.0, min_neighbors=6):
+    """Normal maps for depth panoramas that come without one (the reference's loaders read them from a normal/ folder,
+    datasets/SUNCG.py:300-313): depth numpy [h,4h] -> [3,h,4h], or [B,2,h,4h] -> [B,2,3,h,4h], float32, the dataset dict's `norm` layout;
+    (0,0,0) where no normal could be estimated."""
+    import torch
+    dev = _lib.require_gpu()
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    if d.ndim not in (2, 4):
+        raise ValueError("depth_normals takes depth [h,4h] or [B,2,h,4h]")
+    h, w = d.shape[-2:]
+    nrm, _ = depth_normals_dev(torch.from_numpy(d.reshape(-1, h, w)).to(dev), dataList, radius, gate_scale, min_neighbors)
+    nrm = nrm.cpu().numpy()
+    return nrm[0] if d.ndim == 2 else nrm.reshape(d.shape[0], 2, 3, h, w)
 
 
 # ---- evaluation-side statistics (SURVEY §8f f3) ---------------------------------------------------------------
