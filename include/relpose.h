@@ -779,6 +779,69 @@ typedef struct RelposeDepthNormalsArgs {
 } RelposeDepthNormalsArgs;
 int relpose_depth_normals(const RelposeDepthNormalsArgs* args);
 
+/* -------------------------------------------------------------------- skybox panoramas from posed perspective RGB-D frames
+ * The reference's ScanNet loader reads every frame twice (datasets/ScanNet.py:211-230): the 480x640 frames (obs_depth/, obs_rgb/) and a
+ * 160x640 panorama whose kinect window holds the same data; the tool that made the second from the first was never published, the geometry
+ * that ties them together was (util.depth2pc :499-521, reproj_helper :537-749).  relpose_frames_to_pano splats one or several posed frames
+ * per view into the four-face panorama, with occlusion handled.  The contract is the project's own (tests/panorama_model.py
+ * restates it in numpy).  Three launches behind the workspace clear, enqueued on `stream`; invalid arguments return RELPOSE_EINVAL before
+ * anything is enqueued.  The geometry is float64, every operation rounded on its own; every accumulator is an integer, so the result does
+ * not depend on the order in which points arrive: it is repeatable bit for bit, and a view's result does not depend on the batch around it.
+ *
+ *   depth            [n_views, n_frames, frame_h, frame_w] f32; a value <= 0 or a non-finite one means no data
+ *   rgb              [n_views, n_frames, frame_h, frame_w, 3] u8
+ *   scale            [n_views, n_frames, 2] f64: (sx, sy) = (2 fx / frame_w, 2 fy / frame_h); ScanNet's are (0.8921875 * 2, 1.1895 * 2).  The
+ *                    principal point is the frame centre: an off-centre principal point and lens distortion are not modelled
+ *   pose             [n_views, n_frames, 4, 4] f64 row-major, frame -> panorama; NULL = identity
+ *   unprojection     pixel (row r, column c), depth z (as f64): x = ((c / frame_w - 0.5) * 2 * z) / sx, y = ((0.5 - r / frame_h) * 2 * z) / sy,
+ *                    p = (x, y, -z), then q_a = ((T_a0 x + T_a1 y) + T_a2 (-z)) + T_a3 when there is a pose
+ *   projection       reproj_helper's rule: for slot = 0..3, (X, Y, Z) = Rs[k]^T q with k = slot (suncg) / (slot - 1) % 4 (matterport,
+ *                    scannet); xn = X / (|Z| + 1e-32), yn = Y / (|Z| + 1e-32); the slot is taken when Z < 0, |xn| < 1, |yn| < 1 (the first
+ *                    such slot; the strict tests make the faces disjoint); column = slot h + clip(rint((xn + 1) * 0.5 * h), 0, h - 1),
+ *                    row = clip(rint((1 - yn) * 0.5 * h), 0, h - 1), rint rounding half to even; face depth d = (float)(-Z)
+ *   dropped          points on no face, points outside box, points with d >= 32768
+ *   box              y0, y1, x0, x1 in panorama pixels (half open), or all -1 for none; 0 <= y0 <= y1 <= h, 0 <= x0 <= x1 <= 4h
+ *   pass 1           zmin = min d over all points of all frames of the view on the pixel
+ *   pass 2           a point is accepted when d <= zmin + zmin * gate (f32, two roundings); it adds 1 to count, llrint((double)d * 65536.0)
+ *                    to sum_z and its three bytes to sum_rgb
+ *   pass 3           out_depth = (float)((double)sum_z / (double)count / 65536.0); per channel q = (2 sum + count) / (2 count) in integers,
+ *                    out_rgb = (float)q / 255.0f; out_valid = count > 0; a pixel without accepted points is 0 everywhere
+ *   out_depth        [n_views, h, 4h] f32;  out_rgb [n_views, 3, h, 4h] f32;  out_valid [n_views, h, 4h] u8
+ *   zmin, count,     optional copies of the accumulators: zmin [n_views, h, 4h] u32 (the bits of the f32 minimum, 0 on an empty pixel),
+ *   sum_z, sum_rgb   count [n_views, h, 4h] u32, sum_z [n_views, h, 4h] u64, sum_rgb [n_views, 3, h, 4h] u32
+ *   limits           h even, 2..8192; n_frames >= 1; n_views * n_frames <= 65535; n_frames * frame_h * frame_w <= 2^24 (sum_rgb is u32);
+ *                    gate finite, >= 0 (0.05 is the library's default); frame_h * frame_w = 0 is legal and gives an empty panorama;
+ *                    a launch holds fewer than 2^32 threads: n_views * n_frames * 256 * ceil(frame_h / 16) * ceil(frame_w / 16) < 2^32 and
+ *                    n_views * h * 4h + 255 < 2^32
+ *   workspace        relpose_frames_to_pano_workspace_bytes(n_views, h) bytes (0 for invalid sizes), 8-byte aligned (sum_z lies at its base) */
+typedef struct RelposeFramesToPanoArgs {
+    uint32_t struct_size;       /* sizeof(RelposeFramesToPanoArgs) as the caller compiled it */
+    int32_t n_views;
+    int32_t n_frames;
+    int32_t frame_h;
+    int32_t frame_w;
+    int32_t h;
+    int32_t dataset;
+    float gate;
+    int32_t box[4];
+    const float* depth;
+    const uint8_t* rgb;
+    const double* scale;
+    const double* pose;
+    float* out_depth;
+    float* out_rgb;
+    uint8_t* out_valid;
+    uint32_t* zmin;
+    uint32_t* count;
+    uint64_t* sum_z;
+    uint32_t* sum_rgb;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeFramesToPanoArgs;
+size_t relpose_frames_to_pano_workspace_bytes(int32_t n, int32_t h);
+int relpose_frames_to_pano(const RelposeFramesToPanoArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

@@ -167,6 +167,15 @@ class DepthNormalsArgs(C.Structure):
                 ("count", c_void_p), ("moments", c_void_p), ("stream", c_void_p)]
 
 
+class FramesToPanoArgs(C.Structure):
+    """RelposeFramesToPanoArgs (include/relpose.h): the argument block of relpose_frames_to_pano."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_views", c_int), ("n_frames", c_int), ("frame_h", c_int), ("frame_w", c_int), ("h", c_int),
+                ("dataset", c_int), ("gate", C.c_float), ("box", c_int * 4), ("depth", c_void_p), ("rgb", c_void_p), ("scale", c_void_p),
+                ("pose", c_void_p), ("out_depth", c_void_p), ("out_rgb", c_void_p), ("out_valid", c_void_p), ("zmin", c_void_p),
+                ("count", c_void_p), ("sum_z", c_void_p), ("sum_rgb", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("stream", c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -217,6 +226,8 @@ SIGNATURES = {
     "relpose_contrast_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
     "relpose_contrast_loss": (c_int, [C.POINTER(ContrastLossArgs)]),
     "relpose_depth_normals": (c_int, [C.POINTER(DepthNormalsArgs)]),
+    "relpose_frames_to_pano_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "relpose_frames_to_pano": (c_int, [C.POINTER(FramesToPanoArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

@@ -156,6 +156,42 @@ def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals=
     return stats
 
 
+def evaluate_from_frames(pipe, batches, device, Hf=480, Wf=640):
+    """The pose evaluation from perspective frames alone, next to the same pairs' directly rendered panoramas: for every SyntheticBatch
+    the pairs' rooms are rendered as one Hf x Wf frame per view (synth.render_frames: identity frame pose, util.SCANNET_FRAME_SCALE), the
+    panoramas are built and their normals estimated on the GPU (RelativePosePipeline.prepare_frames) and the recurrent
+    pipeline runs on them; the second route is prepare(rgb, None, depth, ...) on the rendered panoramas, so that the frames are the only
+    difference.  Returns (records from frames, records from the rendered panoramas, relative depth errors of the built panorama against the
+    rendered one over the pixels of the observed box that have data in both, float64 numpy)."""
+    from . import synth, util
+    recs_f, recs_d, errs = [], [], []
+    y0, y1, x0, x1 = synth.observed_box(pipe.mask_method, 160)
+    k = 0
+    for sb in batches:
+        batch = sb.take(range(sb.size))
+        B = batch["rgb"].shape[0]
+        fr = [synth.render_frames(None, batch["R"][b], synth.room_half(sb.seed + b), Hf, Wf) for b in range(B)]
+        depth_full = np.stack([f[0][:, 0] for f in fr])
+        rgb_full = np.stack([np.moveaxis(f[1][:, 0], -1, 1) for f in fr])
+        st_f = pipe.prepare_frames(rgb_full, depth_full, batch["pts"], batch["ptw"], device)
+        pose_f = pipe.run(st_f)[0].cpu().numpy()
+        st_d = pipe.prepare(batch["rgb"], None, batch["depth"], batch["pts"], batch["ptw"], device)
+        pose_d = pipe.run(st_d)[0].cpu().numpy()
+        df, dd = st_f["depth"][:, y0:y1, x0:x1].double(), st_d["depth"][:, y0:y1, x0:x1].double()
+        both = (df > 0) & (dd > 0)
+        errs.append(((df - dd).abs() / dd.clamp(min=1e-12))[both].cpu().numpy())
+        pcs, valid = util.depth2pc_dev(st_d["depth"], pipe.dataset)
+        pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
+        for b in range(B):
+            R_gt_44 = np.matmul(batch["R"][b, 1], np.linalg.inv(batch["R"][b, 0]))
+            pc_src, pc_tgt = pcs[2 * b][valid[2 * b]], pcs[2 * b + 1][valid[2 * b + 1]]
+            ov, cam_dist, pc_dist, pc_nn = util.point_cloud_overlap(pc_src, pc_tgt, R_gt_44)
+            for recs, pose in ((recs_f, pose_f), (recs_d, pose_d)):
+                recs.append(result_record(f"pair{k}/src", f"pair{k}/tgt", pose[b], R_gt_44, pc_src, ov, pc_dist, cam_dist, pc_nn))
+            k += 1
+    return recs_f, recs_d, np.concatenate(errs) if errs else np.zeros(0)
+
+
 class SyntheticBatch:
     """A global batch of `size` seeded synthetic scan pairs (synth.make_pairs / make_keypoints conventions: pair b of the batch comes from
     seed + b) that materialises only the pairs a rank asks for -- evaluate_pairs_sharded hands every rank the same batch list, and a rank
@@ -580,6 +616,11 @@ def _cli_parser_completion():
                     help="--method ours (with --completion 0 / 1 and either --keypoint-mode): estimated = the views' normal maps are not "
                          "read but estimated from the depth panoramas on the GPU (util.depth_normals_dev); the JSON line gains normals, "
                          "normal_err_deg_median and normal_err_deg_p90 (the angle to the given normals over the pixels valid in both)")
+    ap.add_argument("--from-frames", action="store_true",
+                    help="--method ours --dataset scannet: the pairs enter as 480x640 perspective RGB-D frames alone; the panoramas are built "
+                         "from them on the GPU (util.frames_to_pano_dev) and their normals estimated there; the JSON line gains "
+                         "pano_depth_err_median / pano_depth_err_p90 (relative, against the directly rendered panoramas inside the kinect "
+                         "box) and the pose statistics of both routes (stats_from_frames, stats_rendered)")
     return ap
 
 
@@ -598,6 +639,34 @@ def main(argv=None):
     if args.normals == "estimated" and (args.descriptor_eval or args.completion_eval or args.method != "ours"):
         raise SystemExit("--normals estimated applies to --method ours (the pose evaluation): the baselines and the descriptor / completion "
                          "metrics do not read the views' normal maps as an input of the pipeline")
+
+    if args.from_frames:
+        if args.descriptor_eval or args.completion_eval or args.method != "ours" or args.dataset != "scannet" or args.keypoint_mode != "given":
+            raise SystemExit("--from-frames applies to --method ours --dataset scannet with given keypoints: the perspective frames are "
+                             "the ScanNet loader's (datasets/ScanNet.py:211-230)")
+        if args.gpus > 1:
+            raise SystemExit("--from-frames runs on one GPU (--gpus 1): it is not sharded")
+        import torch
+        from types import SimpleNamespace
+        from . import _lib, params, weights
+        from .model import SCNet
+        from .pipeline import RelativePosePipeline
+        dev = _lib.require_gpu()
+        ds, mm, S = "scannet", "kinect", 21
+        net = SCNet(SimpleNamespace(batchnorm=1, useTanh=0, skipLayer=1, outputType="rgbdnsf", snumclass=S))
+        net.load_state_dict(weights.make_state_dict(7, S))
+        net.set_precision(args.precision)
+        pipe = RelativePosePipeline(net, ds, mm, params.final_params(ds), completion=args.completion)
+        bs = min(args.batch, 32)
+        batches = [SyntheticBatch(min(bs, args.pairs - k), args.seed + k, ds, mm, args.keypoints) for k in range(0, args.pairs, bs)]
+        t0 = time.perf_counter()
+        recs_f, recs_d, errs = evaluate_from_frames(pipe, batches, dev)
+        torch.cuda.synchronize()
+        q = lambda p: float(np.quantile(errs, p)) if len(errs) else float("nan")
+        print(json.dumps({"pairs": len(recs_f), "seconds": time.perf_counter() - t0, "dataset": ds, "from_frames": True, "normals": "estimated",
+                          "pano_depth_err_median": q(0.5), "pano_depth_err_p90": q(0.9), "stats_from_frames": summarize(recs_f),
+                          "stats_rendered": summarize(recs_d)}), flush=True)
+        return
 
     if args.descriptor_eval:
         if args.gpus > 1:

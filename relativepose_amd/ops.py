@@ -39,6 +39,7 @@ Operator                    replaces (reference file:line)
   completion_loss           the L1 and cross-entropy sums of the validation pass, mainPanoCompletion2view.py:549-567 (one pass over the output)
   contrast_loss             the sums behind contrast_loss, mainPanoCompletion2view.py:429-455 (batched over pairs)
   depth_normals             the normal/ maps the loaders read from disk, datasets/SUNCG.py:300-313 (estimated from the depth panoramas)
+  frames_to_pano            the depth/ and rgb/ panoramas the ScanNet loader reads next to its frames, datasets/ScanNet.py:211-230 (built from the frames)
   affinity_topk             rpmodule.py:342-379
   match_pairs               RelativePoseEstimation_helper, rpmodule.py:317-508
 """
@@ -95,6 +96,10 @@ _lib.define("contrast_loss(Tensor f, int feat_off, int channels, Tensor idx_src,
             "float margin=0.5) -> (Tensor, Tensor, Tensor, Tensor)")
 # depth f32 [n,h,4h] (0 = no data) -> normal f32 [n,3,h,4h], valid u8 [n,h,4h]
 _lib.define("depth_normals(Tensor depth, int dataset, int radius=3, float gate_scale=3.0, int min_neighbors=6) -> (Tensor, Tensor)")
+# depth f32 [n,F,Hf,Wf], rgb u8 [n,F,Hf,Wf,3], scale f64 [n,F,2], pose f64 [n,F,4,4] (optional); box = (y0,y1,x0,x1) or empty for none
+# -> rgb f32 [n,3,h,4h], depth f32 [n,h,4h], valid u8 [n,h,4h]
+_lib.define("frames_to_pano(Tensor depth, Tensor rgb, Tensor scale, Tensor? pose, int dataset, int h=160, int[] box=[], float gate=0.05) "
+            "-> (Tensor, Tensor, Tensor)")
 _lib.define("affinity_topk(Tensor feat_s, Tensor weight_s, Tensor feat_t, Tensor weight_t, Tensor ns, Tensor nt, "
             "float[] params, int topK, bool want_wij) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("match_pairs(Tensor pc_s, Tensor normal_s, Tensor feat_s, Tensor weight_s, Tensor pc_t, Tensor normal_t, "
@@ -239,6 +244,10 @@ def _depth_normals(depth, dataset, radius=3, gate_scale=3.0, min_neighbors=6):
     return _util.depth_normals_dev(depth, _INV_DATASET[int(dataset)], int(radius), float(gate_scale), int(min_neighbors))
 
 
+def _frames_to_pano(depth, rgb, scale, pose, dataset, h=160, box=(), gate=0.05):
+    return _util.frames_to_pano_dev(depth, rgb, scale, pose, _INV_DATASET[int(dataset)], int(h), tuple(box) if len(box) else None, float(gate))
+
+
 def _affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     wij, cj, cw, keff = _rp.affinity_topk(feat_s.contiguous(), weight_s.contiguous(), feat_t.contiguous(), weight_t.contiguous(),
                                           ns.contiguous(), nt.contiguous(), _para(params, topK), want_wij=bool(want_wij))
@@ -260,7 +269,8 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("sift_detect", _sift_detect), ("fast_global_registration", _fast_global_registration),
                    ("global_registration", _global_registration), ("colored_icp", _colored_icp), ("color_registration", _color_registration),
                    ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank),
-                   ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals)):
+                   ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals),
+                   ("frames_to_pano", _frames_to_pano)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -379,6 +389,12 @@ def _m_depth_normals(depth, dataset, radius=3, gate_scale=3.0, min_neighbors=6):
     return depth.new_empty(n, 3, h, w, dtype=torch.float32), depth.new_empty(n, h, w, dtype=torch.uint8)
 
 
+def _m_frames_to_pano(depth, rgb, scale, pose, dataset, h=160, box=(), gate=0.05):
+    n = depth.shape[0]
+    return (depth.new_empty(n, 3, h, 4 * h, dtype=torch.float32), depth.new_empty(n, h, 4 * h, dtype=torch.float32),
+            depth.new_empty(n, h, 4 * h, dtype=torch.uint8))
+
+
 def _m_affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     B, ns_max, nt_max = feat_s.shape[0], feat_s.shape[1], feat_t.shape[1]
     wij = feat_s.new_empty(B, ns_max, nt_max, dtype=torch.float32) if want_wij else feat_s.new_empty(0)
@@ -397,9 +413,11 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("match_pairs", _m_match_pairs), ("sift_detect", _m_sift_detect), ("fast_global_registration", _m_fast_global_registration),
                    ("global_registration", _m_global_registration), ("colored_icp", _m_colored_icp), ("color_registration", _m_color_registration),
                    ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank),
-                   ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals)):
+                   ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals),
+                   ("frames_to_pano", _m_frames_to_pano)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
-       "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals")
+       "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals",
+       "frames_to_pano")

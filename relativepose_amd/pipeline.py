@@ -121,6 +121,40 @@ class RelativePosePipeline:
                 ("depth", depth.reshape(2 * B, h, w), torch.float32), ("pts", pts.reshape(2 * B, N, 2), torch.float64)) if a is not None}
         return st
 
+    def prepare_frames(self, rgb_full, depth_full, pts, ptw, device, scale=None, pose=None, box="default", gate=0.05, h=160,
+                       keep_host=False, sift=None, kp_seeds=None):
+        """prepare() from perspective RGB-D frames alone: rgb_full [B,2,3,Hf,Wf] (float in 0..1 or uint8) and depth_full
+        [B,2,Hf,Wf] in the loader layout, or [B,2,F,3,Hf,Wf] and [B,2,F,Hf,Wf] for F posed frames per view; scale (sx, sy) for every frame or
+        [B,2,F,2] (default: util.SCANNET_FRAME_SCALE); pose [B,2,F,4,4] (or [B,2,4,4]) frame -> panorama, None = identity.  The panoramas
+        are built on the device (util.frames_to_pano_dev; box "default" = the pipeline's mask method for scannet, none otherwise) and
+        enter prepare() as views without normal maps, which estimates the normals on the device.  prepare() takes host arrays, so the built
+        rgb and depth make one round trip through host memory on the way (a synchronisation; like prepare() this is not part of the timed
+        region).  With one frame per view rgb_full stays the detector's input of the SIFT 'kinect' branch, as float32 in 0..1, which is what
+        rputil.sift_images quantises: uint8 frames are handed on as x / 255, exact under its (x * 255) -> uint8."""
+        import torch
+        depth_full = np.ascontiguousarray(depth_full, dtype=np.float32)
+        if depth_full.ndim == 4:
+            depth_full = depth_full[:, :, None]
+        B, _, F, Hf, Wf = depth_full.shape
+        rgb_in = np.asarray(rgb_full)
+        rgb_f = rgb_in if rgb_in.ndim == 6 else rgb_in[:, :, None]
+        col = util.frames_uint8(rgb_f)
+        if col.shape != (B, 2, F, Hf, Wf, 3):
+            raise ValueError("prepare_frames: rgb_full does not match depth_full")
+        if box == "default":
+            box = self.mask_method if self.dataset == "scannet" else None
+        sc = np.array(np.broadcast_to(np.asarray(util.SCANNET_FRAME_SCALE if scale is None else scale, np.float64), (B, 2, F, 2)))
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        ps = None if pose is None else t(np.asarray(pose, np.float64).reshape(2 * B, F, 4, 4))
+        rgb, depth, _ = util.frames_to_pano_dev(t(depth_full.reshape(2 * B, F, Hf, Wf)), t(col.reshape(2 * B, F, Hf, Wf, 3)),
+                                                t(sc.reshape(2 * B, F, 2)), ps, self.dataset, h, box, gate)
+        w = 4 * h
+        full = None
+        if rgb_in.ndim == 5:
+            full = rgb_in.astype(np.float32) / np.float32(255) if rgb_in.dtype == np.uint8 else rgb_in
+        return self.prepare(rgb.cpu().numpy().reshape(B, 2, 3, h, w), None, depth.cpu().numpy().reshape(B, 2, h, w), pts, ptw, device,
+                            keep_host=keep_host, sift=sift, kp_seeds=kp_seeds, rgb_full=full)
+
     def _prepare_reference(self, rgb, norm, depth, device, keep_host, sift, kp_seeds):
         """prepare() for keypoints="reference": the feature-independent half of every level's getKeypoint call is drawn here, on the host, in the
         reference's np.random call order (rputil.keypoint_plan) and uploaded as query points + slot tables; one keypoint capacity L for all levels."""

@@ -10,6 +10,8 @@ Nothing in this module touches the GPU or the oracle.
 """
 import numpy as np
 
+from .util import SCANNET_FRAME_SCALE
+
 H, W = 160, 640
 DATASETS = ("suncg", "matterport", "scannet")
 
@@ -113,6 +115,11 @@ def make_pairs(B, seed, dataset="suncg", h=H):
     return {"rgb": rgb, "norm": nrm, "depth": dep, "R": Rp}
 
 
+def room_half(seed):
+    """The half-extents of the room of make_pairs' pair with this seed (render_room's first draw), for render_frames."""
+    return np.random.RandomState(seed).uniform(1.5, 4.0, 3)
+
+
 def make_labels(norm, S):
     """A deterministic per-pixel semantic class for the rendered rooms: norm [..., 3, h, w] (the rendered normals) -> uint8 [..., h, w].
     The dominant axis a of the normal and its sign give 2 a + (n_a < 0) in 0..5, taken modulo S; an all-zero normal (a hole) is class 0."""
@@ -185,6 +192,37 @@ def kinect_frames(rgb, h=H):
     crop = torch.from_numpy(np.ascontiguousarray(rgb[:, :, :, y0:y1, x0:x1], dtype=np.float32)).reshape(2 * B, 3, y1 - y0, x1 - x0)
     full = torch.nn.functional.interpolate(crop, size=(480, 640), mode="bilinear", align_corners=False)
     return full.reshape(B, 2, 3, 480, 640).numpy()
+
+
+def render_frames(rs, poses, half, Hf=480, Wf=640, scale=SCANNET_FRAME_SCALE, frame_poses=None, hole_frac=0.0):
+    """Perspective RGB-D frames of render_room's box room (same walls, same texture), rendered analytically: the ray of frame pixel
+    (r, c) at unit depth is ((c/Wf - .5) 2 / sx, (.5 - r/Hf) 2 / sy, -1) in the frame's camera, the inverse of util.depth2pc's 480x640
+    branch.  poses [V,4,4]: the views' panorama cameras (camera-to-world, render_room's); half: the room half-extents; frame_poses
+    [V][F] 4x4: frame -> panorama (default: one frame per view at the identity, which looks into the kinect face of a scannet /
+    matterport panorama).  rs draws the holes (hole_frac > 0).  Returns depth [V,F,Hf,Wf] float32 (0 = hole) and rgb [V,F,Hf,Wf,3] uint8
+    (the texture quantised like the reference's (x * 255).astype(uint8))."""
+    V = len(poses)
+    if frame_poses is None:
+        frame_poses = [[np.eye(4)] for _ in range(V)]
+    F = len(frame_poses[0])
+    half = np.asarray(half, np.float64)
+    dep = np.zeros((V, F, Hf, Wf), np.float32)
+    rgb = np.zeros((V, F, Hf, Wf, 3), np.uint8)
+    rr, cc = np.meshgrid(np.arange(Hf), np.arange(Wf), indexing="ij")
+    d_cam = np.stack([(cc / Wf - 0.5) * 2 / scale[0], (0.5 - rr / Hf) * 2 / scale[1], -np.ones((Hf, Wf))], -1)
+    for v in range(V):
+        for f in range(F):
+            T = np.asarray(poses[v], np.float64) @ np.asarray(frame_poses[v][f], np.float64)      # frame -> world
+            d_w, tw = d_cam @ T[:3, :3].T, T[:3, 3]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                s = np.where(d_w > 0, (half - tw) / d_w, (-half - tw) / d_w)
+            s[~np.isfinite(s)] = np.inf
+            z = np.min(s, -1)
+            dep[v, f] = z
+            rgb[v, f] = (_texture(tw + z[..., None] * d_w) * 255).astype(np.uint8)
+            if hole_frac > 0:
+                dep[v, f][rs.rand(Hf, Wf) < hole_frac] = 0
+    return dep, rgb
 
 
 def make_match_case(N, seed, inlier=0.6, noise=0.005, Nt=None):

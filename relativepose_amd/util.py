@@ -135,6 +135,89 @@ def depth_normals_dev(depth, dataset, radius=3, gate_scale=3.0, min_neighbors=6,
     return (out, valid, count, moments) if stages else (out, valid)
 
 
+# (sx, sy) of util.depth2pc's 480x640 branch (reference util.py:499-507): x = xn z / sx, y = yn z / sy
+SCANNET_FRAME_SCALE = (0.8921875 * 2, 1.1895 * 2)
+
+
+def frame_scale(fx, fy, Wf, Hf):
+    """(sx, sy) of a pinhole camera with focal lengths fx, fy in pixels and its principal point at the centre of a Wf x Hf frame."""
+    return 2.0 * fx / Wf, 2.0 * fy / Hf
+
+
+def _pano_box(box, h):
+    if box is None:
+        return (-1, -1, -1, -1)
+    if isinstance(box, str):
+        from . import synth
+        return tuple(int(b) for b in synth.observed_box(box, h))
+    y0, y1, x0, x1 = (int(b) for b in box)
+    return y0, y1, x0, x1
+
+
+_pano_ws = {}
+
+
+def frames_to_pano_dev(depth, rgb, scale, pose=None, dataset="scannet", h=160, box="kinect", gate=0.05, normals=False, stages=False, out=None):
+    """Posed perspective RGB-D frames -> four-face skybox panoramas (relpose_frames_to_pano; the contract is DESIGN.md §4.13).
+    depth [n,F,Hf,Wf] f32 CUDA (<= 0 or non-finite = no data), rgb [n,F,Hf,Wf,3] uint8, scale [n,F,2] f64 (sx, sy) or one (sx, sy) pair for
+    every frame, pose [n,F,4,4] f64 frame -> panorama (None = identity).  box: a mask method name (synth.observed_box), (y0,y1,x0,x1) in
+    panorama pixels, or None.  Returns (rgb [n,3,h,4h] f32, depth [n,h,4h] f32, valid [n,h,4h] uint8); normals=True appends the normals of
+    depth_normals_dev on the built depth, stages=True appends (zmin [n,h,4h] i32: the bits of the f32 minimum, count [n,h,4h] i32, sum_z
+    [n,h,4h] i64, sum_rgb [n,3,h,4h] i32).  out: existing (rgb, depth, valid) tensors to write into.  Only enqueues on the current stream."""
+    import ctypes as C
+    import torch
+    _lib.require_gpu()
+    assert depth.dim() == 4 and depth.dtype == torch.float32 and depth.is_cuda
+    n, F, Hf, Wf = depth.shape
+    assert rgb.shape == (n, F, Hf, Wf, 3) and rgb.dtype == torch.uint8 and rgb.device == depth.device
+    dev = depth.device
+    depth, rgb = depth.contiguous(), rgb.contiguous()
+    if not torch.is_tensor(scale):
+        scale = torch.tensor(np.broadcast_to(np.asarray(scale, np.float64), (n, F, 2)).copy(), device=dev)
+    assert scale.shape == (n, F, 2) and scale.dtype == torch.float64 and scale.device == dev
+    scale = scale.contiguous()
+    if pose is not None:
+        assert pose.shape == (n, F, 4, 4) and pose.dtype == torch.float64 and pose.device == dev
+        pose = pose.contiguous()
+    w = 4 * h
+    if out is None:
+        out = (torch.empty(n, 3, h, w, dtype=torch.float32, device=dev), torch.empty(n, h, w, dtype=torch.float32, device=dev),
+               torch.empty(n, h, w, dtype=torch.uint8, device=dev))
+    o_rgb, o_depth, o_valid = out
+    assert o_rgb.shape == (n, 3, h, w) and o_rgb.dtype == torch.float32 and o_rgb.is_contiguous() and o_rgb.device == dev
+    assert o_depth.shape == (n, h, w) and o_depth.dtype == torch.float32 and o_depth.is_contiguous() and o_depth.device == dev
+    assert o_valid.shape == (n, h, w) and o_valid.dtype == torch.uint8 and o_valid.is_contiguous() and o_valid.device == dev
+    st = None
+    if stages:
+        st = (torch.empty(n, h, w, dtype=torch.int32, device=dev), torch.empty(n, h, w, dtype=torch.int32, device=dev),
+              torch.empty(n, h, w, dtype=torch.int64, device=dev), torch.empty(n, 3, h, w, dtype=torch.int32, device=dev))
+    L = _lib.lib()
+    nbytes = L.relpose_frames_to_pano_workspace_bytes(n, h)
+    if nbytes == 0:
+        raise ValueError(f"frames_to_pano: {n} views at h = {h} (h must be even, 2..8192)")
+    key = (dev.index, torch.cuda.current_stream().cuda_stream)
+    ws = _pano_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _pano_ws[key] = ws
+    a = _lib.FramesToPanoArgs()
+    a.struct_size = C.sizeof(a)
+    a.n_views, a.n_frames, a.frame_h, a.frame_w, a.h, a.dataset, a.gate = n, F, Hf, Wf, h, dataset_id(dataset), float(gate)
+    a.box[:] = _pano_box(box, h)
+    a.depth, a.rgb, a.scale, a.pose = _lib.ptr(depth), _lib.ptr(rgb), _lib.ptr(scale), _lib.ptr(pose)
+    a.out_depth, a.out_rgb, a.out_valid = _lib.ptr(o_depth), _lib.ptr(o_rgb), _lib.ptr(o_valid)
+    if stages:
+        a.zmin, a.count, a.sum_z, a.sum_rgb = (_lib.ptr(t) for t in st)
+    a.workspace, a.workspace_bytes, a.stream = _lib.ptr(ws), ws.numel(), _lib.stream_ptr()
+    _lib.check(L.relpose_frames_to_pano(C.byref(a)), "relpose_frames_to_pano")
+    res = (o_rgb, o_depth, o_valid)
+    if normals:
+        res += (depth_normals_dev(o_depth, dataset)[0],)
+    if stages:
+        res += (st,)
+    return res
+
+
 def sample_primitives_dev(f, feat_off, obs_norm, obs_depth, pts, npts, mask_method, dataset, compose=0):
     """f [n,cf,h,4h] net output, obs_norm [n,3,h,4h], obs_depth [n,h,4h] f32, pts [n,N,2] f64, npts [n] i32
     -> pc [n,N,3] f64, normal [n,N,3] f64, feat [n,N,32] f32.  compose: 0 = evaluation.py:250-251, 1 = rpmodule.py:633-634."""
@@ -199,6 +282,36 @@ def depth_normals(depth, dataList, radius=3, gate_scale=3.0, min_neighbors=6):
     nrm, _ = depth_normals_dev(torch.from_numpy(d.reshape(-1, h, w)).to(dev), dataList, radius, gate_scale, min_neighbors)
     nrm = nrm.cpu().numpy()
     return nrm[0] if d.ndim == 2 else nrm.reshape(d.shape[0], 2, 3, h, w)
+
+
+def frames_uint8(rgb_full):
+    """Frames in the loader layout [..., 3, Hf, Wf] (float in 0..1, quantised like the reference's (x * 255).astype(uint8), or uint8)
+    -> uint8 [..., Hf, Wf, 3]."""
+    x = np.asarray(rgb_full)
+    if x.dtype != np.uint8:
+        x = (x * 255).astype(np.uint8)
+    return np.ascontiguousarray(np.moveaxis(x, -3, -1))
+
+
+def frames_to_pano(depth_full, rgb_full, dataList, scale=SCANNET_FRAME_SCALE, pose=None, h=160, box="kinect", gate=0.05):
+    """The panorama version of perspective frames in the loader layout (the reference's ScanNet loader reads both from disk,
+    datasets/ScanNet.py:211-230): depth_full numpy [B,2,Hf,Wf], rgb_full [B,2,3,Hf,Wf] (float in 0..1 or uint8), one frame per view
+    -> (rgb [B,2,3,h,4h], depth [B,2,h,4h], norm [B,2,3,h,4h]) float32, the dataset dict's entries; the normals are depth_normals_dev's
+    on the built depth.  pose: [B,2,4,4] frame -> panorama, or None."""
+    import torch
+    dev = _lib.require_gpu()
+    d = np.ascontiguousarray(depth_full, dtype=np.float32)
+    if d.ndim != 4 or d.shape[1] != 2:
+        raise ValueError("frames_to_pano takes depth_full [B,2,Hf,Wf]")
+    B, _, Hf, Wf = d.shape
+    c = frames_uint8(rgb_full)
+    if c.shape != (B, 2, Hf, Wf, 3):
+        raise ValueError("frames_to_pano takes rgb_full [B,2,3,Hf,Wf]")
+    p = None if pose is None else torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64).reshape(2 * B, 1, 4, 4)).to(dev)
+    rgb, dep, _, nrm = frames_to_pano_dev(torch.from_numpy(d.reshape(2 * B, 1, Hf, Wf)).to(dev), torch.from_numpy(c.reshape(2 * B, 1, Hf, Wf, 3)).to(dev),
+                                          scale, p, dataList, h, box, gate, normals=True)
+    w = 4 * h
+    return rgb.cpu().numpy().reshape(B, 2, 3, h, w), dep.cpu().numpy().reshape(B, 2, h, w), nrm.cpu().numpy().reshape(B, 2, 3, h, w)
 
 
 # ---- evaluation-side statistics (SURVEY §8f f3) ---------------------------------------------------------------
