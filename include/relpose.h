@@ -842,6 +842,55 @@ typedef struct RelposeFramesToPanoArgs {
 size_t relpose_frames_to_pano_workspace_bytes(int32_t n, int32_t h);
 int relpose_frames_to_pano(const RelposeFramesToPanoArgs* args);
 
+/* -------------------------------------------------------------------- grid-based overlap statistics
+ * The nearest-neighbour statistics of util.point_cloud_overlap (util.py:21-40) for a batch of directed (query cloud, reference cloud, pose)
+ * triples: how many points of the moved query cloud have a reference point within max_dist, and the clouds' closest-pair distance.  The
+ * values are those relpose_nn_dist gives (the same expressions, every operation rounded on its own); the work is not: every cloud gets one
+ * uniform grid (cell edge max_dist (1 + 2^-10)) that all queries naming it share, a query point looks at the 27 cells around it, and a
+ * query without a hit finds its closest pair in a pass over bounding boxes of 256-point tiles that prunes against a running bound.  The
+ * contract is DESIGN.md 4.14; tests/overlap_model.py restates it in numpy.  Four launches behind a 4-byte clear and the upload of the two index arrays, whatever n_queries is.
+ * Only integer atomics (add, min on the bit pattern of a non-negative double): results are repeatable bit for bit, and a query's outputs
+ * do not depend on the batch around it.
+ *
+ *   pc, valid        [n_clouds, n_points, 3] f64 and [n_clouds, n_points] u8 as relpose_depth2pc writes them; valid NULL = all valid
+ *   query_cloud_host, ref_cloud_host   [n_queries] i32 in HOST memory (they are validated before anything touches the device)
+ *   pose             [n_queries, 4, 4] f64 row-major, query cloud -> the reference cloud's frame: q_a = ((T_a0 x + T_a1 y) + T_a2 z) + T_a3
+ *   max_dist         finite, > 0 (the reference uses 0.08)
+ *   d2               (dx dx + dy dy) + dz dz with d = q - r; a pair with a non-finite d2 is never a neighbour
+ *   hits             [n_queries] i32 = #{valid query points : sqrt(min d2 over the valid reference points) < max_dist}
+ *   nn_min           [n_queries] f64 = the minimum of that square root over the valid query points: the closest-pair distance, exact
+ *                    whether or not a point hits; +inf when either cloud has no valid point (or none with finite coordinates)
+ *   n_valid          [n_clouds] i32 = #{valid points}; points with a non-finite coordinate count
+ *   hit              [n_queries, n_points] u8 or NULL: the per-point flag behind hits (0 for an invalid point)
+ *   workspace        relpose_overlap_workspace_bytes(n_clouds, n_points, n_queries) bytes (0 for invalid sizes), 256-byte aligned
+ *   limits           1 <= n_clouds, n_queries; 1 <= n_points <= 2^24; n_queries * ceil(n_points / 256) < 2^31
+ * Returns RELPOSE_EINVAL before the device is touched for a NULL required pointer, a max_dist that is not finite or <= 0, a cloud index
+ * outside 0..n_clouds-1 or sizes outside the limits.  Returns RELPOSE_OVERLAP_EXTENT, with none of the four outputs written, when the
+ * finite points of some cloud span more than 2^20 cells along an axis (the grid keys would not fit).  The call waits for `stream` once, at
+ * its end, to read that flag. */
+#define RELPOSE_OVERLAP_EXTENT (-7)
+typedef struct RelposeOverlapArgs {
+    uint32_t struct_size;       /* sizeof(RelposeOverlapArgs) as the caller compiled it */
+    int32_t n_clouds;
+    int32_t n_points;
+    int32_t n_queries;
+    const double* pc;
+    const uint8_t* valid;
+    const int32_t* query_cloud_host;
+    const int32_t* ref_cloud_host;
+    const double* pose;
+    double max_dist;
+    int32_t* hits;
+    double* nn_min;
+    int32_t* n_valid;
+    uint8_t* hit;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeOverlapArgs;
+size_t relpose_overlap_workspace_bytes(int32_t n_clouds, int32_t n_points, int32_t n_queries);
+int relpose_overlap(const RelposeOverlapArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

@@ -176,6 +176,17 @@ class FramesToPanoArgs(C.Structure):
                 ("stream", c_void_p)]
 
 
+class OverlapArgs(C.Structure):
+    """RelposeOverlapArgs (include/relpose.h): the argument block of relpose_overlap."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_clouds", c_int), ("n_points", c_int), ("n_queries", c_int), ("pc", c_void_p), ("valid", c_void_p),
+                ("query_cloud_host", c_void_p), ("ref_cloud_host", c_void_p), ("pose", c_void_p), ("max_dist", c_double), ("hits", c_void_p),
+                ("nn_min", c_void_p), ("n_valid", c_void_p), ("hit", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("stream", c_void_p)]
+
+
+OVERLAP_EXTENT = -7                 # RELPOSE_OVERLAP_EXTENT
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -228,6 +239,8 @@ SIGNATURES = {
     "relpose_depth_normals": (c_int, [C.POINTER(DepthNormalsArgs)]),
     "relpose_frames_to_pano_workspace_bytes": (c_size_t, [c_int, c_int]),
     "relpose_frames_to_pano": (c_int, [C.POINTER(FramesToPanoArgs)]),
+    "relpose_overlap_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "relpose_overlap": (c_int, [C.POINTER(OverlapArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

@@ -13,8 +13,13 @@ unchanged" is realised by the build's own eval_pairs-style harness).
                           batch is cut into contiguous per-rank blocks, ONE all_gather of the poses per round, rank 0 writes ONE
                           <exp>.result.npy and resumes from an existing one in units of 100 pairs (:129-133, :319-320)
 
-The metrics are host numpy like the reference's (a handful of 3x3 products per pair); the overlap statistics use the
-GPU nearest-neighbour kernel (util.point_cloud_overlap)."""
+  pairs_from_overlap / mine_pairs / save_data_list / load_data_list / SceneBatch
+                          the loaders' dataList ({'base','id_src','id_tgt',...} per split, datasets/SUNCG.py:66,91-93), whose generator
+                          was never published: which pairs of M posed scans overlap, from util.overlap_matrix_dev
+
+The metrics are host numpy like the reference's (a handful of 3x3 products per pair); overlap and pc_nearest of a batch come from one
+grid-based GPU call (util.point_cloud_overlap_dev), bitwise the values of the per-pair brute-force yardstick
+util.point_cloud_overlap."""
 import numpy as np
 
 OVERLAPS = ("0-0.1", "0.1-0.5", "0.5-1.0")       # evaluation.py:68
@@ -127,6 +132,21 @@ def _prepare_batch(pipe, batch, device, normals="given", normal_hist=None):
     return st
 
 
+def _pair_overlap_stats(pcs_dev, valid_dev, R_gts):
+    """overlap and pc_nearest of every pair of a batch from ONE util.point_cloud_overlap_dev call (pcs_dev [2B,P,3], valid_dev [2B,P] on
+    the device, R_gts [B,4,4] host) -> two float64 numpy arrays [B], bitwise util.point_cloud_overlap's values."""
+    from . import util
+    ov, _, _, nn = util.point_cloud_overlap_dev(pcs_dev, valid_dev, np.asarray(R_gts, dtype=np.float64).reshape(-1, 4, 4))
+    return ov.cpu().numpy(), nn.cpu().numpy()
+
+
+def _host_pair_stats(pc_src, pc_tgt, R_gt_44):
+    """cam_dist and pc_dist of util.point_cloud_overlap (util.py:36-39), its host expressions: (cam_dist, pc_dist)."""
+    R = np.ascontiguousarray(R_gt_44, dtype=np.float64)
+    src_trans = np.matmul(R[:3, :3], pc_src.T) + R[:3, 3:4]
+    return np.linalg.norm(R[:3, 3]), np.linalg.norm(src_trans.mean(1) - pc_tgt.T.mean(1))
+
+
 def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals="given"):
     """The reference's evaluation loop (evaluation.py:203-320) over an iterable of batches
     ``{"rgb","norm","depth","R" [B,2,4,4], "pts" [B,2,N,2], "ptw" [B,2,N]}`` (the DataLoader dict layout, batched, with the
@@ -143,11 +163,14 @@ def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals=
         pose, status, _ = pipe.run(st)
         pose = pose.cpu().numpy()
         pcs, valid = util.depth2pc_dev(st["depth"], pipe.dataset)
+        R_gts = [np.matmul(batch["R"][b, 1], np.linalg.inv(batch["R"][b, 0])) for b in range(B)]
+        ovs, nns = _pair_overlap_stats(pcs, valid, R_gts)
         pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
         for b in range(B):
-            R_gt_44 = np.matmul(batch["R"][b, 1], np.linalg.inv(batch["R"][b, 0]))
+            R_gt_44 = R_gts[b]
             pc_src, pc_tgt = pcs[2 * b][valid[2 * b]], pcs[2 * b + 1][valid[2 * b + 1]]
-            ov, cam_dist, pc_dist, pc_nn = util.point_cloud_overlap(pc_src, pc_tgt, R_gt_44)
+            ov, pc_nn = ovs[b], nns[b]
+            cam_dist, pc_dist = _host_pair_stats(pc_src, pc_tgt, R_gt_44)
             nm = names[k] if names is not None else (f"pair{k}/src", f"pair{k}/tgt")
             stats.append(result_record(nm[0], nm[1], pose[b], R_gt_44, pc_src, ov, pc_dist, cam_dist, pc_nn))
             k += 1
@@ -181,11 +204,14 @@ def evaluate_from_frames(pipe, batches, device, Hf=480, Wf=640):
         both = (df > 0) & (dd > 0)
         errs.append(((df - dd).abs() / dd.clamp(min=1e-12))[both].cpu().numpy())
         pcs, valid = util.depth2pc_dev(st_d["depth"], pipe.dataset)
+        R_gts = [np.matmul(batch["R"][b, 1], np.linalg.inv(batch["R"][b, 0])) for b in range(B)]
+        ovs, nns = _pair_overlap_stats(pcs, valid, R_gts)
         pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
         for b in range(B):
-            R_gt_44 = np.matmul(batch["R"][b, 1], np.linalg.inv(batch["R"][b, 0]))
+            R_gt_44 = R_gts[b]
             pc_src, pc_tgt = pcs[2 * b][valid[2 * b]], pcs[2 * b + 1][valid[2 * b + 1]]
-            ov, cam_dist, pc_dist, pc_nn = util.point_cloud_overlap(pc_src, pc_tgt, R_gt_44)
+            ov, pc_nn = ovs[b], nns[b]
+            cam_dist, pc_dist = _host_pair_stats(pc_src, pc_tgt, R_gt_44)
             for recs, pose in ((recs_f, pose_f), (recs_d, pose_d)):
                 recs.append(result_record(f"pair{k}/src", f"pair{k}/tgt", pose[b], R_gt_44, pc_src, ov, pc_dist, cam_dist, pc_nn))
             k += 1
@@ -224,6 +250,116 @@ class SyntheticBatch:
         return out
 
 
+def pairs_from_overlap(frac, base, ids, min_overlap=None):
+    """The pair list of one scene from its directed overlap matrix (host code): frac [M,M] (frac[i,j] = the share of view i's points
+    that view j also sees, util.overlap_matrix_dev), base = the scene's name, ids = the M view ids -> the loaders' dataList entries
+    {'base', 'id_src', 'id_tgt', 'overlap'} (datasets/SUNCG.py:91-93) for i < j, sorted by (i, j); overlap = max(frac[i,j], frac[j,i]),
+    the symmetric value util.point_cloud_overlap reports.  min_overlap: pairs below it are left out (the baselines' rule is 0.1,
+    evaluation.py:190-191)."""
+    f = np.asarray(frac, dtype=np.float64)
+    M = len(ids)
+    if f.shape != (M, M):
+        raise ValueError("pairs_from_overlap takes frac [M,M] and M ids")
+    out = []
+    for i in range(M):
+        for j in range(i + 1, M):
+            ov = float(max(f[i, j], f[j, i]))
+            if min_overlap is not None and ov < min_overlap:
+                continue
+            out.append({'base': base, 'id_src': ids[i], 'id_tgt': ids[j], 'overlap': ov})
+    return out
+
+
+def mine_pairs(depth, R, dataset, base, ids=None, min_overlap=None, max_dist=0.08, device=None):
+    """Which pairs of M posed scans of one scene overlap, and by how much: depth [M,h,4h] float32 panoramas (numpy or a CUDA tensor),
+    R [M,4,4] world -> camera poses (the loaders' convention) -> pairs_from_overlap's entries.  The observed clouds (util.depth2pc_dev),
+    ONE grid-based overlap call over the M (M - 1) directed pairs (util.overlap_matrix_dev) and the host pair list."""
+    import torch
+    from . import _lib, util
+    dev = device if device is not None else _lib.require_gpu()
+    d = depth if isinstance(depth, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(dev)
+    pc, valid = util.depth2pc_dev(d, dataset)
+    frac, _, _ = util.overlap_matrix_dev(pc, valid, R, max_dist)
+    M = d.shape[0]
+    return pairs_from_overlap(frac.cpu().numpy(), base, list(range(M)) if ids is None else list(ids), min_overlap)
+
+
+def save_data_list(path, lists):
+    """Write {split: [entries]} as the object file the reference's loaders read with np.load(path).item()[split]
+    (datasets/SUNCG.py:66).  -> the path written (.npy appended when missing)."""
+    if not path.endswith(".npy"):
+        path += ".npy"
+    np.save(path, {k: list(v) for k, v in lists.items()}, allow_pickle=True)
+    return path
+
+
+def load_data_list(path, split):
+    return np.load(path, allow_pickle=True).item()[split]
+
+
+class SceneBatch:
+    """The take(idx) counterpart of SyntheticBatch whose pairs OVERLAP: `size` pairs mined (mine_pairs) from synth.render_scene scenes of
+    `views` views each, scene after scene (scene s of the batch has seed 7919 * seed + s) in (scene, i, j) order.  balanced: equal
+    numbers from the three overlap buckets instead, taken round-robin (0-0.1, 0.1-0.5, 0.5-1.0, 0-0.1, ...) in that order from as many
+    scenes as it takes -- so that a synthetic summary has populated rows; at most `max_scenes` scenes are rendered, and a bucket that
+    stays short is filled from the others.  The pair list is built on first use (it needs the GPU); `pairs` holds its entries, with
+    'base' = the scene's seed."""
+
+    def __init__(self, size, seed, dataset, mask_method, keypoints, h=160, views=6, balanced=False, max_scenes=64):
+        self.size, self.seed, self.dataset, self.mask_method, self.keypoints, self.h = size, seed, dataset, mask_method, keypoints, h
+        self.views, self.balanced, self.max_scenes = int(views), bool(balanced), int(max_scenes)
+        self.pairs = None
+        self._scenes = {}
+
+    def _scene(self, s):
+        from . import synth
+        if s not in self._scenes:
+            self._scenes[s] = synth.render_scene(7919 * self.seed + s, self.views, self.dataset, self.h)
+        return self._scenes[s]
+
+    def _mine(self):
+        if self.pairs is not None:
+            return
+        buckets = {k: [] for k in OVERLAPS}
+        flat = []
+        want = -(-self.size // 3)
+        for s in range(self.max_scenes):
+            sc = self._scene(s)
+            found = mine_pairs(sc["depth"], sc["R"], self.dataset, 7919 * self.seed + s)
+            for e in found:
+                e['scene'] = s
+                buckets[overlap_bucket(e['overlap'])].append(e)
+            flat += found
+            if (not self.balanced and len(flat) >= self.size) or (self.balanced and all(len(v) >= want for v in buckets.values())):
+                break
+        if self.balanced:
+            picked, rest = [], []
+            for r in range(max(len(v) for v in buckets.values())):
+                for k in OVERLAPS:
+                    if r < len(buckets[k]):
+                        (picked if r < want else rest).append(buckets[k][r])
+            flat = picked + rest
+        if len(flat) < self.size:
+            raise RuntimeError(f"SceneBatch: {len(flat)} pairs from {self.max_scenes} scenes of {self.views} views, {self.size} wanted")
+        self.pairs = flat[:self.size]
+        used = {e['scene'] for e in self.pairs}
+        self._scenes = {s: v for s, v in self._scenes.items() if s in used}
+
+    def take(self, idx):
+        from . import synth
+        self._mine()
+        out = {k: [] for k in ("rgb", "norm", "depth", "R")}
+        for b in idx:
+            e = self.pairs[int(b)]
+            sc, ij = self._scene(e['scene']), [e['id_src'], e['id_tgt']]
+            for k in out:
+                out[k].append(sc[k][ij])
+        out = {k: np.stack(v) for k, v in out.items()}
+        kps = [synth.make_keypoints(1, self.keypoints, 7919 * (self.seed + int(b)) + 13, self.mask_method, h=self.h) for b in idx]
+        out["pts"], out["ptw"] = np.concatenate([k[0] for k in kps]), np.concatenate([k[1] for k in kps])
+        return out
+
+
 def _batch_size(batch):
     return batch.size if hasattr(batch, "take") else batch["rgb"].shape[0]
 
@@ -249,12 +385,15 @@ def _default_record(pipe, sub, poses, device, names, ks):
     n = len(ks)
     depth = torch.from_numpy(np.ascontiguousarray(sub["depth"].reshape(2 * n, *sub["depth"].shape[2:]))).to(device)
     pcs, valid = util.depth2pc_dev(depth, pipe.dataset)
+    R_gts = [np.matmul(sub["R"][q, 1], np.linalg.inv(sub["R"][q, 0])) for q in range(n)]
+    ovs, nns = _pair_overlap_stats(pcs, valid, R_gts)
     pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
     out = []
     for q in range(n):
-        R_gt_44 = np.matmul(sub["R"][q, 1], np.linalg.inv(sub["R"][q, 0]))
+        R_gt_44 = R_gts[q]
         pc_src, pc_tgt = pcs[2 * q][valid[2 * q]], pcs[2 * q + 1][valid[2 * q + 1]]
-        ov, cam_dist, pc_dist, pc_nn = util.point_cloud_overlap(pc_src, pc_tgt, R_gt_44)
+        ov, pc_nn = ovs[q], nns[q]
+        cam_dist, pc_dist = _host_pair_stats(pc_src, pc_tgt, R_gt_44)
         nm = names[ks[q]] if names is not None else (f"pair{ks[q]}/src", f"pair{ks[q]}/tgt")
         out.append(result_record(nm[0], nm[1], poses[q], R_gt_44, pc_src, ov, pc_dist, cam_dist, pc_nn))
     return out
@@ -312,15 +451,18 @@ def _evaluate_baseline(batches, device, dataset, register, result_path, with_col
         else:
             pose, status = register(pcs, valid)
         pose, status = pose.cpu().numpy(), status.cpu().numpy()
+        R_gts = [np.matmul(sub["R"][q, 1], np.linalg.inv(sub["R"][q, 0])) for q in range(n)]
+        ovs, nns = _pair_overlap_stats(pcs, valid, R_gts)
         pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
         for q in range(n):
-            R_gt_44 = np.matmul(sub["R"][q, 1], np.linalg.inv(sub["R"][q, 0]))
+            R_gt_44 = R_gts[q]
             pc_src, pc_tgt = pcs[2 * q][valid[2 * q]], pcs[2 * q + 1][valid[2 * q + 1]]
             if len(pc_src) == 0 or len(pc_tgt) == 0:                  # evaluation.py:184-186
                 continue
-            ov, cam_dist, pc_dist, pc_nn = util.point_cloud_overlap(pc_src, pc_tgt, R_gt_44)
+            ov, pc_nn = ovs[q], nns[q]
             if ov < 0.1:                                                  # evaluation.py:190-191
                 continue
+            cam_dist, pc_dist = _host_pair_stats(pc_src, pc_tgt, R_gt_44)
             k = len(stats)
             rec = result_record(f"pair{k}/src", f"pair{k}/tgt", pose[q], R_gt_44, pc_src, ov, pc_dist, cam_dist, pc_nn)
             rec['status'] = int(status[q])
@@ -621,6 +763,17 @@ def _cli_parser_completion():
                          "from them on the GPU (util.frames_to_pano_dev) and their normals estimated there; the JSON line gains "
                          "pano_depth_err_median / pano_depth_err_p90 (relative, against the directly rendered panoramas inside the kinect "
                          "box) and the pose statistics of both routes (stats_from_frames, stats_rendered)")
+    ap.add_argument("--mine-pairs", action="store_true",
+                    help="no poses are estimated: render --scenes scenes of --scene-views posed views each (synth.render_scene, seeds --seed, "
+                         "--seed + 1, ...), find which pairs of views overlap on the GPU (mine_pairs) and print one JSON line with scenes, "
+                         "views, pairs per overlap bucket and seconds; --exp writes the pair list to <exp>.datalist.npy, the object file the "
+                         "reference's loaders read (datasets/SUNCG.py:66)")
+    ap.add_argument("--scenes", type=int, default=8, help="--mine-pairs: the number of scenes")
+    ap.add_argument("--scene-views", type=int, default=6, help="--mine-pairs / --pair-source scenes: views per scene")
+    ap.add_argument("--min-overlap", type=float, default=None, help="--mine-pairs: leave out pairs whose overlap is below this")
+    ap.add_argument("--pair-source", choices=["pairs", "scenes"], default="pairs",
+                    help="--method ours / fgs / gs / cgs: scenes = the pairs are mined from multi-view scenes (SceneBatch, equal numbers from "
+                         "the three overlap buckets) instead of synth.make_pairs' two unrelated poses per room, which almost never overlap")
     return ap
 
 
@@ -639,6 +792,35 @@ def main(argv=None):
     if args.normals == "estimated" and (args.descriptor_eval or args.completion_eval or args.method != "ours"):
         raise SystemExit("--normals estimated applies to --method ours (the pose evaluation): the baselines and the descriptor / completion "
                          "metrics do not read the views' normal maps as an input of the pipeline")
+
+    if args.mine_pairs:
+        if args.gpus > 1:
+            raise SystemExit("--mine-pairs runs on one GPU (--gpus 1)")
+        if args.scenes < 1 or args.scene_views < 2:
+            raise SystemExit("--mine-pairs takes --scenes >= 1 and --scene-views >= 2")
+        import torch
+        from . import _lib, synth
+        dev = _lib.require_gpu()
+        entries = []
+        t0 = time.perf_counter()
+        for s in range(args.scenes):
+            sc = synth.render_scene(args.seed + s, args.scene_views, args.dataset)
+            entries += mine_pairs(sc["depth"], sc["R"], args.dataset, f"scene{args.seed + s}", min_overlap=args.min_overlap, device=dev)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        path = None if args.exp is None else save_data_list(args.exp + ".datalist.npy", {"test": entries})
+        per = {k: sum(1 for e in entries if overlap_bucket(e['overlap']) == k) for k in OVERLAPS}
+        print(json.dumps({"mine_pairs": True, "dataset": args.dataset, "scenes": args.scenes, "views": args.scene_views, "pairs": len(entries),
+                          "pairs_per_bucket": per, "min_overlap": args.min_overlap, "seconds": dt, "data_list": path}), flush=True)
+        return
+
+    if args.pair_source == "scenes" and (args.descriptor_eval or args.completion_eval or args.from_frames or args.keypoint_mode != "given"):
+        raise SystemExit("--pair-source scenes applies to --method ours (given keypoints) / fgs / gs / cgs")
+
+    def make_batch(size, seed, ds, mm):
+        if args.pair_source == "scenes":
+            return SceneBatch(size, seed, ds, mm, args.keypoints, views=args.scene_views, balanced=True)
+        return None
 
     if args.from_frames:
         if args.descriptor_eval or args.completion_eval or args.method != "ours" or args.dataset != "scannet" or args.keypoint_mode != "given":
@@ -729,7 +911,8 @@ def main(argv=None):
         from . import _lib
         dev = _lib.require_gpu()
         mm = "second"
-        batches = [SyntheticBatch(min(args.batch, args.pairs - k), args.seed + k, args.dataset, mm, args.keypoints)
+        batches = [make_batch(min(args.batch, args.pairs - k), args.seed + k, args.dataset, mm) or
+                   SyntheticBatch(min(args.batch, args.pairs - k), args.seed + k, args.dataset, mm, args.keypoints)
                    for k in range(0, args.pairs, args.batch)]
         path = None if args.exp is None else args.exp + ".result.npy"
         t0 = time.perf_counter()
@@ -757,7 +940,8 @@ def main(argv=None):
         net.load_state_dict(weights.make_state_dict(7, S))
         net.set_precision(args.precision)
         pipe = RelativePosePipeline(net, ds, mm, params.final_params(ds), keypoints=args.keypoint_mode, completion=args.completion)
-        batches = [SyntheticBatch(min(args.batch, args.pairs - k), args.seed + k, ds, mm, args.keypoints,
+        batches = [make_batch(min(args.batch, args.pairs - k), args.seed + k, ds, mm) or
+                   SyntheticBatch(min(args.batch, args.pairs - k), args.seed + k, ds, mm, args.keypoints,
                                   sift=args.sift if args.keypoint_mode == "reference" else 0, sift_detector=args.sift_detector)
                    for k in range(0, args.pairs, args.batch)]
         path = None if args.exp is None else args.exp + ".result.npy"

@@ -115,6 +115,33 @@ def make_pairs(B, seed, dataset="suncg", h=H):
     return {"rgb": rgb, "norm": nrm, "depth": dep, "R": Rp}
 
 
+def render_scene(seed, M, dataset="suncg", h=H):
+    """M views of ONE box room (make_pairs draws a room and two unrelated poses per pair; here every view sees the same walls, so pairs
+    of views overlap by anything between nothing and most of a face): rs = RandomState(seed); the room's half-extents, then M poses
+    random_rigid(rs, pi, 1.0) with the translation clipped to +-0.6 half, then the views rendered two at a time through render_room (an odd
+    last view is rendered twice and kept once).  -> {"rgb" [M,3,h,4h], "norm" [M,3,h,4h], "depth" [M,h,4h] float32, "R" [M,4,4] float64
+    world -> camera (the loaders' convention: R = inv(pose)), "pose" [M,4,4] camera -> world, "half" [3]}."""
+    rs = np.random.RandomState(seed)
+    half = rs.uniform(1.5, 4.0, 3)
+    poses = []
+    for _ in range(M):
+        T = random_rigid(rs, np.pi, 1.0)
+        T[:3, 3] = np.clip(T[:3, 3], -0.6 * half, 0.6 * half)
+        poses.append(T)
+    hole = 0.0 if "suncg" in dataset else 0.01
+    rgb = np.zeros((M, 3, h, 4 * h), np.float32)
+    nrm = np.zeros((M, 3, h, 4 * h), np.float32)
+    dep = np.zeros((M, h, 4 * h), np.float32)
+    for v in range(0, M, 2):
+        two = [poses[v], poses[min(v + 1, M - 1)]]
+        r, n, d, _ = render_room(rs, dataset, hole, h, poses=two, half=half)
+        k = min(2, M - v)
+        rgb[v:v + k], nrm[v:v + k], dep[v:v + k] = r[:k], n[:k], d[:k]
+    pose = np.stack(poses) if M else np.zeros((0, 4, 4))
+    return {"rgb": rgb, "norm": nrm, "depth": dep, "R": np.stack([np.linalg.inv(T) for T in poses]) if M else np.zeros((0, 4, 4)),
+            "pose": pose, "half": half}
+
+
 def room_half(seed):
     """The half-extents of the room of make_pairs' pair with this seed (render_room's first draw), for render_frames."""
     return np.random.RandomState(seed).uniform(1.5, 4.0, 3)

@@ -355,6 +355,129 @@ def point_cloud_overlap(pc_src, pc_tgt, R_gt_44):
     return ov, np.linalg.norm(R[:3, 3]), np.linalg.norm(src_trans.mean(1) - pc_tgt.T.mean(1)), (d_s2t.min() + d_t2s.min()) / 2
 
 
+def overlap_dev(pc, valid, query_cloud, ref_cloud, pose, max_dist=0.08, want_hit=False):
+    """relpose_overlap (include/relpose.h): pc [n,P,3] f64 and valid [n,P] u8 (or None: all valid) CUDA tensors in
+    depth2pc_dev's layout; query_cloud, ref_cloud: n_queries cloud indices (any integer sequence, array or tensor; they are read on the
+    host); pose [n_queries,4,4] f64 CUDA, query cloud -> the reference cloud's frame.
+    -> (hits [n_queries] i32, nn_min [n_queries] f64, n_valid [n] i32), and hit [n_queries,P] u8 with want_hit.  One grid per cloud per
+    call, shared by every query that names the cloud; the call waits for the stream once, at its end."""
+    import torch
+    _lib.require_gpu()
+    as_host = lambda v: np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.int32).reshape(-1)
+    qc, rc = as_host(query_cloud), as_host(ref_cloud)
+    if pc.dim() != 3 or pc.shape[2] != 3 or pc.dtype != torch.float64:
+        raise ValueError("overlap_dev takes pc [n,P,3] float64")
+    n, P = int(pc.shape[0]), int(pc.shape[1])
+    nq = len(qc)
+    if len(rc) != nq or tuple(pose.shape) != (nq, 4, 4) or pose.dtype != torch.float64:
+        raise ValueError("overlap_dev takes one reference cloud and one float64 4x4 pose per query")
+    if valid is not None and (tuple(valid.shape) != (n, P) or valid.dtype != torch.uint8):
+        raise ValueError("overlap_dev takes valid [n,P] uint8")
+    dev = pc.device
+    hits = torch.empty(nq, dtype=torch.int32, device=dev)
+    nn_min = torch.empty(nq, dtype=torch.float64, device=dev)
+    n_valid = torch.empty(n, dtype=torch.int32, device=dev)
+    hit = torch.empty(nq, P, dtype=torch.uint8, device=dev) if want_hit else None
+    if nq == 0 or n == 0 or P == 0:
+        if n and not P:
+            n_valid.zero_()
+        return (hits, nn_min, n_valid, hit) if want_hit else (hits, nn_min, n_valid)
+    L = _lib.lib()
+    nbytes = L.relpose_overlap_workspace_bytes(n, P, nq)
+    if nbytes == 0:
+        raise ValueError("overlap_dev: sizes outside relpose_overlap's limits")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    pcc, vc, posec = pc.contiguous(), (None if valid is None else valid.contiguous()), pose.contiguous()
+    a = _lib.OverlapArgs()
+    a.struct_size = _lib.C.sizeof(_lib.OverlapArgs)
+    a.n_clouds, a.n_points, a.n_queries = n, P, nq
+    a.pc, a.valid, a.pose = pcc.data_ptr(), (0 if vc is None else vc.data_ptr()), posec.data_ptr()
+    a.query_cloud_host, a.ref_cloud_host = qc.ctypes.data, rc.ctypes.data
+    a.max_dist = float(max_dist)
+    a.hits, a.nn_min, a.n_valid, a.hit = hits.data_ptr(), nn_min.data_ptr(), n_valid.data_ptr(), (hit.data_ptr() if want_hit else 0)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.stream = _lib.stream_ptr()
+    rc_ = L.relpose_overlap(_lib.C.byref(a))
+    if rc_ == _lib.OVERLAP_EXTENT:
+        raise RuntimeError("relpose_overlap: a cloud's finite points span more than 2^20 grid cells along an axis at this max_dist")
+    _lib.check(rc_, "relpose_overlap")
+    return (hits, nn_min, n_valid, hit) if want_hit else (hits, nn_min, n_valid)
+
+
+def point_cloud_overlap_dev(pc, valid, R_gt, max_dist=0.08):
+    """point_cloud_overlap for a batch of pairs without leaving the device: pc [2B,P,3] f64, valid [2B,P] u8 CUDA tensors in the paired
+    layout (cloud 2b = the source of pair b, 2b + 1 its target, as depth2pc_dev writes them), R_gt [B,4,4] host float64 (source -> target)
+    -> (overlap, cam_dist, pc_dist, pc_nn) float64 CUDA tensors [B].  One relpose_overlap call with 2B directed queries; the inverse poses
+    are np.linalg.inv on the host, as point_cloud_overlap computes them.  overlap = max(hits_s2t / n_src, hits_t2s / n_tgt) and
+    pc_nn = (nn_s2t + nn_t2s) / 2 are bitwise point_cloud_overlap's on the pair's valid points.  pc_dist, the distance between the moved
+    source's mean and the target's mean, is computed with float64 torch reductions on the device: it is NOT bitwise numpy's pairwise
+    mean (it agrees to about 1e-15 relative; the evaluation drivers keep the host expression for their records).  A pair with an empty
+    cloud gets overlap 0, pc_nn = +inf and pc_dist NaN."""
+    import torch
+    R = np.ascontiguousarray(R_gt, dtype=np.float64).reshape(-1, 4, 4)
+    B = R.shape[0]
+    if pc.shape[0] != 2 * B:
+        raise ValueError("point_cloud_overlap_dev takes two clouds per pose")
+    dev = pc.device
+    poses = np.empty((2 * B, 4, 4))
+    for b in range(B):
+        poses[2 * b] = R[b]
+        poses[2 * b + 1] = np.linalg.inv(R[b])
+    src, tgt = np.arange(0, 2 * B, 2), np.arange(1, 2 * B, 2)
+    qc = np.stack((src, tgt), 1).reshape(-1)
+    rc = np.stack((tgt, src), 1).reshape(-1)
+    Rd = torch.from_numpy(R).to(dev)
+    hits, nn_min, n_valid = overlap_dev(pc, valid, qc, rc, torch.from_numpy(poses).to(dev), max_dist)
+    n = n_valid.to(torch.float64).reshape(B, 2)
+    frac = hits.to(torch.float64).reshape(B, 2) / n
+    frac = torch.where(n > 0, frac, torch.zeros_like(frac))
+    overlap = torch.maximum(frac[:, 0], frac[:, 1])
+    overlap = torch.where((n > 0).all(1), overlap, torch.zeros_like(overlap))
+    nn = nn_min.reshape(B, 2)
+    pc_nn = (nn[:, 0] + nn[:, 1]) / 2
+    m = (torch.ones(pc.shape[:2], dtype=torch.bool, device=dev) if valid is None else valid != 0).unsqueeze(-1)
+    mean = torch.where(m, pc, torch.zeros_like(pc)).sum(1) / n.reshape(2 * B, 1)                     # [2B,3]
+    ms, mt = mean[0::2], mean[1::2]
+    moved = torch.einsum("bij,bj->bi", Rd[:, :3, :3], ms) + Rd[:, :3, 3]
+    pc_dist = (moved - mt).norm(dim=1)
+    cam_dist = Rd[:, :3, 3].norm(dim=1)
+    return overlap, cam_dist, pc_dist, pc_nn
+
+
+def overlap_matrix_dev(pc, valid, R, max_dist=0.08):
+    """Which of M posed clouds overlap, and by how much: pc [M,P,3] f64, valid [M,P] u8 CUDA tensors, R [M,4,4] host float64 world -> camera
+    poses (the loaders' convention).  T_ij = R_j inv(R_i) moves cloud i into cloud j's frame: the product evaluate_pairs forms for R_gt.
+    -> (frac [M,M] f64, nn_min [M,M] f64, n_valid [M] i32) CUDA tensors from ONE relpose_overlap call with M (M - 1) directed queries:
+    frac[i,j] = the share of cloud i's valid points with a point of cloud j within max_dist (0 for an empty cloud i), nn_min[i,j] their
+    closest-pair distance.  The diagonal is frac 1 (0 for an empty cloud) and nn_min 0 (+inf for an empty cloud) without being computed."""
+    import torch
+    R = np.ascontiguousarray(R, dtype=np.float64).reshape(-1, 4, 4)
+    M = R.shape[0]
+    if pc.shape[0] != M:
+        raise ValueError("overlap_matrix_dev takes one pose per cloud")
+    dev = pc.device
+    inv = [np.linalg.inv(R[i]) for i in range(M)]
+    ij = [(i, j) for i in range(M) for j in range(M) if i != j]
+    frac = torch.zeros(M, M, dtype=torch.float64, device=dev)
+    nn = torch.full((M, M), float("inf"), dtype=torch.float64, device=dev)
+    if not ij:
+        n_valid = (torch.full((M,), pc.shape[1], dtype=torch.int32, device=dev) if valid is None else (valid != 0).sum(1).to(torch.int32))
+    else:
+        poses = np.stack([np.matmul(R[j], inv[i]) for i, j in ij])
+        qi = torch.tensor([i for i, _ in ij], device=dev)
+        qj = torch.tensor([j for _, j in ij], device=dev)
+        hits, nn_min, n_valid = overlap_dev(pc, valid, [i for i, _ in ij], [j for _, j in ij], torch.from_numpy(poses).to(dev), max_dist)
+        nq = n_valid.to(torch.float64)[qi]
+        f = hits.to(torch.float64) / nq
+        frac[qi, qj] = torch.where(nq > 0, f, torch.zeros_like(f))
+        nn[qi, qj] = nn_min
+    d = torch.arange(M, device=dev)
+    some = n_valid > 0
+    frac[d, d] = some.to(torch.float64)
+    nn[d, d] = torch.where(some, torch.zeros(M, dtype=torch.float64, device=dev), torch.full((M,), float("inf"), dtype=torch.float64, device=dev))
+    return frac, nn, n_valid
+
+
 def depth2pc(depth, dataList):
     """util.py:468: depth numpy = one h x h face (suncg / matterport) or the 66x88 kinect crop (scannet)
     -> (pc [k,3] of the non-zero depths, mask)."""
