@@ -91,10 +91,13 @@ void relpose_default_params(RelposeParams* p_host);
  *   RELPOSE_TUNE_DECONV_STRIP       0 = SCNet's deconv4 / deconv5 on the phase strip kernel (default): the split-K launches, and deconv4's
  *                                   unsplit launch of the three-piece bf16 modes (direct stores, fused BatchNorm records), 1 = on the
  *                                   implicit-GEMM kernel (same K split, same order of every sum, same bits); read when a forward looks
- *                                   up its plan: each value has plans of its own */
+ *                                   up its plan: each value has plans of its own
+ *   RELPOSE_TUNE_ZERO_TILES         0 = SCNet's conv2 / conv3 tile kernels run only the patches whose receptive field holds a non-zero
+ *                                   input pixel plus one representative per edge class, the others are copies (default), 1 = every
+ *                                   patch is computed (same bits); read when a forward looks up its plan, like RELPOSE_TUNE_DECONV_STRIP */
 enum { RELPOSE_TUNE_AFFINITY_KERNEL = 0, RELPOSE_TUNE_FIT_MAX_PRODUCTS = 1, RELPOSE_TUNE_FIT_CLUSTER = 2,
        RELPOSE_TUNE_FIT_GLOBAL_VECTORS = 3, RELPOSE_TUNE_FIT_FIXED_CHECKS = 4, RELPOSE_TUNE_HEADS_KERNEL = 5, RELPOSE_TUNE_DECONV_STRIP = 6,
-       RELPOSE_TUNE_COUNT = 8 };
+       RELPOSE_TUNE_ZERO_TILES = 7, RELPOSE_TUNE_COUNT = 8 };
 int relpose_set_tuning(int32_t key, int32_t value);
 const char* relpose_version(void);
 /* ------------------------------------------------------------------ matcher
@@ -1020,6 +1023,11 @@ int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n_images, int32_t flags, 
  * BatchNorm records), 0 = another kernel, <0 = invalid argument or unknown layer.  For tests that
  * compare the two arms of RELPOSE_TUNE_DECONV_STRIP. */
 int relpose_scnet_layer_kernel(RelposeSCNet* net, const char* layer, int32_t n_images);
+
+/* Workgroups the conv2 / conv3 tile kernels of the last forward computed and dropped (RELPOSE_TUNE_ZERO_TILES): counts_host[4] =
+ * {conv2 computed, conv2 dropped, conv3 computed, conv3 dropped}, in workgroups (conv2: one 16 x 16 patch, conv3: a pair of 8 x 8
+ * patches), summed over the launch members of that forward's plan.  Synchronises `stream` (the forward's).  For tests and profiles. */
+int relpose_scnet_zero_tiles(RelposeSCNet* net, void* workspace, void* stream, int64_t* counts_host);
 
 /* Debug: copy a raw (pre-BatchNorm) layer output of the last forward, NHWC float32, to out (device).
  * Returns the number of floats written (or needed if out is NULL), <0 if unknown. */

@@ -102,6 +102,11 @@ struct ConvDesc {
     // snap_mode 2 starts from that snapshot and runs only the chunks of src[0] -- bitwise the accumulator chain of the full forward
     int snap_mode;
     float* snap;
+    // zero-tile lists (conv_s2_tile_kernel; null = every workgroup computes the patch of its own index): zt_count = {workgroups to run,
+    // workgroups to fill}, zt_list the patch (pair) indices to compute, zt_fill {dropped, representative} index pairs (zero_tile_list_kernel)
+    const int* zt_count;
+    const int* zt_list;
+    const int2* zt_fill;
 };
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return fmaxf(v, slope * v); }   // slope in (0,1]
@@ -941,12 +946,18 @@ __global__ __launch_bounds__(256, SPLIT >= 4 ? 2 : (MI * NI <= 2 ? 4 : 3)) void 
     __shared__ __attribute__((aligned(16))) float Bt[B_ROWS * LD];
     __shared__ __attribute__((aligned(16))) float sstab[2 * 128];
     const ConvDesc d = descs[blockIdx.y];
+    // zero-tile list (RELPOSE_TUNE_ZERO_TILES): the workgroup's patch / pair index comes from the list, workgroups past its end have nothing to do
+    int unit = blockIdx.x;
+    if (d.zt_list) {
+        if ((int)blockIdx.x >= d.zt_count[0]) return;
+        unit = __builtin_amdgcn_readfirstlane(d.zt_list[blockIdx.x]);      // (workgroup-uniform: the patch geometry stays in scalar registers)
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l31 = lane & 31;
     const int ppx = d.Wp / PW, ppi = (d.Hp / PR) * ppx;
     int imgs[2], y0s[2], x0s[2];
 #pragma unroll
     for (int sp = 0; sp < 2; ++sp) {
-        const int q = PAIR ? 2 * blockIdx.x + sp : blockIdx.x;
+        const int q = PAIR ? 2 * unit + sp : unit;
         imgs[sp] = q / ppi;
         const int prem = q - imgs[sp] * ppi;
         y0s[sp] = (prem / ppx) * PR; x0s[sp] = (prem % ppx) * PW;
@@ -961,27 +972,25 @@ __global__ __launch_bounds__(256, SPLIT >= 4 ? 2 : (MI * NI <= 2 ? 4 : 3)) void 
     const int a_lds0 = (tid / KQ) * LD + kqa * 4;
     // halo slot it = plane-tile pixel tid / 8 + PSTEP it: input pixel (2 (Y0 + r) - p, 2 (X0 + c) - q) of plane (p, q); a_in[it] is the
     // (p, q) = (0, 0) pixel index relative to image img_base, a_edge[it] flags the slots that leave the image for p = 1 / p = 0 / q = 1 / q = 0
-    int a_in[A_SLOTS], a_edge = 0;
+    // (f16x3 conv2, the one instantiation that sat 4 registers over its 168: slots 8.. keep neither index nor flags, both are recomputed from the
+    // thread index where they are used -- same addresses, same masks)
+    constexpr bool RECOMP = SPLIT == 2 && !PAIR;
+    auto a_slot = [&](int t, int it, int& off, int& e) {
+        const int pix = t / KQ + it * PSTEP;
+        const int sp = (PAIR && pix >= SUBPIX) ? 1 : 0, lp = pix - sp * SUBPIX;
+        const int r = lp / HW1, c = lp - r * HW1;
+        const int iy = 2 * ((sp ? y0s[1] : y0s[0]) + r), ix = 2 * ((sp ? x0s[1] : x0s[0]) + c);
+        off = (((sp ? imgs[1] : imgs[0]) - img_base) * d.Hin + iy) * d.Win + ix;
+        // p = 1 needs iy - 1 >= 0; p = 0 needs iy < Hin; same for columns; slots past the tile are always invalid
+        e = (pix >= NPIX) ? 15 : ((iy - 1 < 0 ? 1 : 0) | (iy >= d.Hin ? 2 : 0) | (ix - 1 < 0 ? 4 : 0) | (ix >= d.Win ? 8 : 0));
+    };
+    int a_in[A_SLOTS], a_edge = 0, a_edge2 = 0;
 #pragma unroll
     for (int it = 0; it < A_SLOTS; ++it) {
-        const int pix = tid / KQ + it * PSTEP;
-        const int sp = (PAIR && pix >= SUBPIX) ? 1 : 0, lp = pix - sp * SUBPIX;
-        const int r = lp / HW1, c = lp - r * HW1;
-        const int iy = 2 * ((sp ? y0s[1] : y0s[0]) + r), ix = 2 * ((sp ? x0s[1] : x0s[0]) + c);
-        a_in[it] = (((sp ? imgs[1] : imgs[0]) - img_base) * d.Hin + iy) * d.Win + ix;
-        // p = 1 needs iy - 1 >= 0; p = 0 needs iy < Hin; same for columns; slots past the tile are always invalid
-        const int e = (pix >= NPIX) ? 15 : ((iy - 1 < 0 ? 1 : 0) | (iy >= d.Hin ? 2 : 0) | (ix - 1 < 0 ? 4 : 0) | (ix >= d.Win ? 8 : 0));
-        if (it < 8) a_edge |= e << (4 * it);                          // (slots 8.. : second word below)
-    }
-    int a_edge2 = 0;
-#pragma unroll
-    for (int it = 8; it < A_SLOTS; ++it) {
-        const int pix = tid / KQ + it * PSTEP;
-        const int sp = (PAIR && pix >= SUBPIX) ? 1 : 0, lp = pix - sp * SUBPIX;
-        const int r = lp / HW1, c = lp - r * HW1;
-        const int iy = 2 * ((sp ? y0s[1] : y0s[0]) + r), ix = 2 * ((sp ? x0s[1] : x0s[0]) + c);
-        const int e = (pix >= NPIX) ? 15 : ((iy - 1 < 0 ? 1 : 0) | (iy >= d.Hin ? 2 : 0) | (ix - 1 < 0 ? 4 : 0) | (ix >= d.Win ? 8 : 0));
-        a_edge2 |= e << (4 * (it - 8));
+        int e;
+        a_slot(tid, it, a_in[it], e);
+        if (it < 8) a_edge |= e << (4 * it);                          // (slots 8.. : the second word)
+        else a_edge2 |= e << (4 * (it - 8));
     }
     const size_t img_px = (size_t)img_base * d.Hin * d.Win;
     const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)(d.src[0].x + img_px * d.src[0].cstride), 0,
@@ -1019,8 +1028,14 @@ __global__ __launch_bounds__(256, SPLIT >= 4 ? 2 : (MI * NI <= 2 ? 4 : 3)) void 
         const int bad_ = (p_ ? 1 : 2) | (q_ ? 4 : 8);                                                         \
         const int dlt_ = p_ * d.Win + q_;                                                                     \
         _Pragma("unroll") for (int it = 0; it < A_SLOTS; ++it) {                                              \
-            const int e_ = ((it < 8 ? a_edge : a_edge2) >> (4 * (it & 7))) & bad_;                            \
+            int e_ = ((it < 8 ? a_edge : a_edge2) >> (4 * (it & 7))) & bad_;                                  \
             int px_ = a_in[it];                                                                               \
+            if (RECOMP && it >= 8) {                                                                          \
+                int t_ = tid, ea_;                                                                            \
+                asm volatile("" : "+v"(t_));                                                                  \
+                a_slot(t_, it, px_, ea_);                                                                     \
+                e_ = ea_ & bad_;                                                                              \
+            }                                                                                                 \
             asm volatile("" : "+v"(px_));                                                                     \
             const int voff_ = (e_ ? 0 : px_ - dlt_) * scs4 + kqa * 16;                                        \
             ra[it] = rp_bufld4(rs_a, voff_, (CH) * BK * 4);                                                   \
@@ -1038,7 +1053,13 @@ __global__ __launch_bounds__(256, SPLIT >= 4 ? 2 : (MI * NI <= 2 ? 4 : 3)) void 
             v01 = v01 * (rp_v2f){s0_.x, s0_.y} + (rp_v2f){s1v_.x, s1v_.y};                                    \
             v23 = v23 * (rp_v2f){s0_.z, s0_.w} + (rp_v2f){s1v_.z, s1v_.w};                                    \
             const rp_v2f t01 = v01 * sl2_, t23 = v23 * sl2_;                                                  \
-            const float okf_ = ((((it < 8 ? a_edge : a_edge2) >> (4 * (it & 7))) & bad_) == 0) ? 1.f : 0.f;   \
+            int ee_ = (it < 8 ? a_edge : a_edge2) >> (4 * (it & 7));                                          \
+            if (RECOMP && it >= 8) {                                                                          \
+                int t_ = tid, po_;                                                                            \
+                asm volatile("" : "+v"(t_));                                                                  \
+                a_slot(t_, it, po_, ee_);                                                                     \
+            }                                                                                                 \
+            const float okf_ = ((ee_ & bad_) == 0) ? 1.f : 0.f;                                               \
             const rp_v2f mk_ = {okf_, okf_};                                                                  \
             v01 = (rp_v2f){fmaxf(v01.x, t01.x), fmaxf(v01.y, t01.y)} * mk_;                                   \
             v23 = (rp_v2f){fmaxf(v23.x, t23.x), fmaxf(v23.y, t23.y)} * mk_;                                   \
@@ -1125,7 +1146,7 @@ __global__ __launch_bounds__(256, SPLIT >= 4 ? 2 : (MI * NI <= 2 ? 4 : 3)) void 
             double a = 0, b = 0;
 #pragma unroll
             for (int w = 0; w < NW; ++w) { a += red[((w * NI) * 32 + tid) * 2]; b += red[((w * NI) * 32 + tid) * 2 + 1]; }
-            double* o = d.stat_part + (((size_t)blockIdx.x * 2) * d.cout_pad + n0 + tid) * 2;
+            double* o = d.stat_part + (((size_t)unit * 2) * d.cout_pad + n0 + tid) * 2;
             rp_stg(o, a); rp_stg(o + 1, b);
         }
     }
@@ -2239,6 +2260,137 @@ __global__ __launch_bounds__(256) void bcast_warped_kernel(float* __restrict__ a
     }
 }
 
+// ---- zero tiles (RELPOSE_TUNE_ZERO_TILES) -----------------------------------------------------------------------------------
+// The resized input X0 is mostly exact zeros (util.apply_mask keeps one face of a view; the warped partner view is that face splatted into a
+// zero panorama).  conv1 has no bias: A1 is +0 wherever the 3 x 3 neighbourhood of X0 is zero, and BatchNorm + LeakyReLU turn such a region
+// into one constant per channel and BatchNorm group.  A conv2 / conv3 patch whose whole receptive field lies in it computes a tile that
+// depends on the patch's edge class only (which image borders it touches: the zero padding comes after BatchNorm), bit for bit -- every
+// workgroup of an instantiation issues the same operations in the same order.  Per BatchNorm group, stream and class one such patch is
+// computed (the lowest index); zero_tile_fill_kernel copies its tile and its BatchNorm record to the others.
+//   conv2 patch p (16 of 112 outputs) reads A1 rows 32p - 1 .. 32p + 32 = X0 rows 32p - 2 .. 32p + 33
+//   conv3 patch p (8 of 56 outputs)   reads A2 rows 16p - 1 .. 16p + 16 = A1 rows 32p - 3 .. 32p + 34 = X0 rows 32p - 4 .. 32p + 35
+// both inside the 8-pixel occupancy blocks 4p - 1 .. 4p + 4: the one block range tested (conservative by up to 6 pixels per side).
+// A non-finite input value makes a group's BatchNorm {scale, shift} NaN: that group and stream skip nothing.
+constexpr int ZT_BLK = 8, ZT_NB = RS / ZT_BLK;      // occupancy block (X0 pixels), blocks per image side (28: a bit each, bit 31 = non-finite value seen)
+constexpr int ZT_NP = 7, ZT_PPI = ZT_NP * ZT_NP;    // patches per image side / per image and stream (conv2: 16 x 16 of 112, conv3: 8 x 8 of 56)
+constexpr int ZT_HDR = 32;                          // ints in front of the lists: counts[2 layers][6 streams]{computed, filled}
+static_assert(RS == ZT_NP * 32 && ZT_NB <= 31, "patch / block geometry");
+inline size_t zt_occ_ints(int n) { return (size_t)n * 6 * ZT_NB; }
+inline size_t zt_ints(int n) { return zt_occ_ints(n) + ZT_HDR + (size_t)36 * n * ZT_PPI; }      // + lists [2][6][cap] + fills [2][6][cap]{2}, cap = 49 n
+
+// occ[img][q][block row]: bit bx = block (by, bx) of stream q = 2 m + s (channels as in conv1_inputs) holds a bit pattern other than +-0.
+// One workgroup = one block row of one image.  c_begin = 8 (self-stream cache): only the warped streams' words are used, channels 0:8 are not read.
+__global__ __launch_bounds__(256) void x0_occupancy_kernel(const float* __restrict__ x0, unsigned* __restrict__ occ, int* __restrict__ counts, int c_begin) {
+    __shared__ unsigned w[6];
+    const int tid = threadIdx.x, img = blockIdx.x / ZT_NB, by = blockIdx.x % ZT_NB;
+    if (blockIdx.x == 0 && tid < ZT_HDR) counts[tid] = 0;             // (zero_tile_list_kernel, the next launch, adds to them)
+    if (tid < 6) w[tid] = 0u;
+    __syncthreads();
+    unsigned m[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    const uint4* base = reinterpret_cast<const uint4*>(x0 + ((size_t)img * RS + (size_t)by * ZT_BLK) * RS * 16);
+    for (int p = tid; p < ZT_BLK * RS; p += 256) {
+        const unsigned bit = 1u << ((p % RS) / ZT_BLK);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (8 * s < c_begin) continue;
+            const uint4 a = base[(size_t)p * 4 + 2 * s], b = base[(size_t)p * 4 + 2 * s + 1];
+            const unsigned k = 0x7fffffffu, c7 = b.w & k;
+            const unsigned v[3] = {max(max(a.x & k, a.y & k), max(a.z & k, c7)), max(max(a.w & k, b.x & k), max(b.y & k, c7)), max(b.z & k, c7)};
+#pragma unroll
+            for (int mm = 0; mm < 3; ++mm)
+                if (v[mm]) m[2 * mm + s] |= bit | (v[mm] >= 0x7f800000u ? 0x80000000u : 0u);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) if (m[q]) atomicOr(&w[q], m[q]);
+    __syncthreads();
+    if (tid < 6) occ[((size_t)img * 6 + tid) * ZT_NB + by] = w[tid];
+}
+
+// The lists of one (BatchNorm group, stream, layer) per workgroup: grid (G, 6, 2), layer 0 = conv2 (unit = a patch), 1 = conv3 (unit = a pair
+// of consecutive patches, the tile kernel's workgroup).  A unit is dropped iff all its patches are redundant and an earlier unit of the
+// group with the same edge classes is too (that one, the lowest index, is the representative and stays on the list).  The groups append
+// their runs to the stream's list in any order (atomicAdd on the counts): the order of the list does not enter any result.
+struct ZtMembers { int nimg[6]; };                  // images of the launch member of stream q in this plan (0 = not launched)
+__device__ __forceinline__ int zt_edge_class(int p) {
+    const int py = p / ZT_NP, px = p - py * ZT_NP;
+    return 3 * (py == 0 ? 0 : (py == ZT_NP - 1 ? 2 : 1)) + (px == 0 ? 0 : (px == ZT_NP - 1 ? 2 : 1));
+}
+__global__ __launch_bounds__(128) void zero_tile_list_kernel(const unsigned* __restrict__ occ, int* __restrict__ zt, ZtMembers mem, int cap) {
+    const int g = blockIdx.x, q = blockIdx.y, layer = blockIdx.z, tid = threadIdx.x;
+    if (2 * g >= mem.nimg[q]) return;
+    __shared__ unsigned ow[2 * ZT_NB];
+    __shared__ int red[2 * ZT_PPI], rep[81], comp[2 * ZT_PPI], nonfin, cnt[2], base[2];
+    __shared__ int2 fl[2 * ZT_PPI];
+    if (tid == 0) nonfin = 0;
+    if (tid < 81) rep[tid] = -1;
+    __syncthreads();
+    if (tid < 2 * ZT_NB) {
+        const unsigned v = occ[((size_t)(2 * g + tid / ZT_NB) * 6 + q) * ZT_NB + tid % ZT_NB];
+        ow[tid] = v;
+        if (v >> 31) nonfin = 1;
+    }
+    __syncthreads();
+    if (tid < 2 * ZT_PPI) {
+        const int img = tid / ZT_PPI, p = tid - img * ZT_PPI, py = p / ZT_NP, px = p - py * ZT_NP;
+        const int by0 = max(4 * py - 1, 0), by1 = min(4 * py + 5, ZT_NB), bx0 = max(4 * px - 1, 0), bx1 = min(4 * px + 5, ZT_NB);
+        const unsigned mask = ((1u << bx1) - 1u) & ~((1u << bx0) - 1u);
+        unsigned any = 0u;
+        for (int by = by0; by < by1; ++by) any |= ow[img * ZT_NB + by] & mask;
+        red[tid] = (any == 0u && !nonfin) ? 1 : 0;
+    }
+    __syncthreads();
+    const int per = layer ? 2 : 1, nu = 2 * ZT_PPI / per;
+    if (tid == 0) {
+        int nc = 0, nf = 0;
+        for (int u = 0; u < nu; ++u) {
+            const int p0 = per * u, p1 = p0 + per - 1;
+            const int U = g * nu + u;
+            int r = -1;
+            if (red[p0] && red[p1]) {
+                const int key = layer ? zt_edge_class(p0 % ZT_PPI) * 9 + zt_edge_class(p1 % ZT_PPI) : zt_edge_class(p0 % ZT_PPI);
+                r = rep[key];
+                if (r < 0) rep[key] = U;
+            }
+            if (r < 0) comp[nc++] = U;
+            else fl[nf++] = make_int2(U, r);
+        }
+        cnt[0] = nc; cnt[1] = nf;
+        int* c = zt + (layer * 6 + q) * 2;
+        base[0] = atomicAdd(c, nc); base[1] = atomicAdd(c + 1, nf);
+    }
+    __syncthreads();
+    int* list = zt + ZT_HDR + (size_t)(layer * 6 + q) * cap;
+    int2* fills = reinterpret_cast<int2*>(zt + ZT_HDR + (size_t)12 * cap) + (size_t)(layer * 6 + q) * cap;
+    if (tid < cnt[0] && base[0] + tid < cap) list[base[0] + tid] = comp[tid];
+    if (tid < cnt[1] && base[1] + tid < cap) fills[base[1] + tid] = fl[tid];
+}
+
+// After a conv_s2_tile_kernel launch with lists: workgroup i of member blockIdx.y copies the output tile(s) and the BatchNorm record of fill
+// entry i's representative to the dropped patch (pair), pixel (r, c) <- pixel (r, c), every output channel.
+template <bool PAIR>
+__global__ __launch_bounds__(256) void zero_tile_fill_kernel(const ConvDesc* __restrict__ descs) {
+    const ConvDesc& d = descs[blockIdx.y];
+    if (!d.zt_fill || (int)blockIdx.x >= d.zt_count[1]) return;
+    const int2 f = d.zt_fill[blockIdx.x];                             // {dropped, representative}
+    constexpr int PR = PAIR ? 8 : 16, PW = PAIR ? 8 : 16, PER = PAIR ? 2 : 1;
+    const int tid = threadIdx.x, ppx = d.Wp / PW, ppi = (d.Hp / PR) * ppx, c4n = d.Cout / 4;
+    auto at = [&](int unit, int sp, int r, int c) {
+        const int qp = PER * unit + sp, img = qp / ppi, prem = qp - img * ppi;
+        const size_t pix = ((size_t)img * d.Hout + (prem / ppx) * PR + r) * d.Wout + (prem % ppx) * PW + c;
+        return d.y + pix * d.ycstride + d.ychoff;
+    };
+    for (int i = tid; i < PER * PR * PW * c4n; i += 256) {
+        const int c4 = i % c4n, pp = i / c4n, sp = pp / (PR * PW), lp = pp - sp * (PR * PW), r = lp / PW, c = lp - r * PW;
+        const float4 v = *reinterpret_cast<const float4*>(at(f.y, sp, r, c) + 4 * c4);
+        *reinterpret_cast<float4*>(at(f.x, sp, r, c) + 4 * c4) = v;
+    }
+    if (d.stat_part && tid < d.cout_pad) {
+        const double2 v = *reinterpret_cast<const double2*>(d.stat_part + (((size_t)f.y * 2) * d.cout_pad + tid) * 2);
+        *reinterpret_cast<double2*>(d.stat_part + (((size_t)f.x * 2) * d.cout_pad + tid) * 2) = v;
+    }
+}
+
 // ---- bilinear resize, align_corners=False (mymodel.py:261,379) --------------------------------------
 __device__ __forceinline__ void lin_coef(int dst, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
     float src = scale * (dst + 0.5f) - 0.5f;
@@ -2420,6 +2572,9 @@ struct RelposeSCNet {
     size_t gb_floats = 0;
     // timing
     int last_n = 0;
+    // relpose_scnet_zero_tiles: the last forward's list counts (device, null = it ran without lists) and the workgroups its conv2 / conv3 launches cover
+    const int* last_zt_counts = nullptr;
+    int64_t last_zt_units[2] = {0, 0};
     bool profiling = false;
     std::vector<hipEvent_t> ev;
     std::vector<int> ev_kind;
@@ -2673,7 +2828,7 @@ std::vector<std::pair<std::string, int>> bn_blocks(const std::string& b) {
 // (sub-pixel phases of a transposed conv, the six shared-weight encoder streams, parallel heads) are
 // merged into ONE grid (blockIdx.z = member) so the 256 CUs see thousands of tiles per launch instead
 // of a few hundred (wave quantisation); layers with few output tiles are split along K.
-enum { OP_CONV = 0, OP_REDUCE = 1, OP_STATS = 2, OP_CONV1 = 3, OP_STATS_FUSED = 4, OP_HEADS = 5, OP_DECONV_TILE = 6, OP_CONV_S2 = 7, OP_CONV_STRIP = 8, OP_BCAST = 9, OP_NOP = 10, OP_SS_FILL = 11 };
+enum { OP_CONV = 0, OP_REDUCE = 1, OP_STATS = 2, OP_CONV1 = 3, OP_STATS_FUSED = 4, OP_HEADS = 5, OP_DECONV_TILE = 6, OP_CONV_S2 = 7, OP_CONV_STRIP = 8, OP_BCAST = 9, OP_NOP = 10, OP_SS_FILL = 11, OP_ZT_FILL = 12 };
 struct Op { int type; int first, count, cfg; dim3 grid; std::string buf; int sslds = 0, uni = 0, split = 0; int ninner = 1, mt_max = 1; int skip_blk = 0; };
 
 struct Plan {
@@ -2693,6 +2848,9 @@ struct Plan {
     int tail_first = -1;         // first op of the forward's tail (the heads; resize_out follows): relpose_scnet_forward2 moves it to a second stream
     int head_count = 0;          // ops of the forward's head (conv1 + its BatchNorm finalize; resize_in precedes): second stream as well
     hipEvent_t tail_ev = nullptr, head_ev = nullptr;
+    bool zt = false;             // zero-tile lists (RELPOSE_TUNE_ZERO_TILES = 0 and conv2 / conv3 on conv_s2_tile_kernel)
+    int zt_nimg[6] = {0, 0, 0, 0, 0, 0};   // images of stream q's conv2 / conv3 launch member (ZtMembers)
+    int64_t zt_units[2] = {0, 0};          // workgroups of the conv2 / conv3 tile-kernel launches
 };
 
 struct Builder {
@@ -2715,6 +2873,8 @@ struct Builder {
     int nimg = 0;               // images of the members added by conv() (0 = n): RELPOSE_FWD_ZERO_WARP plans run the warped streams on 2
     std::string probe_layer;    // relpose_scnet_layer_kernel: the layer asked about and the index of its first descriptor
     int probe_desc = -1;
+    int* zt = nullptr;          // zero-tile counts + lists in the workspace (behind the occupancy words); null = no lists (knob, dry runs)
+    int zt_layer = -1;          // 0 / 1 while the members of conv2 / conv3 are added (conv() sets it from the layer name)
 
     float* buf(const std::string& b);
     float2* ssb(const std::string& b);
@@ -2782,6 +2942,7 @@ void Builder::conv(const std::string& layer, Src s0, const Src* s1, int Hin, con
     const Buf& O = net->bufs[out];
     const int Hout = O.H;
     if (probe_desc < 0 && !probe_layer.empty() && layer == probe_layer) probe_desc = (int)plan->descs.size();
+    zt_layer = !layer.compare(0, 5, "conv2") ? 0 : (!layer.compare(0, 5, "conv3") ? 1 : -1);
     for (const Phase& P : L.phases) {
         ConvDesc d;
         memset(&d, 0, sizeof(d));
@@ -2963,6 +3124,24 @@ void Builder::end_group() {
         Op o; o.type = OP_CONV_S2; o.first = first; o.count = count; o.cfg = s2_cfg; o.split = net->prec;
         o.grid = dim3((unsigned)(plan->descs[first].M / BMt), count, 1);
         plan->ops.push_back(o);
+        if (zt_layer >= 0) plan->zt_units[zt_layer] += (int64_t)o.grid.x * count;
+        // zero-tile lists: the grid stays the worst case, a member's workgroups past its list's end return; the fill pass follows the launch
+        // (RELPOSE_TUNE_ZERO_TILES = 1, dry runs: no lists, every workgroup computes the patch of its own index)
+        if (zt && zt_layer >= 0 && zt_layer == s2_cfg) {
+            const int cap = n * ZT_PPI;
+            for (int i = first; i < first + count; ++i) {
+                ConvDesc& d = plan->descs[i];
+                const int q = d.ychoff / d.Cout;                      // stream block of the output buffer = conv1 block 2 m + s
+                if (q < 0 || q >= 6 || d.ychoff != q * d.Cout || d.Cout % 4 || (int)o.grid.x > cap || (plan->zt_nimg[q] && plan->zt_nimg[q] != d.Nimg)) { rc = RELPOSE_EINVAL; return; }
+                plan->zt_nimg[q] = d.Nimg;
+                d.zt_count = zt + (zt_layer * 6 + q) * 2;
+                d.zt_list = zt + ZT_HDR + (size_t)(zt_layer * 6 + q) * cap;
+                d.zt_fill = reinterpret_cast<const int2*>(zt + ZT_HDR + (size_t)12 * cap) + (size_t)(zt_layer * 6 + q) * cap;
+            }
+            plan->zt = true;
+            Op f = o; f.type = OP_ZT_FILL;
+            plan->ops.push_back(f);
+        }
         return;
     }
     if (dtile) {
@@ -3187,7 +3366,7 @@ void free_plan(RelposeSCNet* net) {
     net->self_state.clear();       // (new weights / precision: nothing cached is valid)
 }
 
-struct WsOffsets { size_t act, ss, partial, splitk, statp, persist, snap, total; };
+struct WsOffsets { size_t act, ss, partial, splitk, statp, persist, snap, zt, total; };
 
 WsOffsets ws_offsets(RelposeSCNet* net, int n) {
     Plan dry;
@@ -3202,6 +3381,7 @@ WsOffsets ws_offsets(RelposeSCNet* net, int n) {
     o.statp = off; off += rp_align(dry.stat_doubles * sizeof(double));
     o.persist = off; off += rp_align(dry.persist_floats * sizeof(float));
     o.snap = off; off += rp_align(dry.snap_floats * sizeof(float));
+    o.zt = off; off += rp_align(zt_ints(n) * sizeof(int));      // occupancy words, then the zero-tile counts and lists (worst case)
     o.total = off;
     return o;
 }
@@ -3420,7 +3600,8 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     bool self_cached = self_tag != 0 && prev.tag == self_tag && prev.n == n && prev.H == H && prev.W == W && prev.pose_only == pose_only && !zero_warp &&
                        prev.gen == ws_gen;
     int snap_mode = 0;
-    const int ds_key = (g_rp_tune[RELPOSE_TUNE_DECONV_STRIP] == 1 ? 1 : 0) << 28;       // the builder reads the knob: one plan per value
+    const bool zt_on = g_rp_tune[RELPOSE_TUNE_ZERO_TILES] != 1;
+    const int ds_key = ((g_rp_tune[RELPOSE_TUNE_DECONV_STRIP] == 1 ? 1 : 0) << 28) | ((zt_on ? 0 : 1) << 29);       // the builder reads the knobs: one plan per value
     for (int attempt = 0; attempt < 2 && !plan; ++attempt) {
         // a tagged forward that computes the self streams also leaves the accumulator snapshots of the skip-connection halves
         snap_mode = self_cached ? 2 : (self_tag != 0 ? 1 : 0);
@@ -3441,6 +3622,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         B.act = (float*)(ws + o.act); B.ss = (float2*)(ws + o.ss); B.splitk = (float*)(ws + o.splitk); B.statp = (double*)(ws + o.statp);
         B.persist = (float*)(ws + o.persist);
         B.snapbuf = (float*)(ws + o.snap); B.snap_mode = snap_mode; p->snap_mode = snap_mode;
+        B.zt = zt_on ? (int*)(ws + o.zt) + zt_occ_ints(n) : nullptr;
         build_plan(net, n, B);
         if (B.rc) {
             delete p;
@@ -3481,6 +3663,20 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     mark(3);
     hipLaunchKernelGGL(resize_in_kernel, dim3(2048), dim3(256), 0, s, x, act + net->bufs["X0"].off * n, n, H, W, plan->self_cached ? 8 : 0);
     mark(-3);
+    net->last_zt_counts = nullptr;
+    net->last_zt_units[0] = plan->zt_units[0]; net->last_zt_units[1] = plan->zt_units[1];
+    if (plan->zt) {
+        // zero-tile lists of conv2 / conv3 from the occupancy of X0, on the stream that runs conv1 (nothing reads them before conv2)
+        unsigned* occ = (unsigned*)(ws + o.zt);
+        int* ztp = (int*)(ws + o.zt) + zt_occ_ints(n);
+        ZtMembers zm;
+        for (int q = 0; q < 6; ++q) zm.nimg[q] = plan->zt_nimg[q];
+        mark(2);
+        hipLaunchKernelGGL(x0_occupancy_kernel, dim3(n * ZT_NB), dim3(256), 0, s, act + net->bufs["X0"].off * n, occ, ztp, plan->self_cached ? 8 : 0);
+        hipLaunchKernelGGL(zero_tile_list_kernel, dim3(G, 6, 2), dim3(128), 0, s, occ, ztp, zm, n * ZT_PPI);
+        mark(-2);
+        net->last_zt_counts = ztp;
+    }
     int op_index = -1;
     for (const Op& op : plan->ops) {
         ++op_index;
@@ -3569,6 +3765,11 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
 #undef RP_L_S2A
 #undef RP_L_S2C
             mark(-1);
+        } else if (op.type == OP_ZT_FILL) {
+            mark(2);
+            if (op.cfg == 0) hipLaunchKernelGGL((zero_tile_fill_kernel<false>), op.grid, dim3(256), 0, s, plan->d_descs + op.first);
+            else hipLaunchKernelGGL((zero_tile_fill_kernel<true>), op.grid, dim3(256), 0, s, plan->d_descs + op.first);
+            mark(-2);
         } else if (op.type == OP_DECONV_TILE) {
             mark(1);
 #define RP_L_DT1(SP_) hipLaunchKernelGGL((deconv_tile_kernel<1, 2, 4, 16, false, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
@@ -3751,6 +3952,23 @@ int relpose_scnet_layer_kernel(RelposeSCNet* net, const char* layer, int32_t n) 
             B.probe_desc < op.first + op.count)
             return (op.type == OP_CONV_STRIP && op.cfg == 1) ? (dry.descs[B.probe_desc].ksplit == 1 ? 2 : 1) : 0;
     return RELPOSE_EINVAL;
+}
+
+int relpose_scnet_zero_tiles(RelposeSCNet* net, void* workspace, void* stream, int64_t* counts_host) {
+    if (!net || !net->finalized || !workspace || !counts_host || net->last_n <= 0) return RELPOSE_EINVAL;
+    for (int l = 0; l < 2; ++l) { counts_host[2 * l] = net->last_zt_units[l]; counts_host[2 * l + 1] = 0; }
+    if (!net->last_zt_counts) return 0;                 // the forward ran without lists: every workgroup computed its patch
+    const char* lo = (const char*)workspace + ws_offsets(net, net->last_n).zt;
+    if ((const char*)net->last_zt_counts < lo || (const char*)net->last_zt_counts >= lo + zt_ints(net->last_n) * sizeof(int)) return RELPOSE_EINVAL;
+    int h[ZT_HDR];
+    RP_HIP(hipMemcpyAsync(h, net->last_zt_counts, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    RP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    for (int l = 0; l < 2; ++l) {
+        int64_t c = 0, f = 0;
+        for (int q = 0; q < 6; ++q) { c += h[(l * 6 + q) * 2]; f += h[(l * 6 + q) * 2 + 1]; }
+        counts_host[2 * l] = c; counts_host[2 * l + 1] = f;
+    }
+    return 0;
 }
 
 int64_t relpose_scnet_read_tap(RelposeSCNet* net, const char* name, float* out, void* workspace, void* stream) {

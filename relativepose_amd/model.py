@@ -252,6 +252,13 @@ class SCNet(torch.nn.Module):
             raise KeyError(layer)
         return r
 
+    def zero_tiles(self):
+        """{2: (computed, dropped), 3: (computed, dropped)}: workgroups of conv2 (one patch) / conv3 (a patch pair) the last forward ran and
+        replaced by copies (relpose_scnet_zero_tiles; synchronises the current stream)."""
+        v = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().relpose_scnet_zero_tiles(self._h, _lib.ptr(self._ws), _lib.stream_ptr(), v), "relpose_scnet_zero_tiles")
+        return {2: (int(v[0]), int(v[1])), 3: (int(v[2]), int(v[3]))}
+
     def layer_on_strip_kernel(self, layer, n):
         """True if ``layer`` runs on deconv_strip_kernel (either launch form)."""
         return self.layer_kernel(layer, n) in (1, 2)
