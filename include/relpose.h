@@ -894,6 +894,71 @@ typedef struct RelposeOverlapArgs {
 size_t relpose_overlap_workspace_bytes(int32_t n_clouds, int32_t n_points, int32_t n_queries);
 int relpose_overlap(const RelposeOverlapArgs* args);
 
+/* -------------------------------------------------------------------- visibility consistency of relative poses
+ * relpose_overlap is blind where two scans share no surface: no point has a neighbour under the right pose or under a wrong one.  A depth
+ * panorama still says which space its sensor saw through.  relpose_visibility scores a batch of directed (query cloud, reference view, pose)
+ * triples: every moved query point is projected into the reference view's depth panorama and compared with the depths measured around its
+ * pixel.  In front of them the point contradicts the view (violation), behind them it is hidden (occluded), on them it agrees.  The
+ * contract is the project's own (tests/visibility_model.py restates it in numpy).  Two launches, whatever n_queries is; the
+ * first also clears the counters.  Invalid arguments return RELPOSE_EINVAL before anything is enqueued or any output is touched.  The
+ * geometry is float64, every operation rounded on its own; only integer atomics are used, one per class per workgroup: results are
+ * repeatable bit for bit, and a query's row does not depend on the batch around it.
+ *
+ *   pc, valid        [n_clouds, n_points, 3] f64 and [n_clouds, n_points] u8 as relpose_depth2pc writes them; valid NULL = all valid
+ *   depth            [n_views, h, 4h] f32 reference panoramas; a value that is not finite or is <= 0 means no data
+ *   query_cloud_host, ref_view_host   [n_queries] i32 in HOST memory (they are validated before anything touches the device)
+ *   pose             [n_queries, 4, 4] f64 row-major, query cloud -> the reference view's frame: q_a = ((T_a0 x + T_a1 y) + T_a2 z) + T_a3
+ *   dataset          RELPOSE_SUNCG / RELPOSE_MATTERPORT / RELPOSE_SCANNET: the face order of the reference panoramas
+ *   radius           r in {0, 1, 2}, h >= 2r + 1;  tol_abs, tol_rel: finite, >= 0 (the library's defaults are r = 1, 0.05 and 0.02)
+ *   pass 1           once per view however many queries name it: for every pixel (dmin, dmax) as f32 = the minimum and maximum of the valid
+ *                    depths in the (2r+1)^2 window around it.  The window is clipped to the pixel's own face: columns do not cross a face
+ *                    seam (neighbouring faces see one wall at different face depths), rows are clipped to 0..h-1; invalid neighbours are
+ *                    skipped; a pixel whose own depth is invalid is unobserved whatever its neighbours hold
+ *   pass 2           relpose_frames_to_pano's projection: for slot = 0..3, (X, Y, Z) = Rs[k]^T q with k = slot (suncg) / (slot - 1) % 4
+ *                    (matterport, scannet); xn = X / (|Z| + 1e-32), yn = Y / (|Z| + 1e-32); the first slot with Z < 0, |xn| < 1, |yn| < 1 is
+ *                    taken; column = slot h + clip(rint((xn + 1) * 0.5 * h), 0, h - 1), row = clip(rint((1 - yn) * 0.5 * h), 0, h - 1), rint
+ *                    rounding half to even; d = -Z, kept in f64
+ *   class            0 invalid point; 1 outside: no face, a non-finite moved coordinate, or d >= 32768; 2 unobserved: the pixel has no data;
+ *                    4 violation: d < dmin - (tol_abs + tol_rel * dmin); 5 occluded: d > dmax + (tol_abs + tol_rel * dmax); 3 consistent
+ *                    otherwise.  dmin, dmax widened to f64; each of the two multiplications, two additions and the subtraction is its own
+ *                    f64 operation; the inequalities are strict: a point exactly on a bound is consistent
+ *   counts           [n_queries, 6] i32: the number of points in each class 0..5; a row sums to n_points
+ *   margin_sum       [n_queries] u64: over the violations, the sum of llrint(min(m, 32768) * 65536.0), m = (dmin - (tol_abs + tol_rel * dmin)) - d
+ *                    (the panorama accumulators' fixed point; a term is at most 2^31 -- the minimum only acts where a reference depth
+ *                    exceeds 32768 -- so the sum cannot overflow for n_points <= 2^24)
+ *   cls              [n_queries, n_points] u8 or NULL: the class of every point
+ *   workspace        relpose_visibility_workspace_bytes(n_views, h, n_queries) bytes (0 for invalid sizes), 256-byte aligned: the window
+ *                    images (8 bytes per pixel, the pair interleaved so that pass 2 needs one gather per point) and the two index arrays
+ *   limits           h even, 2..8192; 1 <= n_views, n_clouds, n_queries; n_views * h * 4h < 2^31; 1 <= n_points <= 2^24;
+ *                    n_queries * ceil(n_points / 256) < 2^31; cloud and view indices in range
+ * The call waits for `stream` once, at its end: the two host index arrays are the caller's again when it returns. */
+typedef struct RelposeVisibilityArgs {
+    uint32_t struct_size;       /* sizeof(RelposeVisibilityArgs) as the caller compiled it */
+    int32_t n_clouds;
+    int32_t n_points;
+    int32_t n_views;
+    int32_t h;
+    int32_t n_queries;
+    int32_t dataset;
+    int32_t radius;
+    const double* pc;
+    const uint8_t* valid;
+    const float* depth;
+    const int32_t* query_cloud_host;
+    const int32_t* ref_view_host;
+    const double* pose;
+    double tol_abs;
+    double tol_rel;
+    int32_t* counts;
+    uint64_t* margin_sum;
+    uint8_t* cls;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeVisibilityArgs;
+size_t relpose_visibility_workspace_bytes(int32_t n_views, int32_t h, int32_t n_queries);
+int relpose_visibility(const RelposeVisibilityArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

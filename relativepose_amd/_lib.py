@@ -187,6 +187,15 @@ class OverlapArgs(C.Structure):
 OVERLAP_EXTENT = -7                 # RELPOSE_OVERLAP_EXTENT
 
 
+class VisibilityArgs(C.Structure):
+    """RelposeVisibilityArgs (include/relpose.h): the argument block of relpose_visibility."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_clouds", c_int), ("n_points", c_int), ("n_views", c_int), ("h", c_int), ("n_queries", c_int),
+                ("dataset", c_int), ("radius", c_int), ("pc", c_void_p), ("valid", c_void_p), ("depth", c_void_p),
+                ("query_cloud_host", c_void_p), ("ref_view_host", c_void_p), ("pose", c_void_p), ("tol_abs", c_double), ("tol_rel", c_double),
+                ("counts", c_void_p), ("margin_sum", c_void_p), ("cls", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("stream", c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -241,6 +250,8 @@ SIGNATURES = {
     "relpose_frames_to_pano": (c_int, [C.POINTER(FramesToPanoArgs)]),
     "relpose_overlap_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "relpose_overlap": (c_int, [C.POINTER(OverlapArgs)]),
+    "relpose_visibility_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "relpose_visibility": (c_int, [C.POINTER(VisibilityArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

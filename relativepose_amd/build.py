@@ -25,6 +25,7 @@ SOURCES = [
     ("normals.hip", ["-ffp-contract=off"]),       # depth normals: count and the nine moments must agree with tests/normals_model.py bit for bit
     ("panorama.hip", ["-ffp-contract=off"]),      # frames to panorama: the f64 geometry and the f32 gate must agree with tests/panorama_model.py bit for bit
     ("overlap.hip", ["-ffp-contract=off"]),        # overlap statistics: hits and the closest-pair distance must agree with tests/overlap_model.py bit for bit
+    ("visibility.hip", ["-ffp-contract=off"]),     # visibility consistency: classes and margins must agree with tests/visibility_model.py bit for bit
     ("scnet.hip", []),
 ]
 

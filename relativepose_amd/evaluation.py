@@ -16,6 +16,9 @@ unchanged" is realised by the build's own eval_pairs-style harness).
   pairs_from_overlap / mine_pairs / save_data_list / load_data_list / SceneBatch
                           the loaders' dataList ({'base','id_src','id_tgt',...} per split, datasets/SUNCG.py:66,91-93), whose generator
                           was never published: which pairs of M posed scans overlap, from util.overlap_matrix_dev
+  select_pose / verify_summary / spearman / observed_depth, evaluate_pairs(verify=...)
+                          no counterpart: the visibility check of an estimated pose against the partner's depth panorama
+                          (util.pose_visibility_dev)
 
 The metrics are host numpy like the reference's (a handful of 3x3 products per pair); overlap and pc_nearest of a batch come from one
 grid-based GPU call (util.point_cloud_overlap_dev), bitwise the values of the per-pair brute-force yardstick
@@ -147,24 +150,76 @@ def _host_pair_stats(pc_src, pc_tgt, R_gt_44):
     return np.linalg.norm(R[:3, 3]), np.linalg.norm(src_trans.mean(1) - pc_tgt.T.mean(1))
 
 
-def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals="given"):
+def select_pose(scores):
+    """Which of K candidate poses per pair the visibility check prefers (host code): scores = util.visibility_scores' dict with entries
+    [B,K] (tensors or arrays) -> int64 numpy [B], the index of the candidate with the highest agreement; ties go to the lower
+    violation_rate, then to the lower index.  A NaN agreement ranks last (among NaNs: the lower violation_rate, a NaN one last, then the
+    lower index)."""
+    host = lambda v: np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.float64)
+    ag, vr = host(scores["agreement"]), host(scores["violation_rate"])
+    if ag.ndim != 2 or ag.shape != vr.shape or ag.shape[1] < 1:
+        raise ValueError("select_pose takes agreement and violation_rate [B,K] with K >= 1")
+    key = lambda b, k: (np.isnan(ag[b, k]), 0.0 if np.isnan(ag[b, k]) else -ag[b, k], np.isnan(vr[b, k]), 0.0 if np.isnan(vr[b, k]) else vr[b, k], k)
+    return np.array([min(range(ag.shape[1]), key=lambda k: key(b, k)) for b in range(ag.shape[0])], dtype=np.int64)
+
+
+VERIFY_MODES = ("observed", "completed")
+
+
+def _verify_depth(pipe, st, verify, kept):
+    """The reference panoramas of the visibility check, [2B,h,4h] f32 on the device.  "observed": the depth under the pipeline's mask, channel 6
+    of util.build_view_dev's output (zero outside the mask): only what the method itself was given.  "completed": the last level's composed
+    depth (1 - m) f[6] + m observed depth, from what run(keep=...) retained."""
+    import torch
+    from . import synth, util
+    if verify == "observed":
+        return util.build_view_dev(st["rgb"], st["norm"], st["depth"], pipe.mask_method)[:, 6].contiguous()
+    y0, y1, x0, x1 = synth.observed_box(pipe.mask_method, st["h"])
+    m = torch.zeros_like(st["depth"][0])
+    m[y0:y1, x0:x1] = 1                                    # the pipeline's mask (util.apply_mask)
+    return ((1 - m) * kept[-1]["f"][:, 6] + m * st["depth"]).contiguous()
+
+
+def _verify_fields(pipe, st, verify, kept, trace, pcs, valid):
+    """Per pair the record fields of evaluate_pairs(verify=...): ONE util.pose_visibility_dev call scores every level's pose of every pair."""
+    from . import util
+    levels = np.stack([t.cpu().numpy() for t in trace], 1)                                 # [B,L,4,4]
+    counts, _, sc = util.pose_visibility_dev(pcs, valid, _verify_depth(pipe, st, verify, kept), levels, pipe.dataset)
+    pick = select_pose(sc)
+    counts = counts.sum(2).cpu().numpy()                                                   # both directions added
+    sc = {k: v.cpu().numpy() for k, v in sc.items()}
+    last = levels.shape[1] - 1
+    return [{'vis_agreement': float(sc["agreement"][b, last]), 'vis_violation_rate': float(sc["violation_rate"][b, last]),
+             'vis_observed': float(sc["observed"][b, last]), 'vis_counts': counts[b, last].copy(), 'vis_level': int(pick[b]),
+             'R_pred_44_selected': levels[b, pick[b]].copy()} for b in range(levels.shape[0])]
+
+
+def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals="given", verify=None):
     """The reference's evaluation loop (evaluation.py:203-320) over an iterable of batches
     ``{"rgb","norm","depth","R" [B,2,4,4], "pts" [B,2,N,2], "ptw" [B,2,N]}`` (the DataLoader dict layout, batched, with the
     injected keypoints; with RelativePosePipeline(keypoints="reference") a batch carries "sift" detections instead, _prepare_batch):
     R_gt = R_t inv(R_s) (:185), overlap statistics from the observed clouds (util.parse_data +
     point_cloud_overlap), the recurrent pipeline on the GPU, then one result record per pair.
-    normals="estimated": a batch needs no "norm"; the normal maps are estimated from the depth panoramas (util.depth_normals_dev)."""
+    normals="estimated": a batch needs no "norm"; the normal maps are estimated from the depth panoramas (util.depth_normals_dev).
+    verify="observed" / "completed": every record gains the visibility check of its pose: the observed clouds of both views
+    against the partner's reference panorama (_verify_depth) -- vis_agreement, vis_violation_rate, vis_observed, vis_counts [6] (both
+    directions added) for the final pose, vis_level = the level select_pose picks among the per-level poses, R_pred_44_selected = that
+    level's pose.  verify=None: the records are what they were."""
     from . import util
+    if verify is not None and verify not in VERIFY_MODES:
+        raise ValueError(f"verify must be None or one of {VERIFY_MODES}")
     stats = []
     k = 0
     for batch in batches:
         B = batch["rgb"].shape[0]
         st = _prepare_batch(pipe, batch, device, normals)
-        pose, status, _ = pipe.run(st)
+        kept = [] if verify == "completed" else None
+        pose, status, trace = pipe.run(st, keep=kept)
         pose = pose.cpu().numpy()
         pcs, valid = util.depth2pc_dev(st["depth"], pipe.dataset)
         R_gts = [np.matmul(batch["R"][b, 1], np.linalg.inv(batch["R"][b, 0])) for b in range(B)]
         ovs, nns = _pair_overlap_stats(pcs, valid, R_gts)
+        vis = _verify_fields(pipe, st, verify, kept, trace, pcs, valid) if verify is not None else None
         pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
         for b in range(B):
             R_gt_44 = R_gts[b]
@@ -173,10 +228,48 @@ def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals=
             cam_dist, pc_dist = _host_pair_stats(pc_src, pc_tgt, R_gt_44)
             nm = names[k] if names is not None else (f"pair{k}/src", f"pair{k}/tgt")
             stats.append(result_record(nm[0], nm[1], pose[b], R_gt_44, pc_src, ov, pc_dist, cam_dist, pc_nn))
+            if vis is not None:
+                stats[-1].update(vis[b])
             k += 1
     if result_path is not None:
         save_results(result_path, stats)
     return stats
+
+
+def spearman(a, b):
+    """Spearman's rank correlation of two sequences (numpy ranks, ties averaged); pairs with a NaN are left out; NaN when fewer than two pairs
+    remain or a side is constant."""
+    a, b = np.asarray(a, dtype=np.float64).reshape(-1), np.asarray(b, dtype=np.float64).reshape(-1)
+    ok = ~(np.isnan(a) | np.isnan(b))
+    a, b = a[ok], b[ok]
+    if a.size < 2:
+        return float("nan")
+
+    def rank(x):
+        order = np.argsort(x, kind="stable")
+        r = np.empty(x.size)
+        r[order] = np.arange(x.size, dtype=np.float64)
+        _, inv, cnt = np.unique(x, return_inverse=True, return_counts=True)
+        return (np.bincount(inv, r) / cnt)[inv]
+
+    ra, rb = rank(a) - rank(a).mean(), rank(b) - rank(b).mean()
+    den = np.sqrt((ra * ra).sum() * (rb * rb).sum())
+    return float((ra * rb).sum() / den) if den > 0 else float("nan")
+
+
+def verify_summary(stats):
+    """What the CLI reports about records that carry the visibility fields: the Spearman rank correlation of vis_agreement with err_ad and
+    with err_t, and per overlap bucket the mean rotation error of the selected level next to that of the last level."""
+    ag = [e['vis_agreement'] for e in stats]
+    out = {"vis_spearman_rot": spearman(ag, [e['err_ad'] for e in stats]), "vis_spearman_trans": spearman(ag, [e['err_t'] for e in stats]),
+           "vis_selected": {}}
+    for ov in OVERLAPS:
+        rows = [e for e in stats if overlap_bucket(e['overlap']) == ov]
+        if rows:
+            sel = [angular_distance_np(e['R_pred_44_selected'][:3, :3].reshape(1, 3, 3), e['R_gt'][:3, :3].reshape(1, 3, 3))[0] for e in rows]
+            out["vis_selected"][ov] = {"nobs": len(rows), "err_ad_last": float(np.mean([e['err_ad'] for e in rows])),
+                                       "err_ad_selected": float(np.mean(sel))}
+    return out
 
 
 def evaluate_from_frames(pipe, batches, device, Hf=480, Wf=640):
@@ -270,18 +363,41 @@ def pairs_from_overlap(frac, base, ids, min_overlap=None):
     return out
 
 
-def mine_pairs(depth, R, dataset, base, ids=None, min_overlap=None, max_dist=0.08, device=None):
+def observed_depth(depth, dataset):
+    """depth [n,h,4h] f32 tensor -> the same with everything outside the dataset's observed box zeroed (the kinect window for scannet, the
+    second face otherwise): channel 6 of util.build_view_dev's output, the reference panorama of verify="observed"."""
+    import torch
+    from . import synth
+    y0, y1, x0, x1 = synth.observed_box("kinect" if "scannet" in dataset else "second", depth.shape[1])
+    out = torch.zeros_like(depth)
+    out[:, y0:y1, x0:x1] = depth[:, y0:y1, x0:x1]
+    return out
+
+
+def mine_pairs(depth, R, dataset, base, ids=None, min_overlap=None, max_dist=0.08, device=None, verify=None):
     """Which pairs of M posed scans of one scene overlap, and by how much: depth [M,h,4h] float32 panoramas (numpy or a CUDA tensor),
     R [M,4,4] world -> camera poses (the loaders' convention) -> pairs_from_overlap's entries.  The observed clouds (util.depth2pc_dev),
-    ONE grid-based overlap call over the M (M - 1) directed pairs (util.overlap_matrix_dev) and the host pair list."""
+    ONE grid-based overlap call over the M (M - 1) directed pairs (util.overlap_matrix_dev) and the host pair list.
+    verify="observed": every entry gains 'vis_agreement', the visibility agreement of the pair under its poses with both directions pooled
+    (util.visibility_matrix_dev on the observed clouds against the observed depth; NaN when no point of either lands on data)."""
     import torch
     from . import _lib, util
+    if verify not in (None, "observed"):
+        raise ValueError("mine_pairs takes verify=None or 'observed'")
     dev = device if device is not None else _lib.require_gpu()
     d = depth if isinstance(depth, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(dev)
     pc, valid = util.depth2pc_dev(d, dataset)
     frac, _, _ = util.overlap_matrix_dev(pc, valid, R, max_dist)
     M = d.shape[0]
-    return pairs_from_overlap(frac.cpu().numpy(), base, list(range(M)) if ids is None else list(ids), min_overlap)
+    ids = list(range(M)) if ids is None else list(ids)
+    out = pairs_from_overlap(frac.cpu().numpy(), base, ids, min_overlap)
+    if verify is not None:
+        counts, margin, _ = util.visibility_matrix_dev(pc, valid, observed_depth(d, dataset), R, dataset)
+        ag = util.visibility_scores(counts + counts.transpose(0, 1), margin + margin.transpose(0, 1))["agreement"].cpu().numpy()
+        pos = {v: k for k, v in enumerate(ids)}
+        for e in out:
+            e['vis_agreement'] = float(ag[pos[e['id_src']], pos[e['id_tgt']]])
+    return out
 
 
 def save_data_list(path, lists):
@@ -399,31 +515,31 @@ def _default_record(pipe, sub, poses, device, names, ks):
     return out
 
 
-def evaluate_fgs(batches, device, dataset, result_path=None, max_points=None, seed=0):
+def evaluate_fgs(batches, device, dataset, result_path=None, max_points=None, seed=0, verify=None):
     """The reference's `--method fgs` loop (evaluation.py:182-203, 286-320) over batches of synthetic pairs: the observed-block clouds
     of both views (util.depth2pc_dev, as _default_record builds them), ONE batched FPFH + fast global registration call per batch
     (baselines.fast_global_registration_dev), then per pair the overlap statistics; pairs with overlap < 0.1 are skipped without a
     record (evaluation.py:190-191).  Returns the record list (the reference's keys + 'status'); written to result_path if given."""
     from . import _lib, baselines
     reg = lambda pcs, valid: baselines.fast_global_registration_dev(pcs, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)[:2]
-    return _evaluate_baseline(batches, device, dataset, reg, result_path)
+    return _evaluate_baseline(batches, device, dataset, reg, result_path, verify=verify)
 
 
-def evaluate_gs(batches, device, dataset, result_path=None, max_points=None, seed=0):
+def evaluate_gs(batches, device, dataset, result_path=None, max_points=None, seed=0, verify=None):
     """The reference's `--method gs` loop: as evaluate_fgs, with ONE batched FPFH + RANSAC call per batch
     (baselines.global_registration_dev, baselines.py:52-81)."""
     from . import _lib, baselines
     reg = lambda pcs, valid: baselines.global_registration_dev(pcs, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)[:2]
-    return _evaluate_baseline(batches, device, dataset, reg, result_path)
+    return _evaluate_baseline(batches, device, dataset, reg, result_path, verify=verify)
 
 
-def evaluate_cgs(batches, device, dataset, result_path=None, max_points=None, seed=0):
+def evaluate_cgs(batches, device, dataset, result_path=None, max_points=None, seed=0, verify=None):
     """The reference's `--method cgs` loop: as evaluate_gs, with the RANSAC pose of every pair refined by the three coloured ICP levels
     (baselines.color_registration_dev, baselines.py:110-168).  The colours are the observed block of `rgb` in the clouds' point order,
     quantised as the reference does: clip(rgb * 255, 0, 255) to uint8 (evaluation.py:168), then / 255 (util.py:53)."""
     from . import _lib, baselines
     reg = lambda pcs, valid, colors: baselines.color_registration_dev(pcs, colors, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)[:2]
-    return _evaluate_baseline(batches, device, dataset, reg, result_path, with_colors=True)
+    return _evaluate_baseline(batches, device, dataset, reg, result_path, with_colors=True, verify=verify)
 
 
 def observed_colors(rgb):
@@ -434,11 +550,14 @@ def observed_colors(rgb):
     return np.ascontiguousarray(q[:, :, :, h:2 * h].transpose(0, 2, 3, 1).reshape(len(q), h * h, 3)) / 255.
 
 
-def _evaluate_baseline(batches, device, dataset, register, result_path, with_colors=False):
+def _evaluate_baseline(batches, device, dataset, register, result_path, with_colors=False, verify=None):
     """register(pcs, valid) -> (pose [B,4,4], status [B]) tensors for the observed-block clouds of a batch; with_colors: register(pcs,
-    valid, colors [2B,P,3] f64)."""
+    valid, colors [2B,P,3] f64).  verify="observed": the records gain evaluate_pairs' visibility fields for the baseline's one pose (vis_level
+    is 0); a baseline completes nothing, so there is no "completed"."""
     import torch
     from . import util
+    if verify not in (None, "observed"):
+        raise ValueError("the baselines take verify=None or 'observed'")
     stats = []
     for batch in batches:
         n = _batch_size(batch)
@@ -453,6 +572,9 @@ def _evaluate_baseline(batches, device, dataset, register, result_path, with_col
         pose, status = pose.cpu().numpy(), status.cpu().numpy()
         R_gts = [np.matmul(sub["R"][q, 1], np.linalg.inv(sub["R"][q, 0])) for q in range(n)]
         ovs, nns = _pair_overlap_stats(pcs, valid, R_gts)
+        if verify is not None:
+            vcounts, _, vsc = util.pose_visibility_dev(pcs, valid, observed_depth(depth, dataset), pose[:, None], dataset)
+            vcounts, vsc = vcounts.sum(2).cpu().numpy(), {k: v.cpu().numpy() for k, v in vsc.items()}
         pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
         for q in range(n):
             R_gt_44 = R_gts[q]
@@ -466,6 +588,10 @@ def _evaluate_baseline(batches, device, dataset, register, result_path, with_col
             k = len(stats)
             rec = result_record(f"pair{k}/src", f"pair{k}/tgt", pose[q], R_gt_44, pc_src, ov, pc_dist, cam_dist, pc_nn)
             rec['status'] = int(status[q])
+            if verify is not None:
+                rec.update(vis_agreement=float(vsc["agreement"][q, 0]), vis_violation_rate=float(vsc["violation_rate"][q, 0]),
+                           vis_observed=float(vsc["observed"][q, 0]), vis_counts=vcounts[q, 0].copy(), vis_level=0,
+                           R_pred_44_selected=rec['R_pred_44'].copy())
             stats.append(rec)
     if result_path is not None:
         save_results(result_path, stats)
@@ -774,6 +900,13 @@ def _cli_parser_completion():
     ap.add_argument("--pair-source", choices=["pairs", "scenes"], default="pairs",
                     help="--method ours / fgs / gs / cgs: scenes = the pairs are mined from multi-view scenes (SceneBatch, equal numbers from "
                          "the three overlap buckets) instead of synth.make_pairs' two unrelated poses per room, which almost never overlap")
+    ap.add_argument("--verify", choices=list(VERIFY_MODES), default=None,
+                    help="check every estimated pose against the partner view's depth panorama (util.pose_visibility_dev, DESIGN.md 4.15): "
+                         "observed = against the depth under the pipeline's mask, completed = against the last level's completed depth "
+                         "(--method ours only).  --method ours (one GPU, given keypoints) / fgs / gs / cgs: the records gain the vis_* fields "
+                         "and the JSON line vis_spearman_rot, vis_spearman_trans (rank correlation of vis_agreement with err_ad / err_t) and "
+                         "vis_selected (per bucket the mean rotation error of the level the check selects next to the last level's); "
+                         "--mine-pairs --verify observed: the mined entries gain vis_agreement")
     return ap
 
 
@@ -793,6 +926,14 @@ def main(argv=None):
         raise SystemExit("--normals estimated applies to --method ours (the pose evaluation): the baselines and the descriptor / completion "
                          "metrics do not read the views' normal maps as an input of the pipeline")
 
+    if args.verify is not None:
+        if args.descriptor_eval or args.completion_eval or args.from_frames:
+            raise SystemExit("--verify applies to the pose evaluation (--method ours / fgs / gs / cgs) and to --mine-pairs")
+        if args.verify == "completed" and (args.mine_pairs or args.method != "ours"):
+            raise SystemExit("--verify completed needs the network's completed depth: --method ours only")
+        if args.gpus > 1 or (not args.mine_pairs and args.method == "ours" and args.keypoint_mode != "given"):
+            raise SystemExit("--verify runs on one GPU (--gpus 1) with given keypoints: the check is not sharded")
+
     if args.mine_pairs:
         if args.gpus > 1:
             raise SystemExit("--mine-pairs runs on one GPU (--gpus 1)")
@@ -805,13 +946,18 @@ def main(argv=None):
         t0 = time.perf_counter()
         for s in range(args.scenes):
             sc = synth.render_scene(args.seed + s, args.scene_views, args.dataset)
-            entries += mine_pairs(sc["depth"], sc["R"], args.dataset, f"scene{args.seed + s}", min_overlap=args.min_overlap, device=dev)
+            entries += mine_pairs(sc["depth"], sc["R"], args.dataset, f"scene{args.seed + s}", min_overlap=args.min_overlap, device=dev,
+                                  verify=args.verify)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         path = None if args.exp is None else save_data_list(args.exp + ".datalist.npy", {"test": entries})
         per = {k: sum(1 for e in entries if overlap_bucket(e['overlap']) == k) for k in OVERLAPS}
-        print(json.dumps({"mine_pairs": True, "dataset": args.dataset, "scenes": args.scenes, "views": args.scene_views, "pairs": len(entries),
-                          "pairs_per_bucket": per, "min_overlap": args.min_overlap, "seconds": dt, "data_list": path}), flush=True)
+        line = {"mine_pairs": True, "dataset": args.dataset, "scenes": args.scenes, "views": args.scene_views, "pairs": len(entries),
+                "pairs_per_bucket": per, "min_overlap": args.min_overlap, "seconds": dt, "data_list": path}
+        if args.verify is not None:
+            line["vis_agreement_mean_per_bucket"] = {k: float(np.nanmean([e['vis_agreement'] for e in entries if overlap_bucket(e['overlap']) == k] or [np.nan]))
+                                                     for k in OVERLAPS}
+        print(json.dumps(line), flush=True)
         return
 
     if args.pair_source == "scenes" and (args.descriptor_eval or args.completion_eval or args.from_frames or args.keypoint_mode != "given"):
@@ -916,11 +1062,40 @@ def main(argv=None):
                    for k in range(0, args.pairs, args.batch)]
         path = None if args.exp is None else args.exp + ".result.npy"
         t0 = time.perf_counter()
-        stats = {"fgs": evaluate_fgs, "gs": evaluate_gs, "cgs": evaluate_cgs}[m](batches, dev, args.dataset, result_path=path)
+        stats = {"fgs": evaluate_fgs, "gs": evaluate_gs, "cgs": evaluate_cgs}[m](batches, dev, args.dataset, result_path=path, verify=args.verify)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(json.dumps({"method": m, "pairs": args.pairs, "records": len(stats), "seconds": dt, "result_file": path,
-                          "dataset": args.dataset, "stats": summarize(stats)}), flush=True)
+        line = {"method": m, "pairs": args.pairs, "records": len(stats), "seconds": dt, "result_file": path,
+                "dataset": args.dataset, "stats": summarize(stats)}
+        if args.verify is not None:
+            line.update(verify=args.verify, **verify_summary(stats))
+        print(json.dumps(line), flush=True)
+        return
+
+    if args.verify is not None:                   # --method ours: the unsharded loop, which keeps every level's pose (and output) for the check
+        import torch
+        from types import SimpleNamespace
+        from . import _lib, params, weights
+        from .model import SCNet
+        from .pipeline import RelativePosePipeline
+        dev = _lib.require_gpu()
+        ds = args.dataset
+        mm, S, tanh = ("kinect", 21, 0) if ds == "scannet" else ("second", 21 if ds == "matterport" else 15, 1)
+        net = SCNet(SimpleNamespace(batchnorm=1, useTanh=tanh, skipLayer=1, outputType="rgbdnsf", snumclass=S))
+        net.load_state_dict(weights.make_state_dict(7, S))
+        net.set_precision(args.precision)
+        pipe = RelativePosePipeline(net, ds, mm, params.final_params(ds), completion=args.completion)
+        lazy = [make_batch(min(args.batch, args.pairs - k), args.seed + k, ds, mm) or
+                SyntheticBatch(min(args.batch, args.pairs - k), args.seed + k, ds, mm, args.keypoints) for k in range(0, args.pairs, args.batch)]
+        path = None if args.exp is None else args.exp + ".result.npy"
+        t0 = time.perf_counter()
+        stats = evaluate_pairs(pipe, (_batch_take(b, np.arange(_batch_size(b))) for b in lazy), dev, result_path=path, normals=args.normals,
+                               verify=args.verify)
+        torch.cuda.synchronize()
+        line = {"pairs": len(stats), "seconds": time.perf_counter() - t0, "n_gpus": 1, "result_file": path, "dataset": ds,
+                "stats": summarize(stats), "verify": args.verify}
+        line.update(verify_summary(stats))
+        print(json.dumps(line), flush=True)
         return
 
     def worker():

@@ -41,6 +41,7 @@ Operator                    replaces (reference file:line)
   depth_normals             the normal/ maps the loaders read from disk, datasets/SUNCG.py:300-313 (estimated from the depth panoramas)
   frames_to_pano            the depth/ and rgb/ panoramas the ScanNet loader reads next to its frames, datasets/ScanNet.py:211-230 (built from the frames)
   overlap                   the two KDTree queries of util.point_cloud_overlap, util.py:21-40 (batched over directed cloud pairs, one grid per cloud)
+  visibility                no counterpart: the free-space check of a relative pose against the partner's depth panorama
   affinity_topk             rpmodule.py:342-379
   match_pairs               RelativePoseEstimation_helper, rpmodule.py:317-508
 """
@@ -104,6 +105,10 @@ _lib.define("frames_to_pano(Tensor depth, Tensor rgb, Tensor scale, Tensor? pose
 # pc f64 [n,P,3], valid u8 [n,P] (optional), query_cloud / ref_cloud integer [Q] (read on the host), pose f64 [Q,4,4] (query -> reference frame)
 # -> hits i32 [Q], nn_min f64 [Q], n_valid i32 [n]
 _lib.define("overlap(Tensor pc, Tensor? valid, Tensor query_cloud, Tensor ref_cloud, Tensor pose, float max_dist=0.08) -> (Tensor, Tensor, Tensor)")
+# pc f64 [n,P,3], valid u8 [n,P] (optional), depth f32 [V,h,4h], query_cloud / ref_view integer [Q] (read on the host), pose f64 [Q,4,4]
+# (query cloud -> reference view's frame) -> counts i32 [Q,6], margin_sum i64 [Q], cls u8 [Q,P]
+_lib.define("visibility(Tensor pc, Tensor? valid, Tensor depth, Tensor query_cloud, Tensor ref_view, Tensor pose, int dataset, "
+            "float tol_abs=0.05, float tol_rel=0.02, int radius=1) -> (Tensor, Tensor, Tensor)")
 _lib.define("affinity_topk(Tensor feat_s, Tensor weight_s, Tensor feat_t, Tensor weight_t, Tensor ns, Tensor nt, "
             "float[] params, int topK, bool want_wij) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("match_pairs(Tensor pc_s, Tensor normal_s, Tensor feat_s, Tensor weight_s, Tensor pc_t, Tensor normal_t, "
@@ -256,6 +261,11 @@ def _overlap(pc, valid, query_cloud, ref_cloud, pose, max_dist=0.08):
     return _util.overlap_dev(pc, valid, query_cloud, ref_cloud, pose, float(max_dist))
 
 
+def _visibility(pc, valid, depth, query_cloud, ref_view, pose, dataset, tol_abs=0.05, tol_rel=0.02, radius=1):
+    return _util.visibility_dev(pc, valid, depth, query_cloud, ref_view, pose, _INV_DATASET[int(dataset)], float(tol_abs), float(tol_rel),
+                                int(radius), want_class=True)
+
+
 def _affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     wij, cj, cw, keff = _rp.affinity_topk(feat_s.contiguous(), weight_s.contiguous(), feat_t.contiguous(), weight_t.contiguous(),
                                           ns.contiguous(), nt.contiguous(), _para(params, topK), want_wij=bool(want_wij))
@@ -278,7 +288,7 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("global_registration", _global_registration), ("colored_icp", _colored_icp), ("color_registration", _color_registration),
                    ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank),
                    ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals),
-                   ("frames_to_pano", _frames_to_pano), ("overlap", _overlap)):
+                   ("frames_to_pano", _frames_to_pano), ("overlap", _overlap), ("visibility", _visibility)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -408,6 +418,11 @@ def _m_overlap(pc, valid, query_cloud, ref_cloud, pose, max_dist=0.08):
     return pc.new_empty(Q, dtype=torch.int32), pc.new_empty(Q, dtype=torch.float64), pc.new_empty(n, dtype=torch.int32)
 
 
+def _m_visibility(pc, valid, depth, query_cloud, ref_view, pose, dataset, tol_abs=0.05, tol_rel=0.02, radius=1):
+    P, Q = pc.shape[1], pose.shape[0]
+    return pc.new_empty(Q, 6, dtype=torch.int32), pc.new_empty(Q, dtype=torch.int64), pc.new_empty(Q, P, dtype=torch.uint8)
+
+
 def _m_affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     B, ns_max, nt_max = feat_s.shape[0], feat_s.shape[1], feat_t.shape[1]
     wij = feat_s.new_empty(B, ns_max, nt_max, dtype=torch.float32) if want_wij else feat_s.new_empty(0)
@@ -427,10 +442,10 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("global_registration", _m_global_registration), ("colored_icp", _m_colored_icp), ("color_registration", _m_color_registration),
                    ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank),
                    ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals),
-                   ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap)):
+                   ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap), ("visibility", _m_visibility)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
        "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals",
-       "frames_to_pano", "overlap")
+       "frames_to_pano", "overlap", "visibility")

@@ -478,6 +478,131 @@ def overlap_matrix_dev(pc, valid, R, max_dist=0.08):
     return frac, nn, n_valid
 
 
+VIS_CLASSES = ("invalid", "outside", "unobserved", "consistent", "violation", "occluded")      # relpose_visibility's classes 0..5
+
+
+def visibility_dev(pc, valid, depth, query_cloud, ref_view, pose, dataset, tol_abs=0.05, tol_rel=0.02, radius=1, want_class=False):
+    """relpose_visibility (include/relpose.h): pc [n,P,3] f64 and valid [n,P] u8 (or None: all valid) CUDA tensors in
+    depth2pc_dev's layout; depth [V,h,4h] f32 CUDA reference panoramas (not finite or <= 0 = no data); query_cloud, ref_view: n_queries
+    cloud / view indices (any integer sequence, array or tensor; they are read on the host); pose [n_queries,4,4] f64 CUDA, query cloud ->
+    the reference view's frame.  Every moved point is projected into the reference panorama and compared with the (2 radius + 1)^2 window
+    of depths around its pixel: VIS_CLASSES names the six classes.
+    -> (counts [n_queries,6] i32, margin_sum [n_queries] i64: the violations' depth margins in 1/65536), and cls [n_queries,P] u8 with
+    want_class.  The defaults are parameters of the library, not claims about real sensors.  The call waits for the stream once, at its end."""
+    import torch
+    _lib.require_gpu()
+    as_host = lambda v: np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.int32).reshape(-1)
+    qc, rv = as_host(query_cloud), as_host(ref_view)
+    if pc.dim() != 3 or pc.shape[2] != 3 or pc.dtype != torch.float64:
+        raise ValueError("visibility_dev takes pc [n,P,3] float64")
+    if depth.dim() != 3 or depth.shape[2] != 4 * depth.shape[1] or depth.dtype != torch.float32 or depth.device != pc.device:
+        raise ValueError("visibility_dev takes depth [V,h,4h] float32 on pc's device")
+    n, P = int(pc.shape[0]), int(pc.shape[1])
+    V, h = int(depth.shape[0]), int(depth.shape[1])
+    nq = len(qc)
+    if len(rv) != nq or tuple(pose.shape) != (nq, 4, 4) or pose.dtype != torch.float64:
+        raise ValueError("visibility_dev takes one reference view and one float64 4x4 pose per query")
+    if valid is not None and (tuple(valid.shape) != (n, P) or valid.dtype != torch.uint8):
+        raise ValueError("visibility_dev takes valid [n,P] uint8")
+    if int(radius) not in (0, 1, 2) or not (np.isfinite(tol_abs) and tol_abs >= 0 and np.isfinite(tol_rel) and tol_rel >= 0):
+        raise ValueError("visibility_dev takes radius 0, 1 or 2 and finite tolerances >= 0")
+    dev = pc.device
+    counts = torch.zeros(nq, 6, dtype=torch.int32, device=dev)
+    margin = torch.zeros(nq, dtype=torch.int64, device=dev)
+    cls = torch.zeros(nq, P, dtype=torch.uint8, device=dev) if want_class else None
+    if nq == 0 or n == 0 or P == 0:
+        return (counts, margin, cls) if want_class else (counts, margin)
+    L = _lib.lib()
+    nbytes = L.relpose_visibility_workspace_bytes(V, h, nq)
+    if nbytes == 0:
+        raise ValueError("visibility_dev: sizes outside relpose_visibility's limits")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    pcc, vc, dc, posec = pc.contiguous(), (None if valid is None else valid.contiguous()), depth.contiguous(), pose.contiguous()
+    a = _lib.VisibilityArgs()
+    a.struct_size = _lib.C.sizeof(_lib.VisibilityArgs)
+    a.n_clouds, a.n_points, a.n_views, a.h, a.n_queries = n, P, V, h, nq
+    a.dataset, a.radius = dataset_id(dataset), int(radius)
+    a.pc, a.valid, a.depth, a.pose = pcc.data_ptr(), (0 if vc is None else vc.data_ptr()), dc.data_ptr(), posec.data_ptr()
+    a.query_cloud_host, a.ref_view_host = qc.ctypes.data, rv.ctypes.data
+    a.tol_abs, a.tol_rel = float(tol_abs), float(tol_rel)
+    a.counts, a.margin_sum, a.cls = counts.data_ptr(), margin.data_ptr(), (cls.data_ptr() if want_class else 0)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.stream = _lib.stream_ptr()
+    rc_ = L.relpose_visibility(_lib.C.byref(a))
+    if rc_ == -1:
+        raise ValueError("relpose_visibility: invalid arguments (an index out of range, h odd or < 2 radius + 1, or sizes outside the limits)")
+    _lib.check(rc_, "relpose_visibility")
+    return (counts, margin, cls) if want_class else (counts, margin)
+
+
+def visibility_scores(counts, margin_sum):
+    """The ratios behind a visibility verdict: counts [...,6], margin_sum [...] (visibility_dev's, or sums of them) -> a dict of float64
+    tensors [...]: with c, v, o = the consistent, violation and occluded counts, agreement = c / (c + v + o), violation_rate = v / (c + v + o),
+    observed = (c + v + o) / (n_points - invalid), mean_violation = margin_sum / 65536 / v (the mean depth by which a violating point stands
+    in front of the measured surface).  An entry is NaN where its denominator is 0."""
+    import torch
+    cn = counts.to(torch.float64)
+    c, v, o = cn[..., 3], cn[..., 4], cn[..., 5]
+    seen = (c + v) + o
+    n = cn.sum(-1) - cn[..., 0]
+    nan = torch.full_like(seen, float("nan"))
+    div = lambda a, b: torch.where(b > 0, a / torch.where(b > 0, b, torch.ones_like(b)), nan)
+    return {"agreement": div(c, seen), "violation_rate": div(v, seen), "observed": div(seen, n),
+            "mean_violation": div(margin_sum.to(torch.float64) / 65536.0, v)}
+
+
+def pose_visibility_dev(pc, valid, depth, T, dataset, tol_abs=0.05, tol_rel=0.02, radius=1):
+    """Visibility scores of K candidate poses per pair without leaving the device: pc [2B,P,3] f64, valid [2B,P] u8, depth [2B,h,4h] f32
+    CUDA tensors in point_cloud_overlap_dev's paired layout (cloud and view 2b = the source of pair b, 2b + 1 its target), T [B,K,4,4] host
+    float64 candidates, source -> target.  ONE relpose_visibility call with the 2 B K directed queries (source cloud into the target view
+    under T, target cloud into the source view under np.linalg.inv(T) from the host).
+    -> (counts [B,K,2,6] i32, margin_sum [B,K,2] i64 per direction, scores: visibility_scores of both directions' sums, [B,K] each)."""
+    import torch
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    if T.ndim != 4 or T.shape[2:] != (4, 4) or pc.shape[0] != 2 * T.shape[0] or depth.shape[0] != pc.shape[0]:
+        raise ValueError("pose_visibility_dev takes T [B,K,4,4] and two clouds and two views per pair")
+    B, K = T.shape[:2]
+    poses = np.empty((B, K, 2, 4, 4))
+    qc = np.empty((B, K, 2), np.int32)
+    rv = np.empty((B, K, 2), np.int32)
+    for b in range(B):
+        for k in range(K):
+            poses[b, k, 0] = T[b, k]
+            poses[b, k, 1] = np.linalg.inv(T[b, k])
+        qc[b, :, 0], rv[b, :, 0] = 2 * b, 2 * b + 1
+        qc[b, :, 1], rv[b, :, 1] = 2 * b + 1, 2 * b
+    counts, margin = visibility_dev(pc, valid, depth, qc, rv, torch.from_numpy(poses.reshape(-1, 4, 4)).to(pc.device), dataset,
+                                    tol_abs, tol_rel, radius)
+    counts, margin = counts.reshape(B, K, 2, 6), margin.reshape(B, K, 2)
+    return counts, margin, visibility_scores(counts.sum(2), margin.sum(2))
+
+
+def visibility_matrix_dev(pc, valid, depth, R, dataset, tol_abs=0.05, tol_rel=0.02, radius=1):
+    """Visibility of every directed pair of M posed views: pc [M,P,3] f64, valid [M,P] u8, depth [M,h,4h] f32 CUDA tensors, R [M,4,4] host
+    float64 world -> camera poses (overlap_matrix_dev's convention; T_ij = R_j inv(R_i) moves cloud i into view j's frame).
+    -> (counts [M,M,6] i32, margin_sum [M,M] i64, scores: visibility_scores per directed pair, [M,M] each) from ONE relpose_visibility call
+    with M (M - 1) queries.  The diagonal is not computed: its counts are 0 and its scores NaN."""
+    import torch
+    R = np.ascontiguousarray(R, dtype=np.float64).reshape(-1, 4, 4)
+    M = R.shape[0]
+    if pc.shape[0] != M or depth.shape[0] != M:
+        raise ValueError("visibility_matrix_dev takes one pose and one panorama per cloud")
+    dev = pc.device
+    inv = [np.linalg.inv(R[i]) for i in range(M)]
+    ij = [(i, j) for i in range(M) for j in range(M) if i != j]
+    counts = torch.zeros(M, M, 6, dtype=torch.int32, device=dev)
+    margin = torch.zeros(M, M, dtype=torch.int64, device=dev)
+    if ij:
+        poses = np.stack([np.matmul(R[j], inv[i]) for i, j in ij])
+        qi = torch.tensor([i for i, _ in ij], device=dev)
+        qj = torch.tensor([j for _, j in ij], device=dev)
+        cn, mg = visibility_dev(pc, valid, depth, [i for i, _ in ij], [j for _, j in ij], torch.from_numpy(poses).to(dev), dataset,
+                                tol_abs, tol_rel, radius)
+        counts[qi, qj] = cn
+        margin[qi, qj] = mg
+    return counts, margin, visibility_scores(counts, margin)
+
+
 def depth2pc(depth, dataList):
     """util.py:468: depth numpy = one h x h face (suncg / matterport) or the 66x88 kinect crop (scannet)
     -> (pc [k,3] of the non-zero depths, mask)."""
