@@ -94,10 +94,15 @@ void relpose_default_params(RelposeParams* p_host);
  *                                   up its plan: each value has plans of its own
  *   RELPOSE_TUNE_ZERO_TILES         0 = SCNet's conv2 / conv3 tile kernels run only the patches whose receptive field holds a non-zero
  *                                   input pixel plus one representative per edge class, the others are copies (default), 1 = every
- *                                   patch is computed (same bits); read when a forward looks up its plan, like RELPOSE_TUNE_DECONV_STRIP */
+ *                                   patch is computed (same bits); read when a forward looks up its plan, like RELPOSE_TUNE_DECONV_STRIP
+ *   RELPOSE_TUNE_CONV1_ZERO         0 = SCNet's input resize writes the occupancy words of the zero-tile lists itself, and conv1 neither
+ *                                   computes nor stores an (image, stream, 8 x 32 tile) block of A1 whose inputs are all +-0 and whose
+ *                                   zeros an earlier forward on the workspace left there (it stores +0.0 once otherwise) (default),
+ *                                   1 = a separate occupancy pass, every launched block computed and stored (same bits); read by every
+ *                                   forward (the plans are the same); without the zero-tile lists (RELPOSE_TUNE_ZERO_TILES = 1) 1 is what runs */
 enum { RELPOSE_TUNE_AFFINITY_KERNEL = 0, RELPOSE_TUNE_FIT_MAX_PRODUCTS = 1, RELPOSE_TUNE_FIT_CLUSTER = 2,
        RELPOSE_TUNE_FIT_GLOBAL_VECTORS = 3, RELPOSE_TUNE_FIT_FIXED_CHECKS = 4, RELPOSE_TUNE_HEADS_KERNEL = 5, RELPOSE_TUNE_DECONV_STRIP = 6,
-       RELPOSE_TUNE_ZERO_TILES = 7, RELPOSE_TUNE_COUNT = 8 };
+       RELPOSE_TUNE_ZERO_TILES = 7, RELPOSE_TUNE_CONV1_ZERO = 8, RELPOSE_TUNE_COUNT = 9 };
 int relpose_set_tuning(int32_t key, int32_t value);
 const char* relpose_version(void);
 /* ------------------------------------------------------------------ matcher
@@ -1093,6 +1098,12 @@ int relpose_scnet_layer_kernel(RelposeSCNet* net, const char* layer, int32_t n_i
  * {conv2 computed, conv2 dropped, conv3 computed, conv3 dropped}, in workgroups (conv2: one 16 x 16 patch, conv3: a pair of 8 x 8
  * patches), summed over the launch members of that forward's plan.  Synchronises `stream` (the forward's).  For tests and profiles. */
 int relpose_scnet_zero_tiles(RelposeSCNet* net, void* workspace, void* stream, int64_t* counts_host);
+
+/* conv1's zero units in the last forward (RELPOSE_TUNE_CONV1_ZERO): counts_host[3] = {launched, skipped without a store, stored as zeros},
+ * in (image, stream, 8 x 32 tile) blocks of A1; the last two are 0 when conv1 computed every block (the knob set, no zero-tile lists, or a
+ * non-finite conv1 weight).  occ_host, if not NULL, receives that forward's occupancy words [n_images][6][28] (RELPOSE_EINVAL if it ran
+ * without the zero-tile lists).  Synchronises `stream` (the forward's).  For tests and profiles. */
+int relpose_scnet_conv1_zero(RelposeSCNet* net, void* workspace, void* stream, int64_t* counts_host, uint32_t* occ_host);
 
 /* Debug: copy a raw (pre-BatchNorm) layer output of the last forward, NHWC float32, to out (device).
  * Returns the number of floats written (or needed if out is NULL), <0 if unknown. */

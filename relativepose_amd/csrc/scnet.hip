@@ -24,6 +24,7 @@
 //  * bilinear resize kernels (align_corners=False) in and out.
 #include "common.h"
 #include "matcher_internal.h"      // g_rp_tune
+#include "conv1_zero_geom.h"        // c1z_range: conv1's zero-unit test
 #include <map>
 #include <string>
 #include <vector>
@@ -61,6 +62,7 @@ constexpr bool rp_split3(int split) { return split >= 4; }
 constexpr float LRELU = 0.1f;
 constexpr double BN_EPS = 1e-5;
 constexpr int RS = 224;         // internal resolution (mymodel.py:261)
+static_assert(RS == C1Z_RS, "conv1_zero_geom.h");
 
 struct Src {
     const float* x;        // NHWC base (+ channel offset)
@@ -1662,14 +1664,50 @@ constexpr int C1_PASSES_PER_GROUP = 2 * RS * RS / 256;      // 392
 // One {sum, sum of squares} record per tile and channel: stat[group][(img & 1) * 196 + tile][192][2] (C1_PASSES_PER_GROUP).
 constexpr int C1T_PS = 17;                          // LDS pixel stride (floats)
 constexpr int C1T_XIN = 10 * 34 * C1T_PS;
+// Zero units (RELPOSE_TUNE_CONV1_ZERO; occ != null): conv1 has no bias, so where the occupancy words (resize_in_occ_kernel)
+// show only +-0 in a stream's channels over the tile and its one-pixel halo (c1z_range), that stream's block of the A1 tile is +0.0
+// everywhere and its statistics record is +0.0.  a1z[img][q][tile] = 1 says the block already holds those zeros (written by the forward
+// that set the byte; the host clears the bytes whenever it cannot vouch for A1: relpose_scnet_forward_ex).  Per launched stream:
+//   unit zero, byte 1 -> no MFMAs, no stores;  unit zero, byte 0 -> the same store instructions write +0.0, the byte becomes 1;
+//   otherwise -> computed as ever, the byte becomes 0.
+// A workgroup whose launched streams are all of the first kind stages neither the input tile nor the weights.  Each byte belongs to one
+// workgroup per forward and forwards on a workspace are stream-ordered: plain loads and stores.  zcode[img * 196 + tile] records the
+// choices, two bits per stream (0 = not launched, 1 = skipped, 2 = zeros stored, 3 = computed), for relpose_scnet_conv1_zero.
 __global__ __launch_bounds__(256, 3) void conv1_mfma_kernel(const float* __restrict__ x0, const float* __restrict__ w1,
-                                                          float* __restrict__ a1, double* __restrict__ stat, int n, int mode) {
+                                                          float* __restrict__ a1, double* __restrict__ stat, int n, int mode,
+                                                          const unsigned* __restrict__ occ, unsigned char* __restrict__ a1z,
+                                                          unsigned short* __restrict__ zcode) {
     __shared__ __attribute__((aligned(16))) float wl[6 * 9 * 4 * 32];
     __shared__ __attribute__((aligned(16))) float xin[C1T_XIN];      // later reused for the per-wave statistics [4][192][2] f64
     static_assert(C1T_XIN * 4 >= 4 * 192 * 2 * 8, "statistics scratch aliases the input tile");
+    static_assert(C1Z_TILES == 196 && C1Z_TPR == 7 && C1Z_TH == 8 && C1Z_TW == 32, "conv1_zero_geom.h describes this kernel's tiles");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l31 = lane & 31;
     const int tile = blockIdx.x % 196, img = blockIdx.x / 196;
     const int ty0 = (tile / 7) * 8, tx0 = (tile % 7) * 32;
+    unsigned code = 0u;                                               // (workgroup-uniform)
+    {
+        const C1zRange zr = c1z_range(tile);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            if (((mode & 1) && img >= 2 && (q & 1)) || ((mode & 2) && !(q & 1))) continue;
+            unsigned c = 3u;
+            if (occ) {
+                unsigned any = 0u;
+                for (int by = zr.by0; by < zr.by1; ++by) { const unsigned v = occ[c1z_word(img, q, by)]; any |= (v & zr.mask) | (v >> 31); }
+                if (!any) c = a1z[c1z_byte(img, q, tile)] ? 1u : 2u;
+            }
+            code |= c << (2 * q);
+        }
+    }
+    if (!(code & 0xaaau)) {                                           // nothing to store: the statistics record of the tile is zeros
+        if (tid == 0) zcode[blockIdx.x] = (unsigned short)code;
+        if (tid < 192) {
+            const size_t pass = (size_t)(img >> 1) * C1_PASSES_PER_GROUP + (size_t)(img & 1) * 196 + tile;
+            double* o = stat + (pass * 192 + tid) * 2;
+            o[0] = 0.0; o[1] = 0.0;
+        }
+        return;
+    }
     for (int i = tid; i < 6 * 9 * 4 * 32 / 4; i += 256) reinterpret_cast<float4*>(wl)[i] = reinterpret_cast<const float4*>(w1)[i];
     for (int i = tid; i < 340 * 4; i += 256) {
         const int p = i >> 2, q4 = i & 3;
@@ -1680,7 +1718,15 @@ __global__ __launch_bounds__(256, 3) void conv1_mfma_kernel(const float* __restr
         float* d = &xin[p * C1T_PS + q4 * 4];
         d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
     }
-    __syncthreads();
+    __syncthreads();                                                   // (every thread has read its state bytes as well)
+    if (occ && tid == 0) {
+        zcode[blockIdx.x] = (unsigned short)code;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const unsigned c = (code >> (2 * q)) & 3u;
+            if (c >= 2u) a1z[c1z_byte(img, q, tile)] = c == 2u ? 1 : 0;
+        }
+    }
     typedef float f32x16 __attribute__((ext_vector_type(16)));
     const int pb = ((2 * wave) * 34 + l31) * C1T_PS;                 // tile row 2w, column l31, tap (0, 0), channel 0
     double st_s[6], st_q[6];
@@ -1690,11 +1736,14 @@ __global__ __launch_bounds__(256, 3) void conv1_mfma_kernel(const float* __restr
         // RELPOSE_FWD_ZERO_WARP: the warped-view blocks (odd q) are exact zeros in every image and only the first image pair's are read
         // (conv2 of those streams runs for one BatchNorm group): no MFMAs, no stores, zero statistics records for the other images
         // mode bit 1 (self-stream cache): the self-view blocks (even q) of A1 are still there from the forward that filled the cache
-        if (((mode & 1) && img >= 2 && (q & 1)) || ((mode & 2) && !(q & 1))) { st_s[q] = 0.0; st_q[q] = 0.0; continue; }
+        // (both code 0); code 1: a zero unit whose zeros are in A1 already
+        const unsigned zc = (code >> (2 * q)) & 3u;
+        if (zc <= 1u) { st_s[q] = 0.0; st_q[q] = 0.0; continue; }
         f32x16 acc0, acc1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
         const int nk = (m == 2) ? 9 : 18;
+        if (zc == 3u) {                                                // (code 2: a zero unit, the stores below write its +0.0)
 #pragma unroll
         for (int kk = 0; kk < nk; ++kk) {
             // (tap, in-block channel) of k = 2kk (lanes 0-31) and k = 2kk + 1 (lanes 32-63); input channel: rgb {0,1,2,7}, n {3,4,5,7}, d {6,7}
@@ -1710,6 +1759,7 @@ __global__ __launch_bounds__(256, 3) void conv1_mfma_kernel(const float* __restr
             const float bv = wl[((q * 9 + tap) * 4 + (h ? c41 : c40)) * 32 + l31];
             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bv, acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v, bv, acc1, 0, 0, 0);
+        }
         }
         // store: register r = pixel column (r & 3) + 8 (r >> 2) + 4 h of the M tile, output channel l31
         double ssum = 0.0, ssq = 0.0;
@@ -2276,7 +2326,11 @@ constexpr int ZT_NP = 7, ZT_PPI = ZT_NP * ZT_NP;    // patches per image side / 
 constexpr int ZT_HDR = 32;                          // ints in front of the lists: counts[2 layers][6 streams]{computed, filled}
 static_assert(RS == ZT_NP * 32 && ZT_NB <= 31, "patch / block geometry");
 inline size_t zt_occ_ints(int n) { return (size_t)n * 6 * ZT_NB; }
-inline size_t zt_ints(int n) { return zt_occ_ints(n) + ZT_HDR + (size_t)36 * n * ZT_PPI; }      // + lists [2][6][cap] + fills [2][6][cap]{2}, cap = 49 n
+inline size_t zt_list_ints(int n) { return zt_occ_ints(n) + ZT_HDR + (size_t)36 * n * ZT_PPI; }      // + lists [2][6][cap] + fills [2][6][cap]{2}, cap = 49 n
+// behind them conv1's zero-unit state bytes a1_zero[n][6][196] and the last forward's codes [n][196] (16 bits each): conv1_mfma_kernel
+static_assert(ZT_NB == C1Z_NB && ZT_BLK == C1Z_BLK, "conv1_zero_geom.h");
+inline size_t c1z_state_bytes(int n) { return (size_t)n * 6 * C1Z_TILES; }
+inline size_t zt_ints(int n) { return zt_list_ints(n) + c1z_state_bytes(n) / 4 + (size_t)n * C1Z_TILES / 2; }
 
 // occ[img][q][block row]: bit bx = block (by, bx) of stream q = 2 m + s (channels as in conv1_inputs) holds a bit pattern other than +-0.
 // One workgroup = one block row of one image.  c_begin = 8 (self-stream cache): only the warped streams' words are used, channels 0:8 are not read.
@@ -2402,28 +2456,71 @@ __device__ __forceinline__ void lin_coef(int dst, float scale, int in, int& i0, 
     l0 = 1.f - l1;
 }
 
+// One output pixel (img, oy, ox) = NHWC pixel idx of y: channels c_begin..15 into out[] and to memory.
+// c_begin = 8 (self-stream cache): channels 0:8 of X0 are already there
+__device__ __forceinline__ void resize_in_pixel(const float* __restrict__ x, float* __restrict__ y, size_t idx, int img, int oy, int ox, int H, int W,
+                                                float shh, float sww, int c_begin, float (&out)[16]) {
+    int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
+    lin_coef(oy, shh, H, y0, y1, ly0, ly1);
+    lin_coef(ox, sww, W, x0, x1, lx0, lx1);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if (c < c_begin) continue;
+        const float* p = x + ((size_t)img * 16 + c) * H * W;
+        out[c] = ly0 * (lx0 * p[(size_t)y0 * W + x0] + lx1 * p[(size_t)y0 * W + x1]) +
+                 ly1 * (lx0 * p[(size_t)y1 * W + x0] + lx1 * p[(size_t)y1 * W + x1]);
+    }
+    float4* o = reinterpret_cast<float4*>(y + idx * 16);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) if (4 * c >= c_begin) o[c] = make_float4(out[4 * c], out[4 * c + 1], out[4 * c + 2], out[4 * c + 3]);
+}
+
 // x [n,16,H,W] NCHW -> y [n,RS,RS,16] NHWC
 __global__ void resize_in_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int H, int W, int c_begin) {
     const size_t total = (size_t)n * RS * RS;
     const float shh = (float)H / RS, sww = (float)W / RS;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int ox = (int)(idx % RS), oy = (int)((idx / RS) % RS), img = (int)(idx / ((size_t)RS * RS));
-        int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
-        lin_coef(oy, shh, H, y0, y1, ly0, ly1);
-        lin_coef(ox, sww, W, x0, x1, lx0, lx1);
-        // c_begin = 8 (self-stream cache): channels 0:8 of X0 are already there
         float out[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            if (c < c_begin) continue;
-            const float* p = x + ((size_t)img * 16 + c) * H * W;
-            out[c] = ly0 * (lx0 * p[(size_t)y0 * W + x0] + lx1 * p[(size_t)y0 * W + x1]) +
-                     ly1 * (lx0 * p[(size_t)y1 * W + x0] + lx1 * p[(size_t)y1 * W + x1]);
-        }
-        float4* o = reinterpret_cast<float4*>(y + idx * 16);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (4 * c >= c_begin) o[c] = make_float4(out[4 * c], out[4 * c + 1], out[4 * c + 2], out[4 * c + 3]);
+        resize_in_pixel(x, y, idx, img, oy, ox, H, W, shh, sww, c_begin, out);
     }
+}
+
+// The same resize with the occupancy words of x0_occupancy_kernel produced on the way (RELPOSE_TUNE_CONV1_ZERO = 0): one workgroup = one
+// 8-row block row of one image, which owns occ[img][0..5][by] outright; the words come from the values the stores hold in registers.
+// Same definition: a bit per 8 x 8 block with a bit pattern other than +-0 in the stream's channels (channel 7 / 15 counts for each of its
+// three streams), bit 31 = a non-finite value; c_begin = 8 reads and judges channels 8:16 only (the self words come out 0, nobody reads them).
+__global__ __launch_bounds__(256) void resize_in_occ_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned* __restrict__ occ,
+                                                            int* __restrict__ counts, int H, int W, int c_begin) {
+    __shared__ unsigned w[6];
+    const int tid = threadIdx.x, img = blockIdx.x / ZT_NB, by = blockIdx.x % ZT_NB;
+    if (blockIdx.x == 0 && tid < ZT_HDR) counts[tid] = 0;             // (zero_tile_list_kernel, the next launch, adds to them)
+    if (tid < 6) w[tid] = 0u;
+    __syncthreads();
+    const float shh = (float)H / RS, sww = (float)W / RS;
+    unsigned m[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    for (int p = tid; p < ZT_BLK * RS; p += 256) {
+        const int oy = by * ZT_BLK + p / RS, ox = p % RS;
+        float out[16];
+        resize_in_pixel(x, y, ((size_t)img * RS + oy) * RS + ox, img, oy, ox, H, W, shh, sww, c_begin, out);
+        const unsigned bit = 1u << (ox / ZT_BLK);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (8 * s < c_begin) continue;
+            const unsigned k = 0x7fffffffu;
+            unsigned b[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) b[c] = __float_as_uint(out[8 * s + c]) & k;
+            const unsigned v[3] = {max(max(b[0], b[1]), max(b[2], b[7])), max(max(b[3], b[4]), max(b[5], b[7])), max(b[6], b[7])};
+#pragma unroll
+            for (int mm = 0; mm < 3; ++mm)
+                if (v[mm]) m[2 * mm + s] |= bit | (v[mm] >= 0x7f800000u ? 0x80000000u : 0u);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) if (m[q]) atomicOr(&w[q], m[q]);
+    __syncthreads();
+    if (tid < 6) occ[((size_t)img * 6 + tid) * ZT_NB + by] = w[tid];
 }
 
 // x [n,RS,RS,C] NHWC -> y [n,C,H,W] NCHW.  One wave = 64 consecutive output pixels of one row.  The <=26
@@ -2575,6 +2672,15 @@ struct RelposeSCNet {
     // relpose_scnet_zero_tiles: the last forward's list counts (device, null = it ran without lists) and the workgroups its conv2 / conv3 launches cover
     const int* last_zt_counts = nullptr;
     int64_t last_zt_units[2] = {0, 0};
+    // conv1's zero units (RELPOSE_TUNE_CONV1_ZERO): 0 * w is NaN for a non-finite weight, so conv1 skips only when its packed weights are all
+    // finite (relpose_scnet_finalize); a1z_state = the workspaces whose a1_zero bytes are known to describe the A1 they hold, under which
+    // allocation and shape (anything else has the bytes cleared before conv1 runs); relpose_scnet_conv1_zero: the last forward's launched
+    // (image, stream, tile) units, whether conv1 tested them (codes written) and whether the occupancy words were computed
+    bool w1_finite = false;
+    struct A1zState { uint64_t gen = 0; int n = 0, H = 0, W = 0; };
+    std::map<void*, A1zState> a1z_state;
+    int64_t last_c1_units = 0;
+    bool last_c1_codes = false, last_occ = false;
     bool profiling = false;
     std::vector<hipEvent_t> ev;
     std::vector<int> ev_kind;
@@ -3364,6 +3470,7 @@ void free_plan(RelposeSCNet* net) {
     }
     net->plans.clear();
     net->self_state.clear();       // (new weights / precision: nothing cached is valid)
+    net->a1z_state.clear();
 }
 
 struct WsOffsets { size_t act, ss, partial, splitk, statp, persist, snap, zt, total; };
@@ -3463,6 +3570,8 @@ int relpose_scnet_finalize(RelposeSCNet* net) {
                         for (int o = 0; o < 32; ++o)
                             w1[(((size_t)(2 * m + s2) * 9 + t) * 4 + c) * 32 + o] = W[((size_t)o * cin_m + c) * 9 + t];
         }
+        net->w1_finite = true;       // (conv1's zero units: 0 * w must be 0)
+        for (int i = 0; i < 6 * 9 * 4 * 32; ++i) if (!std::isfinite(w1[i])) net->w1_finite = false;
     }
     {   // fused heads: weight image (see heads_kernel) + bias in output-channel order
         net->wh_off = blob.size();
@@ -3660,19 +3769,40 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
             RP_HIP(hipMemsetAsync(act + B.off * n, 0, (size_t)n * B.H * B.H * B.C * sizeof(float), s));
         }
     }
+    // RELPOSE_TUNE_CONV1_ZERO: 0 = the resize produces the occupancy words itself and conv1 skips its zero units, 1 = resize_in_kernel,
+    // x0_occupancy_kernel and every launched conv1 block computed and stored (the same bits).  Without the lists there are no words at all.
+    unsigned* const occ = (unsigned*)(ws + o.zt);
+    int* const ztp = (int*)(ws + o.zt) + zt_occ_ints(n);
+    unsigned char* const a1z = (unsigned char*)((int*)(ws + o.zt) + zt_list_ints(n));
+    unsigned short* const zcode = (unsigned short*)(a1z + c1z_state_bytes(n));
+    const bool occ_fused = plan->zt && g_rp_tune[RELPOSE_TUNE_CONV1_ZERO] != 1;
+    const bool c1z = occ_fused && net->w1_finite;
+    // The a1_zero bytes describe what A1 holds: they stand only if the last forward on this workspace maintained them, under this allocation
+    // (a generation the caller names; an unnamed allocation is never trusted) and this shape.  The record is dropped here and committed, like
+    // the self-stream record, once everything is enqueued; a forward that stores every block does not maintain the bytes.
+    RelposeSCNet::A1zState a1z_prev;
+    {
+        auto it = net->a1z_state.find(workspace);
+        if (it != net->a1z_state.end()) { a1z_prev = it->second; net->a1z_state.erase(it); }
+    }
+    if (c1z && !(ws_gen != 0 && !(flags & RELPOSE_FWD_NEW_WORKSPACE) && a1z_prev.gen == ws_gen && a1z_prev.n == n && a1z_prev.H == H && a1z_prev.W == W))
+        RP_HIP(hipMemsetAsync(a1z, 0, c1z_state_bytes(n), s));
     mark(3);
-    hipLaunchKernelGGL(resize_in_kernel, dim3(2048), dim3(256), 0, s, x, act + net->bufs["X0"].off * n, n, H, W, plan->self_cached ? 8 : 0);
+    if (occ_fused)
+        hipLaunchKernelGGL(resize_in_occ_kernel, dim3(n * ZT_NB), dim3(256), 0, s, x, act + net->bufs["X0"].off * n, occ, ztp, H, W, plan->self_cached ? 8 : 0);
+    else
+        hipLaunchKernelGGL(resize_in_kernel, dim3(2048), dim3(256), 0, s, x, act + net->bufs["X0"].off * n, n, H, W, plan->self_cached ? 8 : 0);
     mark(-3);
     net->last_zt_counts = nullptr;
     net->last_zt_units[0] = plan->zt_units[0]; net->last_zt_units[1] = plan->zt_units[1];
+    net->last_c1_units = 0; net->last_c1_codes = false; net->last_occ = plan->zt;
     if (plan->zt) {
         // zero-tile lists of conv2 / conv3 from the occupancy of X0, on the stream that runs conv1 (nothing reads them before conv2)
-        unsigned* occ = (unsigned*)(ws + o.zt);
-        int* ztp = (int*)(ws + o.zt) + zt_occ_ints(n);
         ZtMembers zm;
         for (int q = 0; q < 6; ++q) zm.nimg[q] = plan->zt_nimg[q];
         mark(2);
-        hipLaunchKernelGGL(x0_occupancy_kernel, dim3(n * ZT_NB), dim3(256), 0, s, act + net->bufs["X0"].off * n, occ, ztp, plan->self_cached ? 8 : 0);
+        if (!occ_fused)
+            hipLaunchKernelGGL(x0_occupancy_kernel, dim3(n * ZT_NB), dim3(256), 0, s, act + net->bufs["X0"].off * n, occ, ztp, plan->self_cached ? 8 : 0);
         hipLaunchKernelGGL(zero_tile_list_kernel, dim3(G, 6, 2), dim3(128), 0, s, occ, ztp, zm, n * ZT_PPI);
         mark(-2);
         net->last_zt_counts = ztp;
@@ -3791,7 +3921,11 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         } else if (op.type == OP_CONV1) {
             mark(1);
             hipLaunchKernelGGL(conv1_mfma_kernel, dim3(196 * n), dim3(256), 0, s, act + net->bufs["X0"].off * n, net->d_w + net->w1_off,
-                               act + net->bufs["A1"].off * n, partial, n, (plan->zero_warp ? 1 : 0) | (plan->self_cached ? 2 : 0));
+                               act + net->bufs["A1"].off * n, partial, n, (plan->zero_warp ? 1 : 0) | (plan->self_cached ? 2 : 0),
+                               c1z ? (const unsigned*)occ : nullptr, a1z, zcode);
+            // (image, stream) blocks this plan launches, 196 tiles each
+            net->last_c1_units = (int64_t)C1Z_TILES * (plan->self_cached ? 3 * n : (plan->zero_warp ? 3 * n + 3 * 2 : 6 * n));
+            net->last_c1_codes = c1z;
             mark(-1);
         } else if (op.type == OP_STATS_FUSED) {
             const Buf& B = net->bufs[op.buf];
@@ -3877,6 +4011,10 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     RP_CHECK_LAUNCH();
     {   // everything is enqueued: the workspace now holds (stream-ordered) the self-view streams of `self_tag`
         net->self_state[workspace] = commit;
+        if (net->last_c1_codes) {                 // ... and a1_zero bytes that conv1 kept in step with A1
+            RelposeSCNet::A1zState z; z.gen = ws_gen; z.n = n; z.H = H; z.W = W;
+            net->a1z_state[workspace] = z;
+        }
     }
     return 0;
 }
@@ -3968,6 +4106,30 @@ int relpose_scnet_zero_tiles(RelposeSCNet* net, void* workspace, void* stream, i
         for (int q = 0; q < 6; ++q) { c += h[(l * 6 + q) * 2]; f += h[(l * 6 + q) * 2 + 1]; }
         counts_host[2 * l] = c; counts_host[2 * l + 1] = f;
     }
+    return 0;
+}
+
+int relpose_scnet_conv1_zero(RelposeSCNet* net, void* workspace, void* stream, int64_t* counts_host, uint32_t* occ_host) {
+    if (!net || !net->finalized || !workspace || !counts_host || net->last_n <= 0) return RELPOSE_EINVAL;
+    const int n = net->last_n;
+    counts_host[0] = net->last_c1_units; counts_host[1] = 0; counts_host[2] = 0;
+    if (occ_host && !net->last_occ) return RELPOSE_EINVAL;          // the forward ran without lists: no occupancy words
+    const int* base = (const int*)((const char*)workspace + ws_offsets(net, n).zt);
+    std::vector<unsigned short> codes;
+    if (net->last_c1_codes) {
+        codes.resize((size_t)n * C1Z_TILES);
+        const unsigned char* a1z = (const unsigned char*)(base + zt_list_ints(n));
+        RP_HIP(hipMemcpyAsync(codes.data(), a1z + c1z_state_bytes(n), codes.size() * sizeof(unsigned short), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    }
+    if (occ_host) RP_HIP(hipMemcpyAsync(occ_host, base, zt_occ_ints(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    RP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    int64_t launched = 0;
+    for (unsigned short c : codes)
+        for (int q = 0; q < 6; ++q) {
+            const int v = (c >> (2 * q)) & 3;
+            launched += v != 0; counts_host[1] += v == 1; counts_host[2] += v == 2;
+        }
+    if (net->last_c1_codes && launched != net->last_c1_units) return RELPOSE_EINVAL;       // (the codes and the plan must agree)
     return 0;
 }
 

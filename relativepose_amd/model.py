@@ -163,7 +163,7 @@ class SCNet(torch.nn.Module):
         ws.record_stream(torch.cuda.current_stream())
         for s in also_streams:
             ws.record_stream(s)
-        self._ws = ws
+        self._ws, self._ws_n = ws, n
         return ws
 
     _tag_counter = 0
@@ -258,6 +258,18 @@ class SCNet(torch.nn.Module):
         v = (C.c_int64 * 4)()
         _lib.check(_lib.lib().relpose_scnet_zero_tiles(self._h, _lib.ptr(self._ws), _lib.stream_ptr(), v), "relpose_scnet_zero_tiles")
         return {2: (int(v[0]), int(v[1])), 3: (int(v[2]), int(v[3]))}
+
+    def conv1_zero(self, occupancy=False):
+        """(launched, skipped, zero_stored): conv1's (image, stream, 8 x 32 tile) blocks of A1 in the last forward, those it neither computed
+        nor stored and those it stored as zeros (relpose_scnet_conv1_zero; synchronises the current stream).  occupancy=True: also that
+        forward's occupancy words as an int64 array [n, 6, 28] (bit bx = block column bx occupied, bit 31 = a non-finite value)."""
+        import numpy as np
+        v = (C.c_int64 * 3)()
+        occ = np.zeros((self._ws_n, 6, 28), np.uint32) if occupancy else None
+        _lib.check(_lib.lib().relpose_scnet_conv1_zero(self._h, _lib.ptr(self._ws), _lib.stream_ptr(), v,
+                                                       occ.ctypes.data_as(C.c_void_p) if occupancy else None), "relpose_scnet_conv1_zero")
+        counts = (int(v[0]), int(v[1]), int(v[2]))
+        return (counts, occ.astype(np.int64)) if occupancy else counts
 
     def layer_on_strip_kernel(self, layer, n):
         """True if ``layer`` runs on deconv_strip_kernel (either launch form)."""
