@@ -5,10 +5,11 @@
 //
 // Clouds: c = 2b (source of pair b), 2b + 1 (target); level l = 0, 1, 2 has voxel size = radius 0.04, 0.02, 0.01.  Per-level arrays are
 // indexed by cl = 3 c + l (both clouds) or tl = 3 b + l (target only).  Kernels:
-//   cicp_voxel_kernel     one block per (cloud, level): fgr.hip's voxel downsample with the voxel size as a parameter, colours averaged
-//                         like the points; also keeps every voxel's key and the lattice (min bound, extents) for the searches below
+//   cicp_voxel_kernel     one block per (cloud, level): the voxel downsample fgr.hip runs (cloud_prims.h's rp_voxel_downsample) at the
+//                         level's voxel size, colours averaged like the points; also keeps every voxel's key and the lattice (min bound,
+//                         extents) for the searches below
 //   cicp_neighbors_kernel one wave per target voxel: the (d2, index)-ordered hybrid list (r = 2 radius, max 30) from the sorted keys
-//   cicp_normals_kernel   one thread per target voxel: normal (as §4.6 stage 3) and the colour gradient
+//   cicp_normals_kernel   one thread per target voxel: normal (§4.6 stage 3: cloud_prims.h's rp_normal_from_neighbors) and the colour gradient
 //   cicp_init_kernel      one wave per pair: status, the starting transform, the per-pair state
 //   cicp_nn_kernel        per iteration, one thread per source voxel: q = T p and its nearest target voxel below the radius
 //   cicp_step_kernel      per iteration, one block per pair: fitness / rmse, the stop test, the 27 sums in the fixed order of §4.7
@@ -27,6 +28,7 @@
 #include <cstring>
 #include <vector>
 
+#include "cloud_prims.h"
 #include "common.h"
 
 namespace {
@@ -34,7 +36,6 @@ namespace {
 constexpr int kLevels = RELPOSE_CICP_LEVELS;
 constexpr int kNn = 30;                  // max_nn of the hybrid search
 constexpr int kBuf = 256;                // candidates of one query: at most 6 x 6 x 6 cells of one voxel each
-constexpr int kJacobiSweeps = 6;
 constexpr int kSlots = RELPOSE_CICP_TRACE_SLOTS;
 constexpr double kRelFitness = 1e-6, kRelRmse = 1e-6;
 constexpr double kInflate = 1.0001;      // the searched ball's radius over the true one
@@ -78,39 +79,9 @@ struct CicpBufs {
     double* iter_x;          // [B, 94, 6]
 };
 
-__device__ __forceinline__ unsigned long long lanes_below() {
-    const int l = rp_lane();
-    return l == 0 ? 0ull : (~0ull >> (64 - l));
-}
-
-__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// Block-wide ordered scan of one flag per thread (blockDim 1024 = 16 waves): exclusive prefix and total.
-__device__ __forceinline__ int block_rank(bool f, int* wsum, int& total) {
-    const unsigned long long m = __ballot(f);
-    const int w = threadIdx.x >> 6;
-    if (rp_lane() == 0) wsum[w] = __popcll(m);
-    __syncthreads();
-    int before = 0, tot = 0;
-    const int nw = blockDim.x >> 6;
-    for (int k = 0; k < nw; ++k) {
-        const int v = wsum[k];
-        before += k < w ? v : 0;
-        tot += v;
-    }
-    __syncthreads();
-    total = tot;
-    return before + __popcll(m & lanes_below());
-}
-
 // A x = b by Cholesky in the order of tests/fgr_model.py's cholesky_solve (every inner sum accumulated from 0, then subtracted);
-// false at a non-positive pivot.
+// false at a non-positive pivot.  fgr.hip's fgr_optimize_kernel subtracts every product from the running value instead: the two round
+// differently and each is pinned by its own numpy model, so they stay apart.
 template <int N>
 __device__ bool chol_solve(const double (&A)[N][N], const double (&b)[N], double (&x)[N]) {
     double L[N][N], y[N];
@@ -148,137 +119,31 @@ __device__ bool chol_solve(const double (&A)[N][N], const double (&b)[N], double
 }
 
 // ------------------------------------------------------------------------------------------------------- 1. coloured voxel grid
+// averages the colours like the points; keeps every voxel's key and the lattice for the searches below
+struct CicpVoxelPolicy {
+    static constexpr bool kExtra = true;
+    const double* extra_in;
+    double* extra_out;
+    long long* vkey;
+    double* gmb;
+    long long* gdim;
+    __device__ void lattice(const double* mb, long long nx, long long ny, long long nz) const {
+        for (int a = 0; a < 3; ++a) gmb[a] = mb[a];
+        gdim[0] = nx; gdim[1] = ny; gdim[2] = nz;
+    }
+    __device__ void voxel(int o, long long key, long long, long long) const { vkey[o] = key; }
+};
+
 __global__ __launch_bounds__(1024) void cicp_voxel_kernel(CicpBufs f) {
-    const int cl = blockIdx.x, c = cl / kLevels, l = cl % kLevels, tid = threadIdx.x, nt = blockDim.x;
-    const double vox = kRadius[l];
+    const int cl = blockIdx.x, c = cl / kLevels, l = cl % kLevels;
     const long long P = f.P;
-    const double* pc = f.pc + (long long)c * P * 3;
-    const double* cc = f.color + (long long)c * P * 3;
-    const uint8_t* valid = f.valid + (long long)c * P;
-    __shared__ double smin[3][1024];
-    __shared__ long long smax[3][1024];
-    __shared__ int wsum[16];
-    __shared__ int digit_cnt[16][16];
-    __shared__ int base[16];
-    double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX};
-    for (long long e = tid; e < P; e += nt)
-        if (valid[e])
-            for (int a = 0; a < 3; ++a) mn[a] = fmin(mn[a], pc[3 * e + a]);
-    for (int a = 0; a < 3; ++a) smin[a][tid] = mn[a];
-    __syncthreads();
-    for (int s = nt / 2; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int a = 0; a < 3; ++a) smin[a][tid] = fmin(smin[a][tid], smin[a][tid + s]);
-        __syncthreads();
-    }
-    if (smin[0][0] == DBL_MAX) {                  // no valid point
-        if (tid == 0) f.count[cl] = 0;
-        return;
-    }
-    const double mb[3] = {smin[0][0] - 0.5 * vox, smin[1][0] - 0.5 * vox, smin[2][0] - 0.5 * vox};
-    long long mx[3] = {0, 0, 0};
-    for (long long e = tid; e < P; e += nt)
-        if (valid[e])
-            for (int a = 0; a < 3; ++a) mx[a] = max(mx[a], (long long)floor((pc[3 * e + a] - mb[a]) / vox));
-    for (int a = 0; a < 3; ++a) smax[a][tid] = mx[a];
-    __syncthreads();
-    for (int s = nt / 2; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int a = 0; a < 3; ++a) smax[a][tid] = max(smax[a][tid], smax[a][tid + s]);
-        __syncthreads();
-    }
-    const long long dx = smax[0][0] + 1, dy = smax[1][0] + 1, dz = smax[2][0] + 1, total_keys = dx * dy * dz;
-    const int bits = total_keys > 1 ? 64 - __clzll((unsigned long long)(total_keys - 1)) : 0;
-    if (tid == 0) {
-        for (int a = 0; a < 3; ++a) f.gmb[4 * cl + a] = mb[a];
-        f.gdim[4 * cl] = dx; f.gdim[4 * cl + 1] = dy; f.gdim[4 * cl + 2] = dz;
-    }
-    long long* key0 = f.key[0] + (long long)cl * P;
-    int* idx0 = f.idx[0] + (long long)cl * P;
-    long long* key1 = f.key[1] + (long long)cl * P;
-    int* idx1 = f.idx[1] + (long long)cl * P;
-    // compaction of the valid points, input order kept
-    int nv = 0;
-    for (long long t0 = 0; t0 < P; t0 += nt) {
-        const long long e = t0 + tid;
-        const bool v = e < P && valid[e];
-        int tot;
-        const int r = block_rank(v, wsum, tot);
-        if (v) {
-            long long k[3];
-            for (int a = 0; a < 3; ++a) k[a] = (long long)floor((pc[3 * e + a] - mb[a]) / vox);
-            key0[nv + r] = (k[0] * dy + k[1]) * dz + k[2];
-            idx0[nv + r] = (int)e;
-        }
-        nv += tot;
-    }
-    __syncthreads();
-    // stable LSD radix sort, 4-bit digits
-    const int w = tid >> 6, lane = rp_lane();
-    for (int sh = 0; sh < bits; sh += 4) {
-        if (tid < 16) base[tid] = 0;
-        __syncthreads();
-        for (int e = tid; e < nv; e += nt) atomicAdd(&base[(key0[e] >> sh) & 15], 1);
-        __syncthreads();
-        if (tid == 0) {
-            int s = 0;
-            for (int d = 0; d < 16; ++d) { const int v = base[d]; base[d] = s; s += v; }
-        }
-        __syncthreads();
-        for (int t0 = 0; t0 < nv; t0 += nt) {
-            const int e = t0 + tid;
-            const bool in = e < nv;
-            const long long k = in ? key0[e] : 0;
-            const int d = in ? (int)((k >> sh) & 15) : -1;
-            int rank = 0;
-            for (int dd = 0; dd < 16; ++dd) {
-                const unsigned long long m = __ballot(d == dd);
-                if (d == dd) rank = __popcll(m & lanes_below());
-                if (lane == 0) digit_cnt[w][dd] = __popcll(m);
-            }
-            __syncthreads();
-            if (in) {
-                int off = base[d] + rank;
-                for (int k2 = 0; k2 < w; ++k2) off += digit_cnt[k2][d];
-                key1[off] = k;
-                idx1[off] = idx0[e];
-            }
-            __syncthreads();
-            if (tid < 16) {
-                int s = 0;
-                for (int k2 = 0; k2 < nt / 64; ++k2) s += digit_cnt[k2][tid];
-                base[tid] += s;
-            }
-            __syncthreads();
-        }
-        long long* tk = key0; key0 = key1; key1 = tk;
-        int* ti = idx0; idx0 = idx1; idx1 = ti;
-    }
-    // segmented means: one thread per voxel start, summing its points (and colours) sequentially in input order
-    double* out = f.pts + (long long)cl * f.cap * 3;
-    double* ocol = f.col + (long long)cl * f.cap * 3;
-    long long* okey = f.vkey + (long long)cl * f.cap;
-    int nvox = 0;
-    for (int t0 = 0; t0 < nv; t0 += nt) {
-        const int e = t0 + tid;
-        const bool st = e < nv && (e == 0 || key0[e] != key0[e - 1]);
-        int tot;
-        const int r = block_rank(st, wsum, tot);
-        const int o = nvox + r;
-        if (st && o < f.cap) {
-            const long long k = key0[e];
-            double s[3] = {0.0, 0.0, 0.0}, u[3] = {0.0, 0.0, 0.0};
-            int m = 0;
-            for (int j = e; j < nv && key0[j] == k; ++j, ++m) {
-                const long long i = idx0[j];
-                for (int a = 0; a < 3; ++a) { s[a] += pc[3 * i + a]; u[a] += cc[3 * i + a]; }
-            }
-            for (int a = 0; a < 3; ++a) { out[3 * o + a] = s[a] / (double)m; ocol[3 * o + a] = u[a] / (double)m; }
-            okey[o] = k;
-        }
-        nvox += tot;
-    }
-    if (tid == 0) f.count[cl] = nvox;
+    __shared__ RpVoxelScratch lds;
+    const CicpVoxelPolicy pol{f.color + (long long)c * P * 3, f.col + (long long)cl * f.cap * 3, f.vkey + (long long)cl * f.cap, f.gmb + 4 * cl,
+                              f.gdim + 4 * cl};
+    const int nvox = rp_voxel_downsample(f.pc + (long long)c * P * 3, f.valid + (long long)c * P, P, kRadius[l], f.key[0] + (long long)cl * P,
+                                         f.idx[0] + (long long)cl * P, f.key[1] + (long long)cl * P, f.idx[1] + (long long)cl * P,
+                                         f.pts + (long long)cl * f.cap * 3, f.cap, lds, pol);
+    if (threadIdx.x == 0) f.count[cl] = nvox;
 }
 
 // ------------------------------------------------------------------------------------------------------- lattice lookups
@@ -312,17 +177,6 @@ __device__ __forceinline__ bool axis_range(double q, double mb, double vox, doub
     return true;
 }
 
-__device__ __forceinline__ int lower_bound_key(const long long* key, int n, long long v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (key[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ bool lex_less(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
-
 // ------------------------------------------------------------------------------------------------------- 2. neighbours (target)
 __global__ __launch_bounds__(64) void cicp_neighbors_kernel(CicpBufs f) {
     const int tl = blockIdx.y, b = tl / kLevels, l = tl % kLevels, lane = threadIdx.x;
@@ -344,7 +198,7 @@ __global__ __launch_bounds__(64) void cicp_neighbors_kernel(CicpBufs f) {
             int s = 0, e = 0;
             if (col < ncol) {
                 const long long kb = ((lo[0] + col / ncy) * g.dim[1] + (lo[1] + col % ncy)) * g.dim[2];
-                s = lower_bound_key(g.key, g.n, kb + lo[2]);
+                s = rp_lower_bound(g.key, g.n, kb + lo[2]);
                 e = s;
                 while (e < g.n && g.key[e] <= kb + hi[2]) ++e;
             }
@@ -358,7 +212,7 @@ __global__ __launch_bounds__(64) void cicp_neighbors_kernel(CicpBufs f) {
                     in = d2 < r2;
                 }
                 const unsigned long long msk = __ballot(in);
-                const int o = m + __popcll(msk & lanes_below());
+                const int o = m + __popcll(msk & rp_lanes_below());
                 if (in && o < kBuf) { bd[o] = d2; bi[o] = cnd; }
                 m = min(m + __popcll(msk), kBuf);
             }
@@ -369,7 +223,7 @@ __global__ __launch_bounds__(64) void cicp_neighbors_kernel(CicpBufs f) {
             const double de = bd[e];
             const int ie = bi[e];
             int rank = 0;
-            for (int k = 0; k < m; ++k) rank += lex_less(bd[k], bi[k], de, ie) ? 1 : 0;
+            for (int k = 0; k < m; ++k) rank += rp_lex_less(bd[k], bi[k], de, ie) ? 1 : 0;
             if (rank < kNn) f.nbr[row * kNn + rank] = ie;
         }
         if (lane == 0) f.ncnt[row] = min(m, kNn);
@@ -391,59 +245,9 @@ __global__ __launch_bounds__(256) void cicp_normals_kernel(CicpBufs f) {
     const long long row = (long long)tl * f.cap + q;
     const int* nb = f.nbr + row * kNn;
     const int m = f.ncnt[row];
-    double nv[3] = {0.0, 0.0, 1.0};
-    if (m >= 3) {
-        double s[3] = {0.0, 0.0, 0.0};
-        for (int j = 0; j < m; ++j)
-            for (int a = 0; a < 3; ++a) s[a] += pts[3 * nb[j] + a];
-        const double mf = (double)m;
-        const double mean[3] = {s[0] / mf, s[1] / mf, s[2] / mf};
-        double C[6] = {0, 0, 0, 0, 0, 0};       // 00 01 02 11 12 22
-        for (int j = 0; j < m; ++j) {
-            const double d0 = pts[3 * nb[j]] - mean[0], d1 = pts[3 * nb[j] + 1] - mean[1], d2 = pts[3 * nb[j] + 2] - mean[2];
-            C[0] += d0 * d0; C[1] += d0 * d1; C[2] += d0 * d2; C[3] += d1 * d1; C[4] += d1 * d2; C[5] += d2 * d2;
-        }
-        double A[3][3];
-        A[0][0] = C[0] / mf; A[0][1] = A[1][0] = C[1] / mf; A[0][2] = A[2][0] = C[2] / mf;
-        A[1][1] = C[3] / mf; A[1][2] = A[2][1] = C[4] / mf; A[2][2] = C[5] / mf;
-        double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-#pragma unroll
-        for (int sw = 0; sw < kJacobiSweeps; ++sw) {
-#pragma unroll
-            for (int rot = 0; rot < 3; ++rot) {
-                const int p = rot == 2 ? 1 : 0, qq = rot == 0 ? 1 : 2, r = 3 - p - qq;
-                const double apq = A[p][qq];
-                if (apq != 0.0) {
-                    const double theta = (A[qq][qq] - A[p][p]) / (2.0 * apq);
-                    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    if (theta < 0) t = -t;
-                    const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-                    const double app = A[p][p] - t * apq, aqq = A[qq][qq] + t * apq;
-                    const double arp = A[r][p], arq = A[r][qq];
-                    const double nrp = cs * arp - sn * arq, nrq = sn * arp + cs * arq;
-                    A[p][p] = app; A[qq][qq] = aqq; A[p][qq] = A[qq][p] = 0.0;
-                    A[r][p] = A[p][r] = nrp; A[r][qq] = A[qq][r] = nrq;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const double vkp = V[k][p], vkq = V[k][qq];
-                        V[k][p] = cs * vkp - sn * vkq;
-                        V[k][qq] = sn * vkp + cs * vkq;
-                    }
-                }
-            }
-        }
-        int k = A[1][1] < A[0][0] ? 1 : 0;
-        const double ek = k == 1 ? A[1][1] : A[0][0];
-        if (A[2][2] < ek) k = 2;
-        const double v0 = k == 0 ? V[0][0] : (k == 1 ? V[0][1] : V[0][2]);
-        const double v1 = k == 0 ? V[1][0] : (k == 1 ? V[1][1] : V[1][2]);
-        const double v2 = k == 0 ? V[2][0] : (k == 1 ? V[2][1] : V[2][2]);
-        const double nn = sqrt((v0 * v0 + v1 * v1) + v2 * v2);
-        nv[0] = v0 / nn; nv[1] = v1 / nn; nv[2] = v2 / nn;
-    }
     const double p[3] = {pts[3 * q], pts[3 * q + 1], pts[3 * q + 2]};
-    const double w[3] = {0.0 - p[0], 0.0 - p[1], 0.0 - p[2]};
-    if (dot3(nv, w) < 0) { nv[0] = -nv[0]; nv[1] = -nv[1]; nv[2] = -nv[2]; }
+    double nv[3];
+    rp_normal_from_neighbors(pts, nb, m, p, nv);
     for (int a = 0; a < 3; ++a) f.normal[row * 3 + a] = nv[a];
     // colour gradient: least squares over the neighbours projected onto the tangent plane, plus the row that pins the normal component
     double gr[3] = {0.0, 0.0, 0.0};
@@ -454,7 +258,7 @@ __global__ __launch_bounds__(256) void cicp_normals_kernel(CicpBufs f) {
             const int j = nb[k];
             const double pk[3] = {pts[3 * j], pts[3 * j + 1], pts[3 * j + 2]};
             const double d[3] = {pk[0] - p[0], pk[1] - p[1], pk[2] - p[2]};
-            const double s = dot3(d, nv);
+            const double s = rp_dot3(d, nv);
             const double a[3] = {(pk[0] - s * nv[0]) - p[0], (pk[1] - s * nv[1]) - p[1], (pk[2] - s * nv[2]) - p[2]};
             const double bk = intensity(col + 3 * j) - i0;
             ata[0] += a[0] * a[0]; ata[1] += a[0] * a[1]; ata[2] += a[0] * a[2]; ata[3] += a[1] * a[1]; ata[4] += a[1] * a[2]; ata[5] += a[2] * a[2];
@@ -528,7 +332,7 @@ __global__ __launch_bounds__(256) void cicp_nn_kernel(CicpBufs f, int l, int slo
             for (long long cy = lo[1]; cy <= hi[1]; ++cy) {
                 const long long kb = (cx * g.dim[1] + cy) * g.dim[2];
                 const long long k1 = kb + hi[2];
-                for (int e = lower_bound_key(g.key, g.n, kb + lo[2]); e < g.n && g.key[e] <= k1; ++e) {
+                for (int e = rp_lower_bound(g.key, g.n, kb + lo[2]); e < g.n && g.key[e] <= k1; ++e) {
                     const double dx = g.pts[3 * e] - q[0], dy = g.pts[3 * e + 1] - q[1], dz = g.pts[3 * e + 2] - q[2];
                     const double d2 = (dx * dx + dy * dy) + dz * dz;
                     if (d2 < best) { best = d2; bi = e; }
@@ -573,16 +377,16 @@ __global__ __launch_bounds__(256) void cicp_step_kernel(CicpBufs f, int l, int k
         const double* nt = nrm + 3 * j;
         const double* dit = grd + 3 * j;
         const double d[3] = {vs[0] - vt[0], vs[1] - vt[1], vs[2] - vt[2]};
-        const double dn = dot3(d, nt);
+        const double dn = rp_dot3(d, nt);
         double JG[6], JI[6], c3[3];
-        cross3(vs, nt, c3);
+        rp_cross3(vs, nt, c3);
         for (int a = 0; a < 3; ++a) { JG[a] = sg * c3[a]; JG[3 + a] = sg * nt[a]; }
         const double rG = sg * dn;
         const double pr[3] = {(vs[0] - dn * nt[0]) - vt[0], (vs[1] - dn * nt[1]) - vt[1], (vs[2] - dn * nt[2]) - vt[2]};
-        const double is_proj = dot3(dit, pr) + intensity(clt + 3 * j);
-        const double dd = dot3(dit, nt);
+        const double is_proj = rp_dot3(dit, pr) + intensity(clt + 3 * j);
+        const double dd = rp_dot3(dit, nt);
         const double dm[3] = {-(dit[0] - dd * nt[0]), -(dit[1] - dd * nt[1]), -(dit[2] - dd * nt[2])};
-        cross3(vs, dm, c3);
+        rp_cross3(vs, dm, c3);
         for (int a = 0; a < 3; ++a) { JI[a] = sc * c3[a]; JI[3 + a] = sc * dm[a]; }
         const double rI = sc * (intensity(cls + 3 * i) - is_proj);
         int e = 0;
@@ -595,12 +399,8 @@ __global__ __launch_bounds__(256) void cicp_step_kernel(CicpBufs f, int l, int k
     }
     // the fixed reduction of DESIGN.md §4.7 step 7: per-thread sums in voxel order, xor tree over the wave, the 4 wave sums in order
 #pragma unroll
-    for (int e = 0; e < 28; ++e) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) acc[e] += rp_shfl_xor_d(acc[e], m);
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);
+    for (int e = 0; e < 28; ++e) acc[e] = rp_wave_xor_sum(acc[e]);
+    cnt = rp_wave_sum_i(cnt);
     if (rp_lane() == 0) {
 #pragma unroll
         for (int e = 0; e < 28; ++e) red[tid >> 6][e] = acc[e];
@@ -657,8 +457,6 @@ __global__ __launch_bounds__(256) void cicp_step_kernel(CicpBufs f, int l, int k
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct CicpPlan {
     size_t off_key0, off_key1, off_idx0, off_idx1, off_pts, off_col, off_vkey, off_gmb, off_gdim, off_count, off_nbr, off_ncnt, off_normal,
         off_grad, off_corr, off_cd2, off_T, off_prev, off_state, total;
@@ -668,7 +466,7 @@ bool cicp_plan(int B, int P, int cap, CicpPlan& p) {
     if (B <= 0 || B > 21845 || P <= 0 || cap <= 0 || cap > RELPOSE_FGR_MAX_POINTS_LIMIT || (long long)P > (1LL << 30)) return false;
     const size_t CL = 2 * (size_t)B * kLevels, TL = (size_t)B * kLevels, N = (size_t)cap, Bs = (size_t)B;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = off; off += rp_align(bytes); return o; };
     p.off_key0 = take(CL * P * 8);
     p.off_key1 = take(CL * P * 8);
     p.off_idx0 = take(CL * P * 4);

@@ -62,6 +62,8 @@ __device__ __forceinline__ double rp_readlane_d(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 
+// (rp_wave_sum / rp_block_sum, the DPP row order, are what matcher.hip, affinity.hip and completion.hip sum with; the contracts of FGR,
+// RANSAC and coloured ICP name the xor tree, cloud_prims.h's rp_wave_xor_sum / rp_block_xor_sum, which rounds differently.)
 // Fixed-order sum over the 64 lanes of a wave (deterministic), result in every lane, without LDS traffic: butterfly inside
 // every row of 16 lanes with DPP (quad_perm xor 1, xor 2, row_half_mirror, row_mirror), then ((r0 + r1) + (r2 + r3)) of the
 // four row sums through SGPRs.  (The ds_bpermute butterfly this replaces cost ~1.2 k cycles of LDS latency per double.)

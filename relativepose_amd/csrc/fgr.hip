@@ -3,7 +3,7 @@
 // tests/fgr_model.py restates it in numpy.  Built with -ffp-contract=off: the model and these kernels round alike.
 //
 // Clouds: c = 2b (source of pair b), 2b + 1 (target).  Kernels, each launched once per call whatever the batch size:
-//   fgr_voxel_kernel      one block per cloud: min bound, voxel keys, compaction, stable LSD radix sort, segmented means
+//   fgr_voxel_kernel      one block per cloud: min bound, voxel keys, compaction, stable LSD radix sort, segmented means (rp_voxel_downsample)
 //   fgr_neighbors_kernel  one wave per query: the (d2, index)-ordered hybrid neighbour list (r 0.25, max 100) from the x-slab of the lattice
 //   fgr_normals_kernel    one thread per point: covariance of the r 0.10 / 30 prefix, fixed-sweep Jacobi, turned toward the sensor
 //   fgr_spfh_kernel       one thread per point, histograms in LDS
@@ -11,6 +11,8 @@
 //   fgr_nn_kernel         one thread per query, the other cloud's features staged in LDS: exact fp32 nearest neighbour
 //   fgr_match_kernel      one block per pair: mutual filter, then the tuple trials in order with a block scan
 //   fgr_optimize_kernel   one block per pair: normalisation and the 64 Gauss-Newton steps, fixed-order 6x6 reduction
+// The voxel downsample (scan, compaction, radix sort, segmented means), the normal of a neighbour list, the ordered block scan and the
+// xor-tree reductions are cloud_prims.h's, shared with cicp.hip, ransac.hip and overlap.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +22,7 @@
 #include <cstring>
 #include <vector>
 
+#include "cloud_prims.h"
 #include "common.h"
 #include "fgr_internal.h"
 
@@ -38,7 +41,6 @@ constexpr int kMaxTuples = 1000;
 constexpr int kMinCorr = 10;
 constexpr int kSlab = 6;             // candidate voxel columns |dx| <= 6 >= r / voxel + 1
 constexpr int kBuf = 256;            // per-wave candidate buffer of the neighbour search
-constexpr int kJacobiSweeps = 6;
 constexpr int kFeat = 33;
 constexpr int kNnStage = 64;         // targets per LDS stage of the matcher
 
@@ -50,168 +52,27 @@ __constant__ double kEdgeSin[10] = {-0.5406408174555978, -0.9096319953545184, -0
 
 __device__ __forceinline__ int cloud_n(const FgrBufs& f, int c) { return min(f.count[c], f.cap); }
 
-__device__ __forceinline__ unsigned long long lanes_below() {
-    const int l = rp_lane();
-    return l == 0 ? 0ull : (~0ull >> (64 - l));
-}
-
-// Block-wide ordered scan of one flag per thread (blockDim 1024 = 16 waves): exclusive prefix and total.
-__device__ __forceinline__ int block_rank(bool f, int* wsum, int& total) {
-    const unsigned long long m = __ballot(f);
-    const int w = threadIdx.x >> 6;
-    if (rp_lane() == 0) wsum[w] = __popcll(m);
-    __syncthreads();
-    int before = 0, tot = 0;
-    const int nw = blockDim.x >> 6;
-    for (int k = 0; k < nw; ++k) {
-        const int v = wsum[k];
-        before += k < w ? v : 0;
-        tot += v;
-    }
-    __syncthreads();
-    total = tot;
-    return before + __popcll(m & lanes_below());
-}
-
 // ------------------------------------------------------------------------------------------------------- 1. voxel downsample
+// keeps every voxel's x cell: the neighbour search walks the x-slab of the lattice
+struct FgrVoxelPolicy {
+    static constexpr bool kExtra = false;
+    int* ix;
+    __device__ void lattice(const double*, long long, long long, long long) const {}
+    __device__ void voxel(int o, long long key, long long ny, long long nz) const { ix[o] = (int)(key / (ny * nz)); }
+};
+
 __global__ __launch_bounds__(1024) void fgr_voxel_kernel(FgrBufs f) {
-    const int c = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const int c = blockIdx.x;
     const long long P = f.P;
-    const double* pc = f.pc + (long long)c * P * 3;
-    const uint8_t* valid = f.valid + (long long)c * P;
-    __shared__ double smin[3][1024];
-    __shared__ long long smax[3][1024];
-    __shared__ int wsum[16];
-    __shared__ int digit_cnt[16][16];
-    __shared__ int base[16];
-    double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX};
-    for (long long e = tid; e < P; e += nt)
-        if (valid[e])
-            for (int a = 0; a < 3; ++a) mn[a] = fmin(mn[a], pc[3 * e + a]);
-    for (int a = 0; a < 3; ++a) smin[a][tid] = mn[a];
-    __syncthreads();
-    for (int s = nt / 2; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int a = 0; a < 3; ++a) smin[a][tid] = fmin(smin[a][tid], smin[a][tid + s]);
-        __syncthreads();
-    }
-    if (smin[0][0] == DBL_MAX) {                  // no valid point
-        if (tid == 0) f.count[c] = 0;
-        return;
-    }
-    const double mb[3] = {smin[0][0] - 0.5 * kVoxel, smin[1][0] - 0.5 * kVoxel, smin[2][0] - 0.5 * kVoxel};
-    long long mx[3] = {0, 0, 0};
-    for (long long e = tid; e < P; e += nt)
-        if (valid[e])
-            for (int a = 0; a < 3; ++a) mx[a] = max(mx[a], (long long)floor((pc[3 * e + a] - mb[a]) / kVoxel));
-    for (int a = 0; a < 3; ++a) smax[a][tid] = mx[a];
-    __syncthreads();
-    for (int s = nt / 2; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int a = 0; a < 3; ++a) smax[a][tid] = max(smax[a][tid], smax[a][tid + s]);
-        __syncthreads();
-    }
-    const long long dy = smax[1][0] + 1, dz = smax[2][0] + 1, total_keys = (smax[0][0] + 1) * dy * dz;
-    const int bits = total_keys > 1 ? 64 - __clzll((unsigned long long)(total_keys - 1)) : 0;
-    long long* key0 = f.key[0] + (long long)c * P;
-    int* idx0 = f.idx[0] + (long long)c * P;
-    long long* key1 = f.key[1] + (long long)c * P;
-    int* idx1 = f.idx[1] + (long long)c * P;
-    // compaction of the valid points, input order kept
-    int nv = 0;
-    for (long long t0 = 0; t0 < P; t0 += nt) {
-        const long long e = t0 + tid;
-        const bool v = e < P && valid[e];
-        int tot;
-        const int r = block_rank(v, wsum, tot);
-        if (v) {
-            long long k[3];
-            for (int a = 0; a < 3; ++a) k[a] = (long long)floor((pc[3 * e + a] - mb[a]) / kVoxel);
-            key0[nv + r] = (k[0] * dy + k[1]) * dz + k[2];
-            idx0[nv + r] = (int)e;
-        }
-        nv += tot;
-    }
-    __syncthreads();
-    // stable LSD radix sort, 4-bit digits
-    const int w = tid >> 6, lane = rp_lane();
-    for (int sh = 0; sh < bits; sh += 4) {
-        if (tid < 16) base[tid] = 0;
-        __syncthreads();
-        for (int e = tid; e < nv; e += nt) atomicAdd(&base[(key0[e] >> sh) & 15], 1);
-        __syncthreads();
-        if (tid == 0) {
-            int s = 0;
-            for (int d = 0; d < 16; ++d) { const int v = base[d]; base[d] = s; s += v; }
-        }
-        __syncthreads();
-        for (int t0 = 0; t0 < nv; t0 += nt) {
-            const int e = t0 + tid;
-            const bool in = e < nv;
-            const long long k = in ? key0[e] : 0;
-            const int d = in ? (int)((k >> sh) & 15) : -1;
-            int rank = 0;
-            for (int dd = 0; dd < 16; ++dd) {
-                const unsigned long long m = __ballot(d == dd);
-                if (d == dd) rank = __popcll(m & lanes_below());
-                if (lane == 0) digit_cnt[w][dd] = __popcll(m);
-            }
-            __syncthreads();
-            if (in) {
-                int off = base[d] + rank;
-                for (int k2 = 0; k2 < w; ++k2) off += digit_cnt[k2][d];
-                key1[off] = k;
-                idx1[off] = idx0[e];
-            }
-            __syncthreads();
-            if (tid < 16) {
-                int s = 0;
-                for (int k2 = 0; k2 < nt / 64; ++k2) s += digit_cnt[k2][tid];
-                base[tid] += s;
-            }
-            __syncthreads();
-        }
-        long long* tk = key0; key0 = key1; key1 = tk;
-        int* ti = idx0; idx0 = idx1; idx1 = ti;
-    }
-    // segmented means: one thread per voxel start, summing its points sequentially in input order
-    double* out = f.pts + (long long)c * f.cap * 3;
-    int* oix = f.ix + (long long)c * f.cap;
-    int nvox = 0;
-    for (int t0 = 0; t0 < nv; t0 += nt) {
-        const int e = t0 + tid;
-        const bool st = e < nv && (e == 0 || key0[e] != key0[e - 1]);
-        int tot;
-        const int r = block_rank(st, wsum, tot);
-        const int o = nvox + r;
-        if (st && o < f.cap) {
-            const long long k = key0[e];
-            double s[3] = {0.0, 0.0, 0.0};
-            int m = 0;
-            for (int j = e; j < nv && key0[j] == k; ++j, ++m) {
-                const long long i = idx0[j];
-                for (int a = 0; a < 3; ++a) s[a] += pc[3 * i + a];
-            }
-            for (int a = 0; a < 3; ++a) out[3 * o + a] = s[a] / (double)m;
-            oix[o] = (int)(k / (dy * dz));
-        }
-        nvox += tot;
-    }
-    if (tid == 0) f.count[c] = nvox;
+    __shared__ RpVoxelScratch lds;
+    const FgrVoxelPolicy pol{f.ix + (long long)c * f.cap};
+    const int nvox = rp_voxel_downsample(f.pc + (long long)c * P * 3, f.valid + (long long)c * P, P, kVoxel, f.key[0] + (long long)c * P,
+                                         f.idx[0] + (long long)c * P, f.key[1] + (long long)c * P, f.idx[1] + (long long)c * P,
+                                         f.pts + (long long)c * f.cap * 3, f.cap, lds, pol);
+    if (threadIdx.x == 0) f.count[c] = nvox;
 }
 
 // ------------------------------------------------------------------------------------------------------- 2. neighbours
-__device__ __forceinline__ bool lex_less(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
-
-__device__ __forceinline__ int lower_bound_ix(const int* ix, int n, int v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ix[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // keep the kNnFpfh smallest (d2, index) of buf[0..m) in order at buf[0..min(m, K))
 __device__ int select_k(double* bd, int* bi, double* td, int* ti, int m) {
     const int lane = threadIdx.x;
@@ -219,7 +80,7 @@ __device__ int select_k(double* bd, int* bi, double* td, int* ti, int m) {
         const double de = bd[e];
         const int ie = bi[e];
         int rank = 0;
-        for (int g = 0; g < m; ++g) rank += lex_less(bd[g], bi[g], de, ie) ? 1 : 0;
+        for (int g = 0; g < m; ++g) rank += rp_lex_less(bd[g], bi[g], de, ie) ? 1 : 0;
         if (rank < kNnFpfh) { td[rank] = de; ti[rank] = ie; }
     }
     __syncthreads();
@@ -239,7 +100,7 @@ __global__ __launch_bounds__(64) void fgr_neighbors_kernel(FgrBufs f) {
     const double r2 = kRFpfh * kRFpfh;
     for (int q = blockIdx.x; q < n; q += gridDim.x) {
         const double qx = pts[3 * q], qy = pts[3 * q + 1], qz = pts[3 * q + 2];
-        const int lo = lower_bound_ix(ix, n, ix[q] - kSlab), hi = lower_bound_ix(ix, n, ix[q] + kSlab + 1);
+        const int lo = rp_lower_bound(ix, n, ix[q] - kSlab), hi = rp_lower_bound(ix, n, ix[q] + kSlab + 1);
         int m = 0;
         bool full = false;
         double bnd_d = 0.0;
@@ -251,7 +112,7 @@ __global__ __launch_bounds__(64) void fgr_neighbors_kernel(FgrBufs f) {
             if (cnd < hi) {
                 const double dx = pts[3 * cnd] - qx, dy = pts[3 * cnd + 1] - qy, dz = pts[3 * cnd + 2] - qz;
                 d2 = (dx * dx + dy * dy) + dz * dz;
-                in = d2 < r2 && (!full || lex_less(d2, cnd, bnd_d, bnd_i));
+                in = d2 < r2 && (!full || rp_lex_less(d2, cnd, bnd_d, bnd_i));
             }
             unsigned long long msk = __ballot(in);
             if (m + __popcll(msk) > kBuf) {
@@ -259,11 +120,11 @@ __global__ __launch_bounds__(64) void fgr_neighbors_kernel(FgrBufs f) {
                 full = true;
                 bnd_d = bd[m - 1];
                 bnd_i = bi[m - 1];
-                in = in && lex_less(d2, cnd, bnd_d, bnd_i);
+                in = in && rp_lex_less(d2, cnd, bnd_d, bnd_i);
                 msk = __ballot(in);
             }
             if (in) {
-                const int o = m + __popcll(msk & lanes_below());
+                const int o = m + __popcll(msk & rp_lanes_below());
                 bd[o] = d2;
                 bi[o] = cnd;
             }
@@ -295,67 +156,12 @@ __global__ __launch_bounds__(256) void fgr_normals_kernel(FgrBufs f) {
     const double rn2 = kRNormal * kRNormal;
     int m = 0;
     while (m < cnt && m < kNnNormal && nd[m] < rn2) ++m;
-    double nv[3] = {0.0, 0.0, 1.0};
-    if (m >= 3) {
-        double s[3] = {0.0, 0.0, 0.0};
-        for (int j = 0; j < m; ++j)
-            for (int a = 0; a < 3; ++a) s[a] += pts[3 * nb[j] + a];
-        const double mf = (double)m;
-        const double mean[3] = {s[0] / mf, s[1] / mf, s[2] / mf};
-        double C[6] = {0, 0, 0, 0, 0, 0};       // 00 01 02 11 12 22
-        for (int j = 0; j < m; ++j) {
-            const double d0 = pts[3 * nb[j]] - mean[0], d1 = pts[3 * nb[j] + 1] - mean[1], d2 = pts[3 * nb[j] + 2] - mean[2];
-            C[0] += d0 * d0; C[1] += d0 * d1; C[2] += d0 * d2; C[3] += d1 * d1; C[4] += d1 * d2; C[5] += d2 * d2;
-        }
-        double A[3][3];
-        A[0][0] = C[0] / mf; A[0][1] = A[1][0] = C[1] / mf; A[0][2] = A[2][0] = C[2] / mf;
-        A[1][1] = C[3] / mf; A[1][2] = A[2][1] = C[4] / mf; A[2][2] = C[5] / mf;
-        double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-#pragma unroll
-        for (int sw = 0; sw < kJacobiSweeps; ++sw) {
-#pragma unroll
-            for (int rot = 0; rot < 3; ++rot) {
-                const int p = rot == 2 ? 1 : 0, qq = rot == 0 ? 1 : 2, r = 3 - p - qq;
-                const double apq = A[p][qq];
-                if (apq != 0.0) {
-                    const double theta = (A[qq][qq] - A[p][p]) / (2.0 * apq);
-                    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    if (theta < 0) t = -t;
-                    const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-                    const double app = A[p][p] - t * apq, aqq = A[qq][qq] + t * apq;
-                    const double arp = A[r][p], arq = A[r][qq];
-                    const double nrp = cs * arp - sn * arq, nrq = sn * arp + cs * arq;
-                    A[p][p] = app; A[qq][qq] = aqq; A[p][qq] = A[qq][p] = 0.0;
-                    A[r][p] = A[p][r] = nrp; A[r][qq] = A[qq][r] = nrq;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const double vkp = V[k][p], vkq = V[k][qq];
-                        V[k][p] = cs * vkp - sn * vkq;
-                        V[k][qq] = sn * vkp + cs * vkq;
-                    }
-                }
-            }
-        }
-        int k = A[1][1] < A[0][0] ? 1 : 0;
-        const double ek = k == 1 ? A[1][1] : A[0][0];
-        if (A[2][2] < ek) k = 2;
-        const double v0 = k == 0 ? V[0][0] : (k == 1 ? V[0][1] : V[0][2]);
-        const double v1 = k == 0 ? V[1][0] : (k == 1 ? V[1][1] : V[1][2]);
-        const double v2 = k == 0 ? V[2][0] : (k == 1 ? V[2][1] : V[2][2]);
-        const double nn = sqrt((v0 * v0 + v1 * v1) + v2 * v2);
-        nv[0] = v0 / nn; nv[1] = v1 / nn; nv[2] = v2 / nn;
-    }
-    const double w0 = 0.0 - pts[3 * q], w1 = 0.0 - pts[3 * q + 1], w2 = 0.0 - pts[3 * q + 2];
-    if ((nv[0] * w0 + nv[1] * w1) + nv[2] * w2 < 0) { nv[0] = -nv[0]; nv[1] = -nv[1]; nv[2] = -nv[2]; }
+    double nv[3];
+    rp_normal_from_neighbors(pts, nb, m, pts + 3 * q, nv);
     for (int a = 0; a < 3; ++a) f.normal[row * 3 + a] = nv[a];
 }
 
 // ------------------------------------------------------------------------------------------------------- 4. SPFH / FPFH
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
 __device__ __forceinline__ int lin_bin(double v) {
     const int h = (int)floor(11 * (v + 1.0) * 0.5);
     return h < 0 ? 0 : (h > 10 ? 10 : h);
@@ -375,10 +181,10 @@ __device__ __forceinline__ int angle_bin(double x, double y) {
 // Open3D's ComputePairFeatures + the SPFH binning; the zero feature -> bins 5, 5, 5
 __device__ void pair_bins(const double* p1, const double* n1, const double* p2, const double* n2, int* bins) {
     double dp[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
-    const double L = sqrt(fgr_dot3(dp, dp));
+    const double L = sqrt(rp_dot3(dp, dp));
     bins[0] = bins[1] = bins[2] = 5;
     if (L == 0.0) return;
-    const double a1 = fgr_dot3(n1, dp) / L, a2 = fgr_dot3(n2, dp) / L;
+    const double a1 = rp_dot3(n1, dp) / L, a2 = rp_dot3(n2, dp) / L;
     const double* m1 = n1;
     const double* m2 = n2;
     double f2 = a1;
@@ -388,13 +194,13 @@ __device__ void pair_bins(const double* p1, const double* n1, const double* p2, 
         f2 = -a2;
     }
     double v[3], w[3];
-    cross3(dp, m1, v);
-    const double vn = sqrt(fgr_dot3(v, v));
+    rp_cross3(dp, m1, v);
+    const double vn = sqrt(rp_dot3(v, v));
     if (vn == 0.0) return;
     v[0] = v[0] / vn; v[1] = v[1] / vn; v[2] = v[2] / vn;
-    cross3(m1, v, w);
-    bins[0] = angle_bin(fgr_dot3(m1, m2), fgr_dot3(w, m2));
-    bins[1] = lin_bin(fgr_dot3(v, m2));
+    rp_cross3(m1, v, w);
+    bins[0] = angle_bin(rp_dot3(m1, m2), rp_dot3(w, m2));
+    bins[1] = lin_bin(rp_dot3(v, m2));
     bins[2] = lin_bin(f2);
 }
 
@@ -515,7 +321,7 @@ __global__ __launch_bounds__(1024) void fgr_match_kernel(FgrBufs f) {
             const int j = i < ns ? nns[i] : -1;
             const bool mu = j >= 0 && nnt[j] == i;
             int tot;
-            const int r = block_rank(mu, wsum, tot);
+            const int r = rp_block_rank(mu, wsum, tot);
             if (mu) { corr[2 * (nc + r)] = i; corr[2 * (nc + r) + 1] = j; }
             nc += tot;
         }
@@ -540,13 +346,13 @@ __global__ __launch_bounds__(1024) void fgr_match_kernel(FgrBufs f) {
                 const double* c0 = pt + 3 * corr[2 * r[0] + 1];
                 const double* c1 = pt + 3 * corr[2 * r[1] + 1];
                 const double* c2 = pt + 3 * corr[2 * r[2] + 1];
-                const double li[3] = {fgr_dist3(a0, a1), fgr_dist3(a1, a2), fgr_dist3(a2, a0)};
-                const double lj[3] = {fgr_dist3(c0, c1), fgr_dist3(c1, c2), fgr_dist3(c2, c0)};
+                const double li[3] = {rp_dist3(a0, a1), rp_dist3(a1, a2), rp_dist3(a2, a0)};
+                const double lj[3] = {rp_dist3(c0, c1), rp_dist3(c1, c2), rp_dist3(c2, c0)};
                 ok = true;
                 for (int k = 0; k < 3; ++k) ok = ok && (li[k] * kTupleScale < lj[k]) && (lj[k] < li[k] / kTupleScale);
             }
             int tot;
-            const int rk = block_rank(ok, wsum, tot) + ntup;
+            const int rk = rp_block_rank(ok, wsum, tot) + ntup;
             if (ok && rk < kMaxTuples)
                 for (int k = 0; k < 3; ++k) {
                     tc[2 * (3 * rk + k)] = corr[2 * r[k]];
@@ -562,16 +368,6 @@ __global__ __launch_bounds__(1024) void fgr_match_kernel(FgrBufs f) {
 }
 
 // ------------------------------------------------------------------------------------------------------- 6. optimisation
-// Sum of v over the block (256 threads): per-wave xor tree, then the 4 wave partials in order.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += rp_shfl_xor_d(v, m);
-    __syncthreads();
-    if (rp_lane() == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ __launch_bounds__(256) void fgr_optimize_kernel(FgrBufs f) {
     const int b = blockIdx.x, tid = threadIdx.x;
     __shared__ double red[4];
@@ -594,24 +390,19 @@ __global__ __launch_bounds__(256) void fgr_optimize_kernel(FgrBufs f) {
         double s = 0.0, u = 0.0;
         for (int i = tid; i < ns; i += 256) s += ps[3 * i + a];
         for (int i = tid; i < nt; i += 256) u += pt[3 * i + a];
-        ms[a] = block_sum(s, red) / (double)ns;
-        mt[a] = block_sum(u, red) / (double)nt;
+        ms[a] = rp_block_xor_sum<4>(s, red) / (double)ns;
+        mt[a] = rp_block_xor_sum<4>(u, red) / (double)nt;
     }
     double mx = 0.0;
     for (int i = tid; i < ns; i += 256) {
         const double d[3] = {ps[3 * i] - ms[0], ps[3 * i + 1] - ms[1], ps[3 * i + 2] - ms[2]};
-        mx = fmax(mx, sqrt(fgr_dot3(d, d)));
+        mx = fmax(mx, sqrt(rp_dot3(d, d)));
     }
     for (int i = tid; i < nt; i += 256) {
         const double d[3] = {pt[3 * i] - mt[0], pt[3 * i + 1] - mt[1], pt[3 * i + 2] - mt[2]};
-        mx = fmax(mx, sqrt(fgr_dot3(d, d)));
+        mx = fmax(mx, sqrt(rp_dot3(d, d)));
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) mx = fmax(mx, rp_shfl_xor_d(mx, m));
-    __syncthreads();
-    if (rp_lane() == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    const double scale = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    const double scale = rp_block_max<4>(mx, red);
     const int m = 3 * f.ntup[b];
     const int* tc = f.tcorr + (long long)b * kMaxTuples * 6;
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
@@ -628,7 +419,7 @@ __global__ __launch_bounds__(256) void fgr_optimize_kernel(FgrBufs f) {
             double q[3];
             for (int a = 0; a < 3; ++a) q[a] = ((R[3 * a] * q0[0] + R[3 * a + 1] * q0[1]) + R[3 * a + 2] * q0[2]) + t[a];
             const double r[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
-            const double w = par / (fgr_dot3(r, r) + par);
+            const double w = par / (rp_dot3(r, r) + par);
             const double s = w * w;
             const double J[3][6] = {{0, -q[2], q[1], -1, 0, 0}, {q[2], 0, -q[0], 0, -1, 0}, {-q[1], q[0], 0, 0, 0, -1}};
             int k = 0;
@@ -641,13 +432,15 @@ __global__ __launch_bounds__(256) void fgr_optimize_kernel(FgrBufs f) {
             for (int u = 0; u < 6; ++u) acc[21 + u] += s * ((J[0][u] * r[0] + J[1][u] * r[1]) + J[2][u] * r[2]);
         }
         double tot[27];
-        for (int k = 0; k < 27; ++k) tot[k] = block_sum(acc[k], red);
+        for (int k = 0; k < 27; ++k) tot[k] = rp_block_xor_sum<4>(acc[k], red);
         if (tid == 0) {
             double A[6][6], L[6][6] = {}, y[6], x[6] = {0, 0, 0, 0, 0, 0};
             int k = 0;
             for (int u = 0; u < 6; ++u)
                 for (int v = u; v < 6; ++v, ++k) A[u][v] = A[v][u] = tot[k];
             bool ok = true;
+            // Every product is subtracted from the running value; cicp.hip's chol_solve sums the products from 0 and subtracts once.  The two
+            // round differently and each is pinned by its own numpy model: do not unify them.
             for (int j = 0; j < 6 && ok; ++j) {
                 double s = A[j][j];
                 for (int kk = 0; kk < j; ++kk) s -= L[j][kk] * L[j][kk];
@@ -702,8 +495,6 @@ __global__ __launch_bounds__(256) void fgr_optimize_kernel(FgrBufs f) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct FgrPlan {
     size_t off_key0, off_key1, off_idx0, off_idx1, off_pts, off_ix, off_count, off_nbr, off_nd2, off_ncnt, off_normal, off_spfh, off_fpfh,
         off_f32, off_nn, off_corr, off_ncorr, off_tcorr, off_ntup, off_pose, total;
@@ -713,7 +504,7 @@ bool fgr_plan(int B, int P, int cap, FgrPlan& p) {
     if (B <= 0 || P <= 0 || cap <= 0 || cap > RELPOSE_FGR_MAX_POINTS_LIMIT || (long long)P > (1LL << 30)) return false;
     const size_t C = 2 * (size_t)B, N = (size_t)cap;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = off; off += rp_align(bytes); return o; };
     p.off_key0 = take(C * P * 8);
     p.off_key1 = take(C * P * 8);
     p.off_idx0 = take(C * P * 4);

@@ -1,5 +1,6 @@
 // The front end shared by relpose_fgr (fgr.hip) and relpose_ransac (ransac.hip): stages 1-4 of DESIGN.md §4.6 (voxels, neighbour
-// lists, normals, FPFH) and the exact fp32 feature nearest neighbour, and the small device helpers both contracts name.
+// lists, normals, FPFH) and the exact fp32 feature nearest neighbour, and the draw generator both contracts name.  (The device helpers the
+// two share with the other point-cloud kernels -- dot, distance, scans, sort, reductions -- are in cloud_prims.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,12 +41,4 @@ __device__ __forceinline__ unsigned long long fgr_splitmix(unsigned long long x)
     x ^= x >> 27;
     x *= 0x94D049BB133111EBull;
     return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ double fgr_dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-// |a - b| with d = a - b and (d0^2 + d1^2) + d2^2
-__device__ __forceinline__ double fgr_dist3(const double* a, const double* b) {
-    const double d[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
-    return sqrt(fgr_dot3(d, d));
 }

@@ -6,33 +6,16 @@
 // reproj_helper :537-749, Pano2PointCloud :751-811; rputil.py interpolate :43-58,
 // getPixel :61-119; evaluation.py :217-270.
 //
+// The face rotations are skybox.h's, shared with panorama.hip and visibility.hip.
+//
 // Compiled with -ffp-contract=off: pixel rounding and the float32 bilinear
 // descriptor gather must round like numpy / torch (no FMA fusion).
 #include "common.h"
 #include "rp_math.h"
+#include "skybox.h"
 #include <limits.h>
 
 namespace {
-
-// Face rotations Rs[k] of the skybox (util.py:757-761).  Entries are 0/+-1, so applying
-// them is an exact permutation/sign flip.  ROT(k, v) = Rs[k] @ v ;  ROTT = Rs[k]^T @ v.
-__device__ __forceinline__ void face_rot(int k, double x, double y, double z, double& ox, double& oy, double& oz) {
-    switch (k & 3) {
-        case 0: ox = x; oy = y; oz = z; break;
-        case 1: ox = -z; oy = y; oz = x; break;
-        case 2: ox = -x; oy = y; oz = -z; break;
-        default: ox = z; oy = y; oz = -x; break;
-    }
-}
-__device__ __forceinline__ void face_rot_t(int k, double x, double y, double z, double& ox, double& oy, double& oz) {
-    switch (k & 3) {
-        case 0: ox = x; oy = y; oz = z; break;
-        case 1: ox = z; oy = y; oz = -x; break;
-        case 2: ox = -x; oy = y; oz = -z; break;
-        default: ox = -z; oy = y; oz = x; break;
-    }
-}
-__device__ __forceinline__ int face_index(int dataset, int slot) { return dataset == RELPOSE_SUNCG ? slot : (slot + 3) & 3; }
 
 struct Box { int y0, y1, x0, x1; };
 __host__ __device__ inline Box observed_box(int method, int h) {
@@ -94,7 +77,7 @@ __global__ void pano2pc_kernel(const float* __restrict__ depth, double* __restri
         if (dataset == RELPOSE_SCANNET) { y = ys * z / (1.1895 * 2); x = xs * z / (0.8921875 * 2); }
         else { y = ys * z; x = xs * z; }
         double ox, oy, oz;
-        face_rot(face_index(dataset, face), x, y, -z, ox, oy, oz);
+        rp_face_rot(rp_face_index(dataset, face), x, y, -z, ox, oy, oz);
         double* o = pc + img * 3 * hw;
         o[q] = ox; o[hw + q] = oy; o[2 * hw + q] = oz;
         if (valid) valid[idx] = (dataset == RELPOSE_SCANNET) ? (z != 0.0) : 1;
@@ -131,7 +114,7 @@ __device__ __forceinline__ bool warp_point(const float* view, const double* T, i
     } else {
         const double xs = ((double)u / h - 0.5) * 2, ys = (0.5 - (double)v / h) * 2;
         x = xs * z; y = ys * z;
-        if (dataset == RELPOSE_SUNCG) face_rot(1, x, y, -z, X, Y, Z);   // observed face = slot 1, Rs[1]
+        if (dataset == RELPOSE_SUNCG) rp_face_rot(1, x, y, -z, X, Y, Z);   // observed face = slot 1, Rs[1]
         else { X = x; Y = y; Z = -z; }                                  // matterport: Rs[(1-1)%4] = I
     }
     // np.matmul(R44, [p;1])[:3]
@@ -140,10 +123,11 @@ __device__ __forceinline__ bool warp_point(const float* view, const double* T, i
     return true;
 }
 
-// Projection of a moved point into face slot `slot` (reproj_helper).  Returns pixel or -1.
+// Projection of a moved point into face slot `slot` (reproj_helper).  Returns pixel or -1.  Not skybox.h's rp_skybox_project: that one
+// searches the first slot and divides only behind its |x| < az test; this one is asked about one given slot and divides first.
 __device__ __forceinline__ int warp_project(const double* q, int h, int dataset, int slot, double& depth_out) {
     double x, y, z;
-    face_rot_t(face_index(dataset, slot), q[0], q[1], q[2], x, y, z);
+    rp_face_rot_t(rp_face_index(dataset, slot), q[0], q[1], q[2], x, y, z);
     const double az = fabs(z) + 1e-32;
     const double xn = x / az, yn = y / az;
     if (!((z < 0) && (fabs(xn) < 1) && (fabs(yn) < 1))) return -1;
@@ -281,7 +265,7 @@ __global__ void sample_primitives_kernel(const float* __restrict__ f, int cf, in
     const int slot = (int)floor(px / h);          // xs // H
     const double ystp = (0.5 - py / h) * 2, xstp = ((px - slot * h) / h - 0.5) * 2;
     double ox, oy, oz;
-    face_rot(face_index(dataset, slot), xstp * val, ystp * val, -val, ox, oy, oz);
+    rp_face_rot(rp_face_index(dataset, slot), xstp * val, ystp * val, -val, ox, oy, oz);
     double* po = pc + ((size_t)img * npts_max + k) * 3;
     po[0] = ox; po[1] = oy; po[2] = oz;
     // rputil.interpolate :43-58 in float32: pt = (x/W, y/H) cast to float32, x = pt*(W-1)
@@ -329,7 +313,7 @@ __global__ void get_pixel_kernel(const double* __restrict__ depth, const double*
     const int slot = (int)floor(px / h);
     const double ystp = (0.5 - py / h) * 2, xstp = ((px - slot * h) / h - 0.5) * 2;
     double ox, oy, oz;
-    face_rot(face_index(dataset, slot), xstp * val, ystp * val, -val, ox, oy, oz);
+    rp_face_rot(rp_face_index(dataset, slot), xstp * val, ystp * val, -val, ox, oy, oz);
     pc[(size_t)k * 3 + 0] = ox; pc[(size_t)k * 3 + 1] = oy; pc[(size_t)k * 3 + 2] = oz;
 }
 
@@ -372,7 +356,7 @@ __global__ void depth2pc_kernel(const float* __restrict__ depth, double* __restr
             X = (xs * z) * s.pw / 160; Y = (ys * z) * ph / 160; Z = -z;
         } else {
             const double xs = ((double)u / h - 0.5) * 2, ys = (0.5 - (double)v / h) * 2;
-            if (dataset == RELPOSE_SUNCG) face_rot(1, xs * z, ys * z, -z, X, Y, Z);
+            if (dataset == RELPOSE_SUNCG) rp_face_rot(1, xs * z, ys * z, -z, X, Y, Z);
             else { X = xs * z; Y = ys * z; Z = -z; }
         }
         double* o = pc + ((size_t)img * s.npts + p) * 3;

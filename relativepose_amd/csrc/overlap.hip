@@ -21,6 +21,8 @@
 //                           the query's workgroups through atomicMin on the bit pattern; the tile nearest to the block goes first.
 //   overlap_finalize_kernel accumulators -> hits, nn_min = sqrt(min d2), n_valid.
 // A cloud whose extent cannot be keyed raises a flag in the build kernel; the later kernels then return at once and the host reports it.
+// The ordered scan of the compaction, the radix sort and the wave / block minima are cloud_prims.h's, shared with fgr.hip and cicp.hip; the
+// bound and cell pass is this file's own (finite-point filter, origin at the minimum, tile boxes).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +30,7 @@
 #include <cstddef>
 #include <cstring>
 
+#include "cloud_prims.h"
 #include "common.h"
 
 namespace {
@@ -70,31 +73,6 @@ struct OverlapBufs {
     int* bad;
 };
 
-__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << rp_lane()) - 1ull; }
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmin(v, rp_shfl_xor_d(v, m));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, rp_shfl_xor_d(v, m));
-    return v;
-}
-
-// minimum over the workgroup, in every thread; fmin drops NaN operands.  `red` holds one double per wave.
-__device__ double block_min(double v, double* red) {
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    v = wave_min(v);
-    __syncthreads();
-    if (rp_lane() == 0) red[w] = v;
-    __syncthreads();
-    double r = red[0];
-    for (int k = 1; k < nw; ++k) r = fmin(r, red[k]);
-    return r;
-}
-
 __device__ int block_sum_i(int v, int* red) {
     const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
     v = rp_wave_sum_i(v);
@@ -106,33 +84,16 @@ __device__ int block_sum_i(int v, int* red) {
     return r;
 }
 
-// rank of this thread among the threads of the workgroup with f set, and their number
-__device__ int block_rank(bool f, int* wsum, int& total) {
-    const unsigned long long m = __ballot(f);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (rp_lane() == 0) wsum[w] = __popcll(m);
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int k = 0; k < nw; ++k) {
-        const int v = wsum[k];
-        before += k < w ? v : 0;
-        tot += v;
-    }
-    total = tot;
-    return before + __popcll(m & lanes_below());
-}
-
 __device__ __forceinline__ bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // ------------------------------------------------------------------------------------------------------- 1. one grid per cloud
 __global__ __launch_bounds__(kBuildThreads) void overlap_build_kernel(OverlapBufs b) {
     const int c = blockIdx.x, tid = threadIdx.x, nt = kBuildThreads, lane = rp_lane(), w = tid >> 6;
+    static_assert(kBuildThreads == kRpSortThreads, "rp_block_radix_sort");
     const int P = b.P;
     __shared__ double red[16];
     __shared__ int ired[16];
-    __shared__ int digit_cnt[16][16];
-    __shared__ int base[16];
+    __shared__ RpSortScratch sort_lds;
 
     for (long long q = (long long)c * nt + tid; q < b.nq; q += (long long)gridDim.x * nt) {
         b.acc_hits[q] = 0;
@@ -156,8 +117,8 @@ __global__ __launch_bounds__(kBuildThreads) void overlap_build_kernel(OverlapBuf
     }
     nval = block_sum_i(nval, ired);
     for (int a = 0; a < 3; ++a) {
-        lo[a] = block_min(lo[a], red);
-        hi[a] = -block_min(-hi[a], red);
+        lo[a] = rp_block_min<kBuildThreads / 64>(lo[a], red);
+        hi[a] = -rp_block_min<kBuildThreads / 64>(-hi[a], red);
     }
     double cells[3];
     bool bad = false;
@@ -183,7 +144,6 @@ __global__ __launch_bounds__(kBuildThreads) void overlap_build_kernel(OverlapBuf
     long long* key1 = b.key[1] + (size_t)c * P;
     int* idx0 = b.idx[0] + (size_t)c * P;
     int* idx1 = b.idx[1] + (size_t)c * P;
-    int which = 0;
 
     // compaction of the finite valid points, input order kept
     int nv = 0;
@@ -196,7 +156,7 @@ __global__ __launch_bounds__(kBuildThreads) void overlap_build_kernel(OverlapBuf
             v = (!va || va[e]) && finite3(x, y, z);
         }
         int tot;
-        const int r = block_rank(v, ired, tot);
+        const int r = rp_block_rank(v, ired, tot);
         if (v) {
             const long long cx = (long long)floor((x - lo[0]) / b.edge), cy = (long long)floor((y - lo[1]) / b.edge),
                             cz = (long long)floor((z - lo[2]) / b.edge);
@@ -207,47 +167,7 @@ __global__ __launch_bounds__(kBuildThreads) void overlap_build_kernel(OverlapBuf
     }
     __syncthreads();
 
-    // stable LSD radix sort, 4-bit digits
-    for (int sh = 0; sh < bits; sh += 4) {
-        if (tid < 16) base[tid] = 0;
-        __syncthreads();
-        for (int e = tid; e < nv; e += nt) atomicAdd(&base[(key0[e] >> sh) & 15], 1);
-        __syncthreads();
-        if (tid == 0) {
-            int s = 0;
-            for (int d = 0; d < 16; ++d) { const int v = base[d]; base[d] = s; s += v; }
-        }
-        __syncthreads();
-        for (int t0 = 0; t0 < nv; t0 += nt) {
-            const int e = t0 + tid;
-            const bool in = e < nv;
-            const long long k = in ? key0[e] : 0;
-            const int d = in ? (int)((k >> sh) & 15) : -1;
-            int rank = 0;
-            for (int dd = 0; dd < 16; ++dd) {
-                const unsigned long long m = __ballot(d == dd);
-                if (d == dd) rank = __popcll(m & lanes_below());
-                if (lane == 0) digit_cnt[w][dd] = __popcll(m);
-            }
-            __syncthreads();
-            if (in) {
-                int off = base[d] + rank;
-                for (int k2 = 0; k2 < w; ++k2) off += digit_cnt[k2][d];
-                key1[off] = k;
-                idx1[off] = idx0[e];
-            }
-            __syncthreads();
-            if (tid < 16) {
-                int s = 0;
-                for (int k2 = 0; k2 < nt / 64; ++k2) s += digit_cnt[k2][tid];
-                base[tid] += s;
-            }
-            __syncthreads();
-        }
-        long long* tk = key0; key0 = key1; key1 = tk;
-        int* ti = idx0; idx0 = idx1; idx1 = ti;
-        which ^= 1;
-    }
+    const int which = rp_block_radix_sort(key0, idx0, key1, idx1, nv, bits, sort_lds);
 
     // coordinates in key order
     double* sx = b.sx + (size_t)c * P;
@@ -272,8 +192,8 @@ __global__ __launch_bounds__(kBuildThreads) void overlap_build_kernel(OverlapBuf
             }
         }
         for (int a = 0; a < 3; ++a) {
-            l[a] = wave_min(l[a]);
-            h[a] = wave_max(h[a]);
+            l[a] = rp_wave_min(l[a]);
+            h[a] = rp_wave_max(h[a]);
         }
         if (lane == 0)
             for (int a = 0; a < 3; ++a) { box[(size_t)t * 6 + a] = l[a]; box[(size_t)t * 6 + 3 + a] = h[a]; }
@@ -296,15 +216,6 @@ __device__ __forceinline__ void moved_point(const OverlapBufs& b, int qc, int q,
         y = ((T[4] * a + T[5] * bb) + T[6] * c) + T[7];
         z = ((T[8] * a + T[9] * bb) + T[10] * c) + T[11];
     }
-}
-
-__device__ __forceinline__ int lower_bound_key(const long long* keys, int n, long long v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // ------------------------------------------------------------------------------------------------------- 2. the 27 cells
@@ -347,7 +258,7 @@ __global__ __launch_bounds__(kTile) void overlap_grid_kernel(OverlapBufs b) {
                     for (long long ay = cy - 1; ay <= cy + 1; ++ay) {
                         if (ay < 0 || ay >= hr.ny) continue;
                         const long long k0 = (ax * hr.ny + ay) * hr.nz + z0, k1 = (ax * hr.ny + ay) * hr.nz + z1;
-                        for (int e = lower_bound_key(keys, nvr, k0); e < nvr && keys[e] <= k1; ++e) {
+                        for (int e = rp_lower_bound(keys, nvr, k0); e < nvr && keys[e] <= k1; ++e) {
                             const double dx = x - rx[e], dy = y - ry[e], dz = z - rz[e];
                             const double d2 = (dx * dx + dy * dy) + dz * dz;
                             best = d2 < best ? d2 : best;
@@ -360,7 +271,7 @@ __global__ __launch_bounds__(kTile) void overlap_grid_kernel(OverlapBufs b) {
     const bool h = i < nvq && sqrt(best) < b.max_dist;
     if (i < nvq && b.hit) b.hit[(size_t)q * P + b.idx[hq.which][(size_t)qc * P + i]] = h ? 1 : 0;
     const int cnt = __popcll(__ballot(h));
-    const double wmin = wave_min(best);
+    const double wmin = rp_wave_min(best);
     if (lane == 0) {
         if (cnt) atomicAdd(&s_hits, cnt);
         if (wmin < INFINITY) atomicMin(&s_d2, (unsigned long long)__double_as_longlong(wmin));
@@ -399,8 +310,8 @@ __global__ __launch_bounds__(kTile) void overlap_closest_kernel(OverlapBufs b) {
     moved_point(b, qc, q, blk * kTile + tid, nvq, x, y, z);
     if (!finite3(x, y, z)) x = y = z = __builtin_nan("");    // never nearer than anything, and outside the block's box
     double blo[3], bhi[3];
-    blo[0] = block_min(x, red); blo[1] = block_min(y, red); blo[2] = block_min(z, red);
-    bhi[0] = -block_min(-x, red); bhi[1] = -block_min(-y, red); bhi[2] = -block_min(-z, red);
+    blo[0] = rp_block_min<kTile / 64>(x, red); blo[1] = rp_block_min<kTile / 64>(y, red); blo[2] = rp_block_min<kTile / 64>(z, red);
+    bhi[0] = -rp_block_min<kTile / 64>(-x, red); bhi[1] = -rp_block_min<kTile / 64>(-y, red); bhi[2] = -rp_block_min<kTile / 64>(-z, red);
     if (!(blo[0] <= bhi[0])) return;                     // no finite moved point in this block
 
     const double* box = b.box + (size_t)rc * b.nblk * 6;
@@ -458,7 +369,7 @@ __global__ __launch_bounds__(kTile) void overlap_closest_kernel(OverlapBufs b) {
                 best = d2 < best ? d2 : best;
             }
         }
-        const double wmin = wave_min(best);
+        const double wmin = rp_wave_min(best);
         if (lane == 0 && wmin < bound) atomicMin(b.acc_d2 + q, (unsigned long long)__double_as_longlong(wmin));
         __syncthreads();
         if (tid == 0) s_bound = __hip_atomic_load(b.acc_d2 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

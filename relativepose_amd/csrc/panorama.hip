@@ -1,5 +1,5 @@
 // Skybox panoramas from posed perspective RGB-D frames: every frame pixel with data is unprojected (util.depth2pc's 480x640 branch), moved
-// by its frame's pose, projected into the four-face panorama by reproj_helper's rule (geometry.hip's warp_project, restated here), and the
+// by its frame's pose, projected into the four-face panorama by reproj_helper's rule (skybox.h's rp_skybox_project, shared with visibility.hip), and the
 // points that fall on one panorama pixel are fused by a foreground-gated mean.  The contract -- the float64 geometry, the gate, the integer
 // accumulators, the resolve -- is DESIGN.md §4.13 and the comment above relpose_frames_to_pano in include/relpose.h;
 // tests/panorama_model.py restates it in numpy.  Built with -ffp-contract=off.  Every accumulator is an integer, so the result does not
@@ -27,6 +27,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "skybox.h"
 
 namespace {
 
@@ -52,16 +53,6 @@ struct PanoBufs {
     unsigned* sum_rgb;                // [n, 3, h, 4h]
 };
 
-// Rs[k]^T v (util.py:757-761): entries 0 / +-1, an exact signed permutation
-__device__ __forceinline__ void pano_face_rot_t(int k, double x, double y, double z, double& ox, double& oy, double& oz) {
-    switch (k & 3) {
-        case 0: ox = x; oy = y; oz = z; break;
-        case 1: ox = z; oy = y; oz = -x; break;
-        case 2: ox = -x; oy = y; oz = -z; break;
-        default: ox = -z; oy = y; oz = x; break;
-    }
-}
-
 // Frame pixel (r, c) with depth zf -> panorama pixel (row * 4h + column) and face depth d, or -1 when the point is dropped.
 // sc = (sx, sy), T = the frame's 4x4 pose or NULL.
 __device__ __forceinline__ int pano_point(const PanoBufs& a, const double* sc, const double* T, int r, int c, float zf, float& d) {
@@ -75,29 +66,14 @@ __device__ __forceinline__ int pano_point(const PanoBufs& a, const double* sc, c
         q1 = ((T[4] * X + T[5] * Y) + T[6] * Z) + T[7] * 1.0;
         q2 = ((T[8] * X + T[9] * Y) + T[10] * Z) + T[11] * 1.0;
     }
-    const int h = a.h;
-    int pix = -1;
-    // the first slot whose test passes (the strict tests make the faces disjoint).  |x| >= az implies |x / az| >= 1 after rounding too, so
-    // the divisions are only made where the test can still pass.
-#pragma unroll 1
-    for (int slot = 0; slot < 4 && pix == -1; ++slot) {
-        double x, y, zz;
-        pano_face_rot_t(a.dataset == RELPOSE_SUNCG ? slot : slot + 3, q0, q1, q2, x, y, zz);
-        const double az = fabs(zz) + 1e-32;
-        if (zz < 0 && fabs(x) < az && fabs(y) < az) {
-            const double xn = x / az, yn = y / az;
-            if (fabs(xn) < 1 && fabs(yn) < 1) {
-                double cx = rint((xn + 1) * 0.5 * h), cy = rint((1 - yn) * 0.5 * h);      // round half to even
-                cx = cx < 0 ? 0 : (cx > h - 1 ? h - 1 : cx);
-                cy = cy < 0 ? 0 : (cy > h - 1 ? h - 1 : cy);
-                const int px = slot * h + (int)cx, py = (int)cy;
-                d = (float)(-zz);
-                const bool keep = py >= a.by0 && py < a.by1 && px >= a.bx0 && px < a.bx1 && d < kMaxDepth;
-                pix = keep ? py * 4 * h + px : -2;               // -2: found its face and is dropped
-            }
-        }
-    }
-    return pix;
+    // the first slot whose test passes (skybox.h); the box, the depth cap and the -2 code are this kernel's own
+    int slot, cx, cy;
+    double zz;
+    if (!rp_skybox_project(a.dataset, a.h, q0, q1, q2, slot, cx, cy, zz)) return -1;
+    const int px = slot * a.h + cx, py = cy;
+    d = (float)(-zz);
+    const bool keep = py >= a.by0 && py < a.by1 && px >= a.bx0 && px < a.bx1 && d < kMaxDepth;
+    return keep ? py * 4 * a.h + px : -2;                        // -2: found its face and is dropped
 }
 
 // Claims the table entry of `key`: its index, or -1 when kProbes probes found only other keys.

@@ -2,7 +2,8 @@
 // open3d_global_registration (baselines.py:52-81).  The contract -- draws, checks, orders, reductions -- is DESIGN.md §4.7;
 // tests/ransac_model.py restates it in numpy.  Built with -ffp-contract=off: the model and these kernels round alike.
 //
-// Clouds: c = 2b (source of pair b), 2b + 1 (target).  The front end is relpose_fgr's (fgr_internal.h: six launches), then
+// Clouds: c = 2b (source of pair b), 2b + 1 (target).  The front end is relpose_fgr's (fgr_internal.h: six launches); the exclusive block
+// scan and the xor-tree reductions are cloud_prims.h's.  Then
 //   ransac_grid_kernel      one block per pair: the target's dense cell table (cell 0.16 >= 2 x 0.075, doubled until it fits)
 //   ransac_screen_kernel    per round, one thread per iteration: draws, edge test, Horn + distance test for the survivors, pass bits
 //   ransac_compact_kernel   per round, one block per pair: appends the passing iterations in order until the validated set is full
@@ -18,6 +19,7 @@
 #include <cstring>
 #include <vector>
 
+#include "cloud_prims.h"
 #include "common.h"
 #include "fgr_internal.h"
 #include "rp_math.h"
@@ -83,7 +85,7 @@ __device__ bool ransac_hypothesis(const RansacBufs& r, int b, long long t, doubl
     for (int j = 0; j < 3; ++j)
 #pragma unroll
         for (int k = j + 1; k < 4; ++k) {
-            const double ds = fgr_dist3(s[j], s[k]), dt = fgr_dist3(q[j], q[k]);
+            const double ds = rp_dist3(s[j], s[k]), dt = rp_dist3(q[j], q[k]);
             if (ds < kEdge * dt || dt < kEdge * ds) return false;
         }
     double cs[3], ct[3];
@@ -110,31 +112,9 @@ __device__ bool ransac_hypothesis(const RansacBufs& r, int b, long long t, doubl
         double p[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) p[a] = ((R[a][0] * s[k][0] + R[a][1] * s[k][1]) + R[a][2] * s[k][2]) + tr[a];
-        if (fgr_dist3(p, q[k]) > kMaxDist) return false;
+        if (rp_dist3(p, q[k]) > kMaxDist) return false;
     }
     return true;
-}
-
-// Block-wide exclusive scan of one int per thread (blockDim a multiple of 64, at most 1024) and the total.
-__device__ __forceinline__ int block_excl_scan(int v, int* wsum, int& total) {
-    const int lane = rp_lane(), w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int k = 0; k < nw; ++k) {
-        const int s = wsum[k];
-        before += k < w ? s : 0;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return before + x - v;
 }
 
 // ------------------------------------------------------------------------------------------------------- grid + state
@@ -159,9 +139,7 @@ __global__ __launch_bounds__(1024) void ransac_grid_kernel(RansacBufs r) {
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int i = tid; i < n; i += nt)
         for (int a = 0; a < 3; ++a) { mn[a] = fmin(mn[a], pts[3 * i + a]); mx[a] = fmax(mx[a], pts[3 * i + a]); }
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { mn[a] = fmin(mn[a], rp_shfl_xor_d(mn[a], m)); mx[a] = fmax(mx[a], rp_shfl_xor_d(mx[a], m)); }
+    for (int a = 0; a < 3; ++a) { mn[a] = rp_wave_min(mn[a]); mx[a] = rp_wave_max(mx[a]); }
     if (rp_lane() == 0)
         for (int a = 0; a < 3; ++a) { red[a][tid >> 6] = mn[a]; red[3 + a][tid >> 6] = mx[a]; }
     __syncthreads();
@@ -198,7 +176,7 @@ __global__ __launch_bounds__(1024) void ransac_grid_kernel(RansacBufs r) {
         const int e = e0 + tid;
         const int c = e < ncell ? cfill[e] : 0;
         int tot;
-        const int before = block_excl_scan(c, wsum, tot);
+        const int before = rp_block_excl_scan(c, wsum, tot);
         if (e < ncell) { cstart[e] = run + before; cfill[e] = run + before; }
         run += tot;
     }
@@ -239,7 +217,7 @@ __global__ __launch_bounds__(1024) void ransac_compact_kernel(RansacBufs r, long
         const long long w = c0 + tid;
         unsigned long long m = w < w1 ? bits[w] : 0ull;
         int tot;
-        int slot = nval + block_excl_scan(__popcll(m), wsum, tot);
+        int slot = nval + rp_block_excl_scan(__popcll(m), wsum, tot);
         while (m != 0ull && slot < r.max_val) {
             const long long it = (w << 6) + __builtin_ctzll(m);
             vi[slot] = (int)it;
@@ -300,11 +278,8 @@ __global__ __launch_bounds__(256) void ransac_validate_kernel(RansacBufs r) {
         if (hit) { ++cnt; sum += best; }
     }
     // the fixed reduction of DESIGN.md §4.7 step 7: per-thread sums in point order, xor tree over the wave, the 4 wave sums in order
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        sum += rp_shfl_xor_d(sum, m);
-        cnt += __shfl_xor(cnt, m, 64);
-    }
+    sum = rp_wave_xor_sum(sum);
+    cnt = rp_wave_sum_i(cnt);
     if (rp_lane() == 0) { red[tid >> 6] = sum; redi[tid >> 6] = cnt; }
     __syncthreads();
     if (tid == 0) {
@@ -357,8 +332,6 @@ __global__ __launch_bounds__(64) void ransac_select_kernel(RansacBufs r) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int rounds_for(int max_iter) {
     int n = 0;
     while ((long long)kRound0 * ((1LL << n) - 1) < max_iter) ++n;
@@ -381,7 +354,7 @@ bool ransac_plan(int B, int P, int cap, int max_iter, int max_val, RansacPlan& p
     p.nwords = ((long long)p.max_iter + 63) / 64;
     const size_t C = 2 * (size_t)B, N = (size_t)cap, Bs = (size_t)B;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = off; off += rp_align(bytes); return o; };
     p.off_key0 = take(C * P * 8);
     p.off_key1 = take(C * P * 8);
     p.off_idx0 = take(C * P * 4);

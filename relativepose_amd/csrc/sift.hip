@@ -3,7 +3,8 @@
 // (IJCV 60(2), 2004) with 3 layers per octave, sigma 1.6, contrast 0.02, edge ratio 10 and the image doubled first.  The detection
 // contract -- what every step computes, in which order the floating-point sums run -- is DESIGN.md's "SIFT detector" section;
 // tests/sift_model.py implements the same contract in numpy.  Compiled with -ffp-contract=off: no FMA contraction, so the blur,
-// the differences of Gaussians and the refinement round exactly like the float32 model.
+// the differences of Gaussians and the refinement round exactly like the float32 model.  The source image, its gray value and the border
+// rule are sift_common.h's, shared with siftdesc.hip.
 //
 // Launches (none of them depends on the number of views; views are the z / y grid dimension of each):
 //   per octave   layer 0 (octave 0: gray + x2 upsample + base blur, fused; later octaves: every second pixel of layer 3 before),
@@ -18,7 +19,9 @@
 #include <cstring>
 #include <mutex>
 
+#include "cloud_prims.h"
 #include "common.h"
+#include "sift_common.h"
 
 namespace {
 
@@ -36,14 +39,6 @@ struct SiftTaps {
     float t[2 * SIFT_RMAX + 1];
     int r;
 };
-
-__host__ __device__ inline int refl101(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * n - 2;
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
 
 // candidate / keypoint location: c 12 bits, r 12 bits, layer 2 bits, octave 4 bits
 __device__ inline int kp_code(int o, int l, int r, int c) { return (o << 26) | (l << 24) | (r << 12) | c; }
@@ -66,44 +61,31 @@ __device__ inline int wave_append(bool want, int* counter) {
     int base = 0;
     if (lane == leader) base = atomicAdd(counter, __popcll(m));
     base = __shfl(base, leader, 64);
-    return want ? base + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+    return want ? base + __popcll(m & rp_lanes_below()) : -1;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ gray + blur
-struct SrcImage {
-    const uint8_t* img;
-    long long vstride;   // bytes per view
-    int img_w, channels, cx, cy, cw, ch;
-};
-
-// cv2.COLOR_BGR2GRAY on uint8: 14-bit fixed-point weights B 1868, G 9617, R 4899 (rputil.bgr2gray)
-__device__ inline int gray_at(const SrcImage& s, const uint8_t* im, int y, int x) {
-    const uint8_t* p = im + ((long long)(s.cy + y) * s.img_w + (s.cx + x)) * s.channels;
-    if (s.channels == 1) return p[0];
-    return ((int)p[0] * 1868 + (int)p[1] * 9617 + (int)p[2] * 4899 + (1 << 13)) >> 14;
-}
-
 // x2 bilinear upsample with half-pixel centres: taps 3/4 (nearer source pixel), 1/4 (the other neighbour, edge clamped)
-__device__ inline float up_at(const SrcImage& s, const uint8_t* im, int gy, int gx) {
-    const int ny = gy >> 1, fy = (gy & 1) ? min(ny + 1, s.ch - 1) : max(ny - 1, 0);
-    const int nx = gx >> 1, fx = (gx & 1) ? min(nx + 1, s.cw - 1) : max(nx - 1, 0);
-    const float a = (float)gray_at(s, im, ny, nx), b = (float)gray_at(s, im, ny, fx);
-    const float c = (float)gray_at(s, im, fy, nx), d = (float)gray_at(s, im, fy, fx);
+__device__ inline float up_at(const SiftImage& s, const uint8_t* im, int gy, int gx) {
+    const int ny = gy >> 1, fy = (gy & 1) ? min(ny + 1, s.h - 1) : max(ny - 1, 0);
+    const int nx = gx >> 1, fx = (gx & 1) ? min(nx + 1, s.w - 1) : max(nx - 1, 0);
+    const float a = (float)sift_gray_at(s, im, ny, nx), b = (float)sift_gray_at(s, im, ny, fx);
+    const float c = (float)sift_gray_at(s, im, fy, nx), d = (float)sift_gray_at(s, im, fy, fx);
     return 0.75f * (0.75f * a + 0.25f * b) + 0.25f * (0.75f * c + 0.25f * d);
 }
 
-__global__ __launch_bounds__(256) void sift_gray_kernel(SrcImage s, uint8_t* __restrict__ gray) {
+__global__ __launch_bounds__(256) void sift_gray_kernel(SiftImage s, uint8_t* __restrict__ gray) {
     const int v = blockIdx.y;
-    const int n = s.cw * s.ch;
+    const int n = s.w * s.h;
     const uint8_t* im = s.img + v * s.vstride;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
-        gray[(long long)v * n + i] = (uint8_t)gray_at(s, im, i / s.cw, i % s.cw);
+        gray[(long long)v * n + i] = (uint8_t)sift_gray_at(s, im, i / s.w, i % s.w);
 }
 
 // One Gaussian layer: dst = blur(src) (rows first, then columns, float32 intermediate, reflect-101 border), taps summed in index order.
 // UP: the source is the gray crop of the uint8 images, upsampled x2 on the fly (octave 0 layer 0).  dog != NULL: also dog = dst - src.
 template <bool UP>
-__global__ __launch_bounds__(256) void sift_blur_kernel(const float* __restrict__ src, long long src_vstride, SrcImage s, float* __restrict__ dst,
+__global__ __launch_bounds__(256) void sift_blur_kernel(const float* __restrict__ src, long long src_vstride, SiftImage s, float* __restrict__ dst,
                                                         long long dst_vstride, float* __restrict__ dog, long long dog_vstride, int H, int W, SiftTaps tp) {
     __shared__ float tin[BT_H + 2 * SIFT_RMAX][BT_W + 2 * SIFT_RMAX];
     __shared__ float tmid[BT_H + 2 * SIFT_RMAX][BT_W];
@@ -114,7 +96,7 @@ __global__ __launch_bounds__(256) void sift_blur_kernel(const float* __restrict_
     const uint8_t* im = UP ? s.img + v * s.vstride : nullptr;
     for (int i = threadIdx.x; i < rows * cols; i += 256) {
         const int ly = i / cols, lx = i - ly * cols;
-        const int gy = refl101(y0 + ly - R, H), gx = refl101(x0 + lx - R, W);
+        const int gy = sift_refl101(y0 + ly - R, H), gx = sift_refl101(x0 + lx - R, W);
         tin[ly][lx] = UP ? up_at(s, im, gy, gx) : sv[(long long)gy * W + gx];
     }
     __syncthreads();
@@ -427,7 +409,6 @@ struct SiftPlan {
     size_t off_g, off_d, off_cand, off_ref, off_stage, off_cnt, total;
 };
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int sift_octaves(int h, int w) {
     return (int)std::floor(std::log2((double)std::min(h, w)) - 2.0 + 0.5) + 1;
@@ -454,12 +435,12 @@ bool sift_plan(int V, int h, int w, int max_kp, SiftPlan& p) {
     while (sc < std::max(4 * max_kp, 8192)) sc <<= 1;
     p.stage_cap = sc;
     size_t off = 0;
-    p.off_g = off; off += al(gsum * sizeof(float));
-    p.off_d = off; off += al(dsum * sizeof(float));
-    p.off_cand = off; off += al((size_t)V * p.cand_cap * sizeof(int));
-    p.off_ref = off; off += al((size_t)V * sc * sizeof(RefKp));
-    p.off_stage = off; off += al((size_t)5 * V * sc * sizeof(float));
-    p.off_cnt = off; off += al((size_t)(3 * V + 1) * sizeof(int));
+    p.off_g = off; off += rp_align(gsum * sizeof(float));
+    p.off_d = off; off += rp_align(dsum * sizeof(float));
+    p.off_cand = off; off += rp_align((size_t)V * p.cand_cap * sizeof(int));
+    p.off_ref = off; off += rp_align((size_t)V * sc * sizeof(RefKp));
+    p.off_stage = off; off += rp_align((size_t)5 * V * sc * sizeof(float));
+    p.off_cnt = off; off += rp_align((size_t)(3 * V + 1) * sizeof(int));
     p.total = off;
     return true;
 }
@@ -529,7 +510,7 @@ int relpose_sift_detect(const RelposeSiftArgs* args_in) {
     Stage st{stg, stg + V * sc, stg + 2 * V * sc, stg + 3 * V * sc, stg + 4 * V * sc, p.stage_cap};
     RP_HIP(hipMemsetAsync(cnt, 0, (size_t)(3 * V + 1) * sizeof(int), s));
 
-    SrcImage src{a.images, (long long)a.img_h * a.img_w * a.channels, a.img_w, a.channels, a.crop_x, a.crop_y, a.crop_w, a.crop_h};
+    SiftImage src{a.images, (long long)a.img_h * a.img_w * a.channels, a.img_w, a.channels, a.crop_x, a.crop_y, a.crop_w, a.crop_h};
     if (a.gray) {
         const int n = a.crop_w * a.crop_h;
         hipLaunchKernelGGL(sift_gray_kernel, dim3(std::min((n + 255) / 256, 1024), V), dim3(256), 0, s, src, a.gray);

@@ -2,7 +2,8 @@
 // (evalSiftDescriptor, mainPanoCompletion2view.py:353-381: cv2.xfeatures2d.SIFT_create().compute(gray, [cv2.KeyPoint(x, y, 5)]) on the
 // correspondences and on a step-5 grid of the target, then the rank of the true match among the grid descriptors, :373-379).  The contract
 // -- the project's own, written from Lowe (IJCV 60(2), 2004) with that call's parameters -- is DESIGN.md 4.10; tests/siftdesc_model.py
-// implements it in numpy.  Compiled with -ffp-contract=off: the base blur rounds exactly like the float32 model (sift_model.blur).
+// implements it in numpy.  Compiled with -ffp-contract=off: the base blur rounds exactly like the float32 model (sift_model.blur).  The
+// source image, its gray value and the border rule are sift_common.h's, shared with sift.hip.
 //
 // Launches (none of them depends on the number of views):
 //   relpose_sift_describe   base image (gray + 13-tap blur, one LDS tile kernel), descriptors (one workgroup per keypoint slot)
@@ -18,6 +19,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "sift_common.h"
 
 namespace {
 
@@ -31,30 +33,9 @@ struct SdTaps {
     float t[2 * SD_R + 1];
 };
 
-struct SdImage {
-    const uint8_t* img;
-    long long vstride;   // bytes per view
-    int img_w, channels, cx, cy, w, h;
-};
-
-__device__ inline int sd_refl101(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * n - 2;
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
-
-// cv2.COLOR_BGR2GRAY on uint8: 14-bit fixed-point weights B 1868, G 9617, R 4899 (rputil.bgr2gray)
-__device__ inline int sd_gray_at(const SdImage& s, const uint8_t* im, int y, int x) {
-    const uint8_t* p = im + ((long long)(s.cy + y) * s.img_w + (s.cx + x)) * s.channels;
-    if (s.channels == 1) return p[0];
-    return ((int)p[0] * 1868 + (int)p[1] * 9617 + (int)p[2] * 4899 + (1 << 13)) >> 14;
-}
-
 // ------------------------------------------------------------------------------------------------------------------ base image
 // base = blur(gray as float32): rows first, then columns, reflect-101 border, taps summed in index order.
-__global__ __launch_bounds__(256) void siftdesc_base_kernel(SdImage s, float* __restrict__ base, SdTaps tp) {
+__global__ __launch_bounds__(256) void siftdesc_base_kernel(SiftImage s, float* __restrict__ base, SdTaps tp) {
     __shared__ float tin[SD_TH + 2 * SD_R][SD_TW + 2 * SD_R];
     __shared__ float tmid[SD_TH + 2 * SD_R][SD_TW];
     const int v = blockIdx.z, H = s.h, W = s.w;
@@ -63,7 +44,7 @@ __global__ __launch_bounds__(256) void siftdesc_base_kernel(SdImage s, float* __
     const uint8_t* im = s.img + v * s.vstride;
     for (int i = threadIdx.x; i < rows * cols; i += 256) {
         const int ly = i / cols, lx = i - ly * cols;
-        tin[ly][lx] = (float)sd_gray_at(s, im, sd_refl101(y0 + ly - SD_R, H), sd_refl101(x0 + lx - SD_R, W));
+        tin[ly][lx] = (float)sift_gray_at(s, im, sift_refl101(y0 + ly - SD_R, H), sift_refl101(x0 + lx - SD_R, W));
     }
     __syncthreads();
     for (int i = threadIdx.x; i < rows * SD_TW; i += 256) {
@@ -361,7 +342,7 @@ int relpose_sift_describe(const RelposeSiftDescArgs* args_in) {
     std::call_once(g_sd_taps_once, sd_init_taps);
     hipStream_t s = (hipStream_t)a.stream;
     const int V = a.n_views, h = a.crop_h, w = a.crop_w;
-    SdImage src{a.images, (long long)a.img_h * a.img_w * a.channels, a.img_w, a.channels, a.crop_x, a.crop_y, w, h};
+    SiftImage src{a.images, (long long)a.img_h * a.img_w * a.channels, a.img_w, a.channels, a.crop_x, a.crop_y, w, h};
     hipLaunchKernelGGL(siftdesc_base_kernel, dim3((w + SD_TW - 1) / SD_TW, (h + SD_TH - 1) / SD_TH, V), dim3(256), 0, s, src, base, g_sd_taps);
     RP_CHECK_LAUNCH();
     if (a.n_kp > 0) {

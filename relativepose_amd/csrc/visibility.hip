@@ -1,5 +1,5 @@
 // Visibility consistency of relative poses for a batch of directed (query cloud, reference view, pose) triples: every moved query point is
-// projected into the reference view's depth panorama with relpose_frames_to_pano's rule and compared with the depths the view measured
+// projected into the reference view's depth panorama with relpose_frames_to_pano's rule (skybox.h) and compared with the depths the view measured
 // around that pixel.  In front of them = the point stands in space the view saw through (violation); behind them = hidden (occluded); on
 // them = consistent.  The contract is DESIGN.md §4.15 and the comment above relpose_visibility in include/relpose.h;
 // tests/visibility_model.py restates it in numpy.  Built with -ffp-contract=off: every f64 operation is rounded on its own.
@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "skybox.h"
 
 namespace {
 
@@ -83,16 +84,6 @@ __global__ __launch_bounds__(kTile) void vis_window_kernel(VisBufs b) {
     b.win[gid] = o;
 }
 
-// Rs[k]^T v (util.py:757-761): entries 0 / +-1, an exact signed permutation (panorama.hip's)
-__device__ __forceinline__ void vis_face_rot_t(int k, double x, double y, double z, double& ox, double& oy, double& oz) {
-    switch (k & 3) {
-        case 0: ox = x; oy = y; oz = z; break;
-        case 1: ox = z; oy = y; oz = -x; break;
-        case 2: ox = -x; oy = y; oz = -z; break;
-        default: ox = -z; oy = y; oz = x; break;
-    }
-}
-
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
@@ -124,27 +115,12 @@ __global__ __launch_bounds__(kTile) void vis_classify_kernel(VisBufs b) {
             const double q1 = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
             const double q2 = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
             c = 1;
-            int pix = -1;
-            double d = 0.0;
-            if (isfinite(q0) && isfinite(q1) && isfinite(q2)) {
-                // the first slot whose test passes.  |x| >= az implies |x / az| >= 1 after rounding too, so the divisions are only made
-                // where the test can still pass (panorama.hip's pano_point).
-#pragma unroll 1
-                for (int slot = 0; slot < 4 && pix < 0; ++slot) {
-                    double x, y, zz;
-                    vis_face_rot_t(b.dataset == RELPOSE_SUNCG ? slot : slot + 3, q0, q1, q2, x, y, zz);
-                    const double az = fabs(zz) + 1e-32;
-                    if (zz < 0 && fabs(x) < az && fabs(y) < az) {
-                        const double xn = x / az, yn = y / az;
-                        if (fabs(xn) < 1 && fabs(yn) < 1) {
-                            double cx = rint((xn + 1) * 0.5 * h), cy = rint((1 - yn) * 0.5 * h);      // round half to even
-                            cx = cx < 0 ? 0 : (cx > h - 1 ? h - 1 : cx);
-                            cy = cy < 0 ? 0 : (cy > h - 1 ? h - 1 : cy);
-                            pix = (int)cy * 4 * h + slot * h + (int)cx;
-                            d = -zz;
-                        }
-                    }
-                }
+            int pix = -1, slot, cx, cy;
+            double d = 0.0, zz;
+            // relpose_frames_to_pano's projection (skybox.h): the first slot whose face takes the point
+            if (isfinite(q0) && isfinite(q1) && isfinite(q2) && rp_skybox_project(b.dataset, h, q0, q1, q2, slot, cx, cy, zz)) {
+                pix = cy * 4 * h + slot * h + cx;
+                d = -zz;
             }
             if (pix >= 0 && d < kMaxDepth) {
                 const float2 wn = b.win[(size_t)rv * h * 4 * h + pix];

@@ -71,3 +71,39 @@ def pose_error(T_hat, T):
     """(rotation error in degrees, translation error in m)."""
     c = (np.trace(T_hat[:3, :3] @ T[:3, :3].T) - 1) / 2
     return float(np.degrees(np.arccos(np.clip(c, -1, 1)))), float(np.linalg.norm(T_hat[:3, 3] - T[:3, 3]))
+
+
+VOXEL_EDGE_POINTS = 2600
+
+
+def voxel_edge_clouds(voxel, seed=5):
+    """The situations where a voxel downsample's scan, compaction and sort can go wrong, as six clouds of VOXEL_EDGE_POINTS slots whose
+    invalid slots lie BETWEEN the valid ones -> (names, pc [6, P, 3], valid [6, P] u8, colour [6, P, 3]).  Invalid slots hold a far-away
+    point, so one that leaked into the bounds or the sums would show.
+      empty     no valid point
+      few       40 valid points (less than a wave)
+      sparse    2500 valid points (two full compaction / sort rounds of 1024 and a partial one) in a cube of 20 voxels: about 2000
+                voxels, 21^3 keys = 14 bits (the last digit of the sort is a partial one)
+      dense     2300 valid points in 5 x 3 x 3 voxels: long runs of one key, 6 x 4 x 4 keys = 7 bits
+      one_cell  1500 valid points inside 4 % of a voxel: one key, bits = 0, no sort pass
+      sparse2   another sampling of `sparse` (the partner of one_cell)"""
+    rs = np.random.RandomState(seed)
+    P = VOXEL_EDGE_POINTS
+    spec = [("empty", 0, None), ("few", 40, np.r_[6.0, 4.0, 3.0]), ("sparse", 2500, np.r_[20.0, 20.0, 20.0]),
+            ("dense", 2300, np.r_[4.9, 2.9, 2.9]), ("one_cell", 1500, np.r_[0.04, 0.04, 0.04]), ("sparse2", 2500, np.r_[20.0, 20.0, 20.0])]
+    pc = np.full((len(spec), P, 3), -1.0e3)
+    col = rs.uniform(0, 1, (len(spec), P, 3))
+    valid = np.zeros((len(spec), P), np.uint8)
+    for i, (_, n, ext) in enumerate(spec):
+        if n:
+            slots = np.sort(rs.choice(P, n, replace=False))
+            valid[i, slots] = 1
+            pc[i, slots] = np.r_[0.3, -0.2, 1.0] + rs.uniform(0, 1, (n, 3)) * ext * voxel
+    return [s[0] for s in spec], pc, valid, col
+
+
+def key_bits(pts, voxel):
+    """Bits of the largest key of §4.6 stage 1's lattice over pts (0: one cell)."""
+    mb = pts.min(0) - 0.5 * voxel
+    dims = np.floor((pts - mb) / voxel).astype(np.int64).max(0) + 1
+    return int(int(dims.prod()) - 1).bit_length()

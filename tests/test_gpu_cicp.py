@@ -213,6 +213,37 @@ def test_overflow_at_one_level_returns_true_counts():
     assert _lib.lib().relpose_cicp(C.byref(a)) == _lib.CICP_OVERFLOW
 
 
+def test_voxel_edge_cases_match_the_model_bitwise():
+    """The shared scan, compaction and sort (csrc/cloud_prims.h) where they can go wrong, at the three voxel sizes:
+    fgr_scenes.voxel_edge_clouds, with max_points below the voxel count of the sparse clouds (the first max_points voxels in key order are
+    kept, the count is the true one)."""
+    import torch
+    import fgr_scenes
+    from relativepose_amd import baselines
+    cap = 1024
+    names, pc, valid, col = fgr_scenes.voxel_edge_clouds(M.RADII[0])
+    dev = _dev()
+    pose, status, out = baselines.colored_icp_dev(torch.from_numpy(pc).to(dev), torch.from_numpy(col).to(dev), torch.from_numpy(valid).to(dev),
+                                                  max_points=cap, stages=True)
+    out = _np(out)
+    bits, over = {}, {}
+    for c, name in enumerate(names):
+        m = valid[c] != 0
+        for l, vox in enumerate(M.RADII):
+            dp, dc = M.voxel_down(pc[c][m], col[c][m], vox)
+            n = len(dp)
+            bits[name, l], over[name, l] = (fgr_scenes.key_bits(pc[c][m], vox) if m.any() else -1), n > cap
+            log("cicp_voxel_edge", cloud=name, level=l, valid=int(m.sum()), bits=bits[name, l], voxels=n)
+            assert out["down_count"][c, l] == n, (name, l)
+            assert np.array_equal(out["down_points"][c, l, :min(n, cap)].view(np.uint64), dp[:cap].view(np.uint64)), (name, l)
+            assert np.array_equal(out["down_colors"][c, l, :min(n, cap)].view(np.uint64), dc[:cap].view(np.uint64)), (name, l)
+    # the cases reach what they are meant to
+    assert all(bits["empty", l] == -1 and bits["one_cell", l] == 0 and over["sparse", l] for l in range(3))
+    assert bits["sparse", 0] % 4 and bits["sparse", 1] % 4 and bits["sparse", 2] % 4 == 0 and bits["dense", 0] % 4 and not over["dense", 1]
+    assert status.cpu().numpy().tolist() == [M.STATUS_FEW_POINTS, M.STATUS_OVERFLOW, M.STATUS_OVERFLOW]
+    assert np.array_equal(pose.cpu().numpy(), np.tile(np.eye(4), (3, 1, 1)))
+
+
 def test_too_few_points_gives_the_identity():
     import torch
     from relativepose_amd import baselines

@@ -133,6 +133,31 @@ def test_overflow_returns_true_counts():
     assert _lib.lib().relpose_fgr(C.byref(a)) == _lib.FGR_OVERFLOW
 
 
+def test_voxel_edge_cases_match_the_model_bitwise():
+    """The shared scan, compaction and sort (csrc/cloud_prims.h) where they can go wrong: fgr_scenes.voxel_edge_clouds, with max_points
+    below the voxel count of the sparse clouds (the first max_points voxels in key order are kept, the count is the true one)."""
+    import torch
+    from relativepose_amd import baselines
+    cap = 1024
+    names, pc, valid, _ = S.voxel_edge_clouds(M.VOXEL)
+    pose, status, st = baselines.fast_global_registration_dev(torch.from_numpy(pc).to(_dev()), torch.from_numpy(valid).to(_dev()),
+                                                              max_points=cap, stages=True)
+    st = {k: v.cpu().numpy() for k, v in st.items()}
+    bits, over = {}, {}
+    for c, name in enumerate(names):
+        pts = pc[c][valid[c] != 0]
+        down, _, _ = M.voxel_down(pts)
+        n = len(down)
+        bits[name], over[name] = (S.key_bits(pts, M.VOXEL) if len(pts) else -1), n > cap
+        log("fgr_voxel_edge", cloud=name, valid=len(pts), bits=bits[name], voxels=n)
+        assert st["down_count"][c] == n, name
+        assert np.array_equal(st["down_points"][c, :min(n, cap)].view(np.uint64), down[:cap].view(np.uint64)), name
+    # the cases reach what they are meant to
+    assert bits["empty"] == -1 and bits["one_cell"] == 0 and bits["sparse"] % 4 and bits["dense"] % 4 and over["sparse"] and not over["dense"]
+    assert status.cpu().numpy().tolist() == [M.STATUS_FEW_POINTS, M.STATUS_OVERFLOW, M.STATUS_OVERFLOW]
+    assert np.array_equal(pose.cpu().numpy(), np.tile(np.eye(4), (3, 1, 1)))
+
+
 @pytest.mark.parametrize("seed", SEEDS)
 def test_planted_motion_on_the_gpu(seed):
     from relativepose_amd import baselines

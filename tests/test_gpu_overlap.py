@@ -136,6 +136,27 @@ def test_clouds_with_no_valid_point_and_with_one():
     assert (want["hits"][2:] == 0).all() and np.isposinf(want["nn_min"][2:]).all()
 
 
+def test_grid_edge_cases_match_the_brute_model_bitwise():
+    """The shared scan and sort (csrc/cloud_prims.h) where they can go wrong, on clouds whose invalid slots lie between the valid ones
+    (fgr_scenes.voxel_edge_clouds at the grid's edge length): no valid point, 40 of them, 2500 (two full rounds of 1024 and a partial one)
+    over 13 bits of keys, 2300 over 6 bits, 1500 in one cell (no sort pass: the header's buffer index stays 0)."""
+    import fgr_scenes
+    edge = MD * OM.EDGE_MARGIN
+    names, pc, valid, _ = fgr_scenes.voxel_edge_clouds(edge)
+    k = {n: i for i, n in enumerate(names)}
+
+    def bits(name):
+        p = pc[k[name]][valid[k[name]] != 0]
+        return int(int((np.floor((p.max(0) - p.min(0)) / edge) + 1).prod()) - 1).bit_length()
+
+    assert bits("sparse") == 13 and bits("dense") == 6 and bits("one_cell") == 0 and valid[k["empty"]].sum() == 0
+    assert valid[k["few"]].sum() == 40 and valid[k["sparse"]].sum() == 2500
+    q = [("sparse", "sparse2"), ("sparse2", "sparse"), ("dense", "sparse"), ("sparse", "dense"), ("few", "sparse"), ("sparse", "few"),
+         ("one_cell", "dense"), ("dense", "one_cell"), ("empty", "sparse"), ("sparse", "empty")]
+    want = check("grid_edge", pc, valid, [k[a] for a, _ in q], [k[b] for _, b in q], [EYE] * len(q))
+    assert want["hits"][0] > 0 and want["hits"][2] > 0 and want["hits"][6] == 1500 and (want["hits"][8:] == 0).all()
+
+
 def test_a_cloud_against_itself_under_the_identity():
     rs = np.random.RandomState(5)
     P = 1500

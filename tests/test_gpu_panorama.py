@@ -91,6 +91,16 @@ def _holes():
     return dict(depth=dep, rgb=_u8((1, 2, 20, 20, 3), 52), scale=(1.0, 1.0), pose=None, dataset="suncg", h=16, box=None)
 
 
+def _ties():
+    """64x64 frames of depth 2 at scale 1 into h = 160: every product and quotient of the projection is exact, column c lands on 2.5 c and
+    row r on 2.5 r -- a .5 tie at every odd one (round half to even) -- and row 0 / column 0 lie exactly on a face edge, |x| = |z|.  The second
+    frame is turned by exactly 90 degrees: the same ties and edges through another slot."""
+    dep = np.full((1, 2, 64, 64), 2.0, np.float32)
+    quarter = np.array([[0.0, 0, 1, 0], [0, 1, 0, 0], [-1, 0, 0, 0], [0, 0, 0, 1]])
+    return dict(depth=dep, rgb=_u8((1, 2, 64, 64, 3), 53), scale=(1.0, 1.0), pose=np.stack([np.eye(4), quarter])[None], dataset="scannet", h=160,
+                box=None)
+
+
 def _odd_aligned_off1():
     """odd_aligned with the rgb buffer one byte past a dword boundary: rows of 216 bytes, yet no row starts on a dword boundary, so
     every tile takes the byte path."""
@@ -98,7 +108,7 @@ def _odd_aligned_off1():
 
 
 CASES = {"scannet4": _scannet4, "odd": _odd, "odd_aligned": _odd_aligned, "odd_aligned_off1": _odd_aligned_off1, "ring_scannet": lambda: _ring("scannet"), "ring_suncg": lambda: _ring("suncg"),
-         "overflow": _overflow, "contention": _contention, "empty": _empty, "holes": _holes}
+         "overflow": _overflow, "contention": _contention, "empty": _empty, "holes": _holes, "ties": _ties}
 
 
 def _abi(c, gate=0.05, expect=0, **over):
@@ -178,6 +188,10 @@ def test_the_cases_reach_what_they_are_meant_to():
     m = _case("contention")[1]
     assert m["valid"].sum() == 1 and 30000 < m["count"].max() < 76800 and m["sum_rgb"].max() > 2 ** 22
     assert _case("empty")[1]["valid"].sum() == 0 and _case("holes")[1]["valid"].sum() == 0
+    m = _case("ties")[1]                                                    # per frame 63 x 63 points, one per pixel; the edge row and column dropped
+    assert m["count"].max() == 1 and m["count"].sum() == 2 * 63 * 63
+    cols = np.flatnonzero(m["valid"][0, 5])                                 # row 5 = frame row 2; 2.5 -> 2, 7.5 -> 8, 12.5 -> 12, 17.5 -> 18
+    assert len(cols) == 2 * 63 and all(np.array_equal((c - c[0] + 2)[:8], [2, 5, 8, 10, 12, 15, 18, 20]) for c in (cols[:63], cols[63:]))
     assert _case("odd_aligned")[1]["valid"][0, :, 40:].sum() == 0 and _case("odd_aligned")[1]["valid"][0, 2:14, :40].sum() > 100
 
 
