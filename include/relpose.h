@@ -964,6 +964,103 @@ typedef struct RelposeVisibilityArgs {
 size_t relpose_visibility_workspace_bytes(int32_t n_views, int32_t h, int32_t n_queries);
 int relpose_visibility(const RelposeVisibilityArgs* args);
 
+/* -------------------------------------------------------------------- TSDF fusion of posed depth panoramas
+ * What a user does with poses is merge the scans.  relpose_tsdf_fuse integrates the views of n_scenes scenes into n_scenes volumes of
+ * nx * ny * nz voxels (a truncated signed distance function in the style of Curless-Levoy / KinectFusion: positive in the space a sensor
+ * saw through, negative behind the surface it measured), relpose_tsdf_surface extracts the zero crossings as an oriented, coloured point
+ * cloud in relpose_overlap's layout.  The contract is the project's own (tests/tsdf_model.py restates it in numpy).  Every
+ * accumulated value is an integer: the volume does not depend on the order of the views, nor on whether they come in one call or several.
+ * The geometry is float64, every operation rounded on its own.  No atomics.  Invalid arguments return RELPOSE_EINVAL before anything is
+ * enqueued or any output is touched.
+ *
+ *   depth            [n_views, h, 4h] f32 panoramas; a value is data iff z > 0 && z <= FLT_MAX (relpose_visibility's rule)
+ *   rgb              [n_views, 3, h, 4h] f32 or NULL
+ *   pose             [n_views, 4, 4] f64 row-major on the DEVICE, world -> camera (the loaders' R)
+ *   view_begin_host  [n_scenes + 1] i32 in HOST memory, ascending from 0 to n_views: scene s owns the views view_begin[s] .. view_begin[s+1]-1
+ *                    (a scene may have none; at most 4096 per scene per call)
+ *   origin_host      [n_scenes, 3] f64 in HOST memory, finite: the corner of voxel (0, 0, 0);  voxel, trunc: finite, > 0, shared
+ *   tsdf_sum, weight [n_scenes, nz, ny, nx] i32, x fastest;  color_sum [n_scenes, 3, nz, ny, nx] u32, required with rgb and NULL without
+ *   accumulate       0: the sums of this call are stored (no clear is needed); 1: they are added to what is there
+ *   rule             for voxel (i, j, k) and each view v of its scene: c_a = origin_a + ((double)idx_a + 0.5) * voxel;
+ *                    q_a = ((T_a0 cx + T_a1 cy) + T_a2 cz) + T_a3; relpose_visibility's projection of q gives the pixel and d = -Z; the view
+ *                    is skipped if q is not finite, no face takes it, or d >= 32768; D = (double)depth[v, pixel], skipped if no data;
+ *                    sdf = D - d, skipped if sdf < -trunc; t = fmin(sdf / trunc, 1.0); tsdf_sum += llrint(t * 32768.0); weight += 1; with rgb,
+ *                    per channel, color_sum += (uint32)rintf(fminf(fmaxf(c, 0.f), 1.f) * 255.f) of the same pixel (a NaN colour counts 0).
+ *                    The lookup is nearest-pixel.
+ *   limits           h even, 2..8192; n_views * h * 4h < 2^31; 1 <= n_scenes; n_scenes * nx * ny * nz < 2^31; dataset as relpose_visibility.
+ *                    Across accumulating calls the CALLER keeps every voxel's weight <= 65535: |tsdf_sum| <= 65535 * 32768 and
+ *                    color_sum <= 65535 * 255 then stay below 2^31.
+ *   workspace        relpose_tsdf_fuse_workspace_bytes(n_scenes, n_views, h, nx, ny, nz) bytes (0 for sizes outside the limits), 256-byte
+ *                    aligned: the device copies of view_begin and origin
+ * The call waits for `stream` once, at its end: the host arrays are the caller's again when it returns. */
+typedef struct RelposeTsdfFuseArgs {
+    uint32_t struct_size;       /* sizeof(RelposeTsdfFuseArgs) as the caller compiled it */
+    int32_t n_scenes;
+    int32_t n_views;
+    int32_t h;
+    int32_t dataset;
+    int32_t nx, ny, nz;
+    int32_t accumulate;
+    int32_t reserved0;
+    const float* depth;
+    const float* rgb;
+    const double* pose;
+    const int32_t* view_begin_host;
+    const double* origin_host;
+    double voxel;
+    double trunc;
+    int32_t* tsdf_sum;
+    int32_t* weight;
+    uint32_t* color_sum;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeTsdfFuseArgs;
+size_t relpose_tsdf_fuse_workspace_bytes(int32_t n_scenes, int32_t n_views, int32_t h, int32_t nx, int32_t ny, int32_t nz);
+int relpose_tsdf_fuse(const RelposeTsdfFuseArgs* args);
+
+/* The surface of relpose_tsdf_fuse's state, per scene.  A voxel is known iff weight >= min_weight (>= 1); its value is
+ * t = (double)tsdf_sum / (32768.0 * (double)weight).  For every known voxel a, in ascending linear index, and each positive-axis neighbour
+ * b = a + e_axis (x, then y, then z) inside the volume that is known: if (ta >= 0 && tb < 0) || (ta < 0 && tb >= 0) one point is emitted at
+ * s = ta / (ta - tb) along the edge: its coordinate on that axis is origin + (((double)idx + 0.5) + s) * voxel, the other two are the
+ * centre's, origin + ((double)idx + 0.5) * voxel.
+ *   normal           g(a) + s * (g(b) - g(a)) per component, divided by sqrt((gx gx + gy gy) + gz gz); a zero vector stays zero.  Component
+ *                    c of g(v) is (t(v + e_c) - t(v - e_c)) * 0.5 when both neighbours are known (inside the volume and weight >=
+ *                    min_weight), t(v + e_c) - t(v) or t(v) - t(v - e_c) when one is, 0 when neither is.  t grows towards the space the
+ *                    sensors saw through: the normal points there, in the world frame.
+ *   colour           with color_sum and colors: (float)(ca + s * (cb - ca)) per channel, c = (double)color_sum / (255.0 * (double)weight)
+ *   points, normals  [n_scenes, cap, 3] f64;  colors [n_scenes, cap, 3] f32 or NULL (needs color_sum);  valid [n_scenes, cap] u8:
+ *                    relpose_overlap's pc / valid.  n_points [n_scenes] i32: the number of crossings, which may exceed cap; only the
+ *                    first cap are written; valid is 1 for rows < min(n, cap) and 0 beyond; the other rows beyond are not touched.
+ *   limits           1 <= n_scenes; n_scenes * nx * ny * nz < 2^31; 3 * nx * ny * nz < 2^31; 1 <= cap; n_scenes * cap < 2^29;
+ *                    min_weight >= 1; voxel finite > 0; origin finite
+ *   workspace        relpose_tsdf_surface_workspace_bytes(n_scenes, nx, ny, nz) bytes (0 for sizes outside the limits), 256-byte aligned: the
+ *                    crossings per workgroup, their scan, and the device copy of origin
+ * Three launches: count per workgroup, scan per scene, write.  The call waits for `stream` once, at its end. */
+typedef struct RelposeTsdfSurfaceArgs {
+    uint32_t struct_size;       /* sizeof(RelposeTsdfSurfaceArgs) as the caller compiled it */
+    int32_t n_scenes;
+    int32_t nx, ny, nz;
+    int32_t min_weight;
+    int32_t cap;
+    int32_t reserved0;
+    const int32_t* tsdf_sum;
+    const int32_t* weight;
+    const uint32_t* color_sum;
+    const double* origin_host;
+    double voxel;
+    double* points;
+    double* normals;
+    float* colors;
+    uint8_t* valid;
+    int32_t* n_points;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeTsdfSurfaceArgs;
+size_t relpose_tsdf_surface_workspace_bytes(int32_t n_scenes, int32_t nx, int32_t ny, int32_t nz);
+int relpose_tsdf_surface(const RelposeTsdfSurfaceArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

@@ -196,6 +196,27 @@ class VisibilityArgs(C.Structure):
                 ("stream", c_void_p)]
 
 
+class TsdfFuseArgs(C.Structure):
+    """RelposeTsdfFuseArgs (include/relpose.h): the argument block of relpose_tsdf_fuse."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("n_views", c_int), ("h", c_int), ("dataset", c_int), ("nx", c_int),
+                ("ny", c_int), ("nz", c_int), ("accumulate", c_int), ("reserved0", c_int), ("depth", c_void_p), ("rgb", c_void_p),
+                ("pose", c_void_p), ("view_begin_host", c_void_p), ("origin_host", c_void_p), ("voxel", c_double), ("trunc", c_double),
+                ("tsdf_sum", c_void_p), ("weight", c_void_p), ("color_sum", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("stream", c_void_p)]
+
+
+class TsdfSurfaceArgs(C.Structure):
+    """RelposeTsdfSurfaceArgs (include/relpose.h): the argument block of relpose_tsdf_surface."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("nx", c_int), ("ny", c_int), ("nz", c_int), ("min_weight", c_int),
+                ("cap", c_int), ("reserved0", c_int), ("tsdf_sum", c_void_p), ("weight", c_void_p), ("color_sum", c_void_p),
+                ("origin_host", c_void_p), ("voxel", c_double), ("points", c_void_p), ("normals", c_void_p), ("colors", c_void_p),
+                ("valid", c_void_p), ("n_points", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
+TSDF_MAX_VIEWS = 4096               # per scene per relpose_tsdf_fuse call
+TSDF_MAX_WEIGHT = 65535             # the caller's bound on a voxel's weight across accumulating calls
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/relpose.h
 SIGNATURES = {
     "relpose_default_params": (None, [C.POINTER(Params)]),
@@ -252,6 +273,10 @@ SIGNATURES = {
     "relpose_overlap": (c_int, [C.POINTER(OverlapArgs)]),
     "relpose_visibility_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "relpose_visibility": (c_int, [C.POINTER(VisibilityArgs)]),
+    "relpose_tsdf_fuse_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "relpose_tsdf_fuse": (c_int, [C.POINTER(TsdfFuseArgs)]),
+    "relpose_tsdf_surface_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "relpose_tsdf_surface": (c_int, [C.POINTER(TsdfSurfaceArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

@@ -26,6 +26,7 @@ SOURCES = [
     ("panorama.hip", ["-ffp-contract=off"]),      # frames to panorama: the f64 geometry and the f32 gate must agree with tests/panorama_model.py bit for bit
     ("overlap.hip", ["-ffp-contract=off"]),        # overlap statistics: hits and the closest-pair distance must agree with tests/overlap_model.py bit for bit
     ("visibility.hip", ["-ffp-contract=off"]),     # visibility consistency: classes and margins must agree with tests/visibility_model.py bit for bit
+    ("tsdf.hip", ["-ffp-contract=off"]),           # TSDF fusion: the integer volume and the surface must agree with tests/tsdf_model.py bit for bit
     ("scnet.hip", []),
 ]
 

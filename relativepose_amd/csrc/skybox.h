@@ -1,4 +1,4 @@
-// The four-face skybox panorama shared by geometry.hip, panorama.hip and visibility.hip: the face rotations and reproj_helper's rule for
+// The four-face skybox panorama shared by geometry.hip, panorama.hip, visibility.hip and tsdf.hip: the face rotations and reproj_helper's rule for
 // the panorama pixel of a point.  Device-only and force-inlined; the including files are built with -ffp-contract=off.
 #pragma once
 #include "common.h"

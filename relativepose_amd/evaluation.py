@@ -19,6 +19,9 @@ unchanged" is realised by the build's own eval_pairs-style harness).
   select_pose / verify_summary / spearman / observed_depth, evaluate_pairs(verify=...)
                           no counterpart: the visibility check of an estimated pose against the partner's depth panorama
                           (util.pose_visibility_dev)
+  fuse_views / reconstruction_scores / fuse_summary / wall_error, evaluate_pairs(fuse=...)
+                          no counterpart: the posed views merged into a TSDF volume and its surface cloud, and what a pose error does to
+                          it (util.tsdf_fuse_dev / tsdf_surface_dev)
 
 The metrics are host numpy like the reference's (a handful of 3x3 products per pair); overlap and pc_nearest of a batch come from one
 grid-based GPU call (util.point_cloud_overlap_dev), bitwise the values of the per-pair brute-force yardstick
@@ -194,7 +197,7 @@ def _verify_fields(pipe, st, verify, kept, trace, pcs, valid):
              'R_pred_44_selected': levels[b, pick[b]].copy()} for b in range(levels.shape[0])]
 
 
-def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals="given", verify=None):
+def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals="given", verify=None, fuse=None):
     """The reference's evaluation loop (evaluation.py:203-320) over an iterable of batches
     ``{"rgb","norm","depth","R" [B,2,4,4], "pts" [B,2,N,2], "ptw" [B,2,N]}`` (the DataLoader dict layout, batched, with the
     injected keypoints; with RelativePosePipeline(keypoints="reference") a batch carries "sift" detections instead, _prepare_batch):
@@ -204,10 +207,14 @@ def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals=
     verify="observed" / "completed": every record gains the visibility check of its pose: the observed clouds of both views
     against the partner's reference panorama (_verify_depth) -- vis_agreement, vis_violation_rate, vis_observed, vis_counts [6] (both
     directions added) for the final pose, vis_level = the level select_pose picks among the per-level poses, R_pred_44_selected = that
-    level's pose.  verify=None: the records are what they were."""
+    level's pose.  verify=None: the records are what they were.
+    fuse=voxel: every record gains what its pose does to the reconstruction (_fuse_fields): fuse_accuracy, fuse_completeness
+    (the pair's observed views fused under the estimate against the same fusion under R_gt) and fuse_points.  fuse=None: nothing changes."""
     from . import util
     if verify is not None and verify not in VERIFY_MODES:
         raise ValueError(f"verify must be None or one of {VERIFY_MODES}")
+    if fuse is not None and not (np.isfinite(fuse) and fuse > 0):
+        raise ValueError("fuse must be None or a voxel size > 0")
     stats = []
     k = 0
     for batch in batches:
@@ -220,6 +227,7 @@ def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals=
         R_gts = [np.matmul(batch["R"][b, 1], np.linalg.inv(batch["R"][b, 0])) for b in range(B)]
         ovs, nns = _pair_overlap_stats(pcs, valid, R_gts)
         vis = _verify_fields(pipe, st, verify, kept, trace, pcs, valid) if verify is not None else None
+        fus = _fuse_fields(_verify_depth(pipe, st, "observed", None), pose, R_gts, pipe.dataset, fuse) if fuse is not None else None
         pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
         for b in range(B):
             R_gt_44 = R_gts[b]
@@ -230,6 +238,8 @@ def evaluate_pairs(pipe, batches, device, result_path=None, names=None, normals=
             stats.append(result_record(nm[0], nm[1], pose[b], R_gt_44, pc_src, ov, pc_dist, cam_dist, pc_nn))
             if vis is not None:
                 stats[-1].update(vis[b])
+            if fus is not None:
+                stats[-1].update(fus[b])
             k += 1
     if result_path is not None:
         save_results(result_path, stats)
@@ -270,6 +280,89 @@ def verify_summary(stats):
             out["vis_selected"][ov] = {"nobs": len(rows), "err_ad_last": float(np.mean([e['err_ad'] for e in rows])),
                                        "err_ad_selected": float(np.mean(sel))}
     return out
+
+
+def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, max_points=None, view_begin=None):
+    """Merge posed depth panoramas into one surface cloud per scene: depth [V,h,4h] f32 and rgb [V,3,h,4h] f32 (or None)
+    CUDA tensors, R [V,4,4] host float64 world -> camera poses (the loaders' R), view_begin as util.tsdf_fuse_dev's (None: one scene).  The box
+    is util.tsdf_bounds_dev's, the volume util.tsdf_fuse_dev's, the cloud util.tsdf_surface_dev's.
+    -> {"points" [S,cap,3] f64, "normals", "colors" (or None), "valid" [S,cap] u8, "n_points" [S] i32, "origin", "dims", "voxel", "state"}."""
+    from . import util
+    vb = np.array([0, int(depth.shape[0])], np.int32) if view_begin is None else view_begin
+    origin, dims = util.tsdf_bounds_dev(depth, R, dataset, voxel, pad, vb)
+    state = util.tsdf_fuse_dev(depth, rgb, R, vb, origin, dims, voxel, dataset, trunc)
+    points, normals, colors, valid, n = util.tsdf_surface_dev(state, min_weight, max_points)
+    return {"points": points, "normals": normals, "colors": colors, "valid": valid, "n_points": n, "origin": origin, "dims": dims,
+            "voxel": float(voxel), "state": state}
+
+
+def reconstruction_scores(est, ref, max_dist=0.08):
+    """Accuracy and completeness of fused surfaces against reference surfaces, scene by scene: est, ref = fuse_views' dicts (or any dicts
+    with "points" [S,cap,3] f64 and "valid" [S,cap] u8 CUDA tensors) with the same S.  accuracy = the share of est's points with a point of
+    ref within max_dist, completeness = the share of ref's points with a point of est within max_dist.  ONE util.overlap_dev call with 2 S
+    directed queries under the identity pose.  -> (accuracy [S], completeness [S]) float64 numpy; NaN where the cloud divided by is empty."""
+    import torch
+    from . import util
+    pe, ve, pr, vr = est["points"], est["valid"], ref["points"], ref["valid"]
+    S = int(pe.shape[0])
+    if int(pr.shape[0]) != S:
+        raise ValueError("reconstruction_scores takes as many reference scenes as estimated ones")
+    P = max(int(pe.shape[1]), int(pr.shape[1]))
+    dev = pe.device
+    pc = torch.zeros(2 * S, P, 3, dtype=torch.float64, device=dev)
+    valid = torch.zeros(2 * S, P, dtype=torch.uint8, device=dev)
+    pc[:S, :pe.shape[1]], valid[:S, :pe.shape[1]] = pe, ve
+    pc[S:, :pr.shape[1]], valid[S:, :pr.shape[1]] = pr, vr
+    q = np.arange(2 * S)
+    eye = torch.eye(4, dtype=torch.float64, device=dev).repeat(2 * S, 1, 1)
+    hits, _, n_valid = util.overlap_dev(pc, valid, q, (q + S) % (2 * S), eye, max_dist)
+    hits, n = hits.cpu().numpy().astype(np.float64), n_valid.cpu().numpy().astype(np.float64)
+    with np.errstate(all="ignore"):
+        share = np.where(n > 0, hits / np.where(n > 0, n, 1.0), np.nan)
+    return share[:S], share[S:]
+
+
+def _fuse_fields(depth_obs, poses, R_gts, dataset, voxel, max_dist=0.08):
+    """Per pair the record fields of evaluate_pairs(fuse=voxel): the pair's two observed views depth_obs [2B,h,4h] (view 2b = the source)
+    fused in the target's frame -- target pose I, source pose inv(R) -- once under the estimate poses[b] and once under R_gts[b]; the
+    estimate's surface is scored against the ground truth's (reconstruction_scores).  2 B scenes of 2 views in one fuse call.  A pose that
+    cannot be inverted gives NaN scores."""
+    import torch
+    B = len(R_gts)
+    R = np.empty((4 * B, 4, 4))
+    bad = np.zeros(B, bool)
+    for b in range(B):
+        for k, T in enumerate((poses[b], R_gts[b])):
+            T = np.vstack([np.asarray(T, np.float64)[:3], [0.0, 0.0, 0.0, 1.0]])
+            try:
+                inv = np.linalg.inv(T)
+            except np.linalg.LinAlgError:
+                inv = np.full((4, 4), np.nan)
+            if not np.isfinite(inv).all():
+                inv, bad[b] = np.eye(4), True
+            s = k * B + b
+            R[2 * s], R[2 * s + 1] = inv, np.eye(4)
+    idx = torch.tensor([2 * (s % B) + v for s in range(2 * B) for v in range(2)], device=depth_obs.device)
+    surf = fuse_views(depth_obs[idx].contiguous(), None, R, dataset, voxel, view_begin=np.arange(0, 4 * B + 1, 2, dtype=np.int32))
+    half = lambda lo, hi: {"points": surf["points"][lo:hi], "valid": surf["valid"][lo:hi]}
+    acc, comp = reconstruction_scores(half(0, B), half(B, 2 * B), max_dist)
+    n = surf["n_points"].cpu().numpy()
+    return [{'fuse_accuracy': float("nan") if bad[b] else float(acc[b]), 'fuse_completeness': float("nan") if bad[b] else float(comp[b]),
+             'fuse_points': int(n[b])} for b in range(B)]
+
+
+def fuse_summary(stats):
+    """What the CLI reports about records that carry the fusion fields: the medians, and the Spearman rank correlation of fuse_accuracy with
+    the rotation error."""
+    acc, comp = [e['fuse_accuracy'] for e in stats], [e['fuse_completeness'] for e in stats]
+    med = lambda v: float(np.nanmedian(v)) if len(v) and not np.all(np.isnan(v)) else float("nan")
+    return {"fuse_accuracy_median": med(acc), "fuse_completeness_median": med(comp), "fuse_points_median": med([e['fuse_points'] for e in stats]),
+            "fuse_spearman_rot": spearman(acc, [e['err_ad'] for e in stats])}
+
+
+def wall_error(points, half, voxel):
+    """Distance of points [N,3] (world frame of synth.render_scene: the room is the box |x_a| <= half_a) to the nearest wall plane, in voxels."""
+    return np.abs(np.abs(np.asarray(points, np.float64)) - np.asarray(half, np.float64)[None]).min(1) / float(voxel)
 
 
 def evaluate_from_frames(pipe, batches, device, Hf=480, Wf=640):
@@ -515,31 +608,31 @@ def _default_record(pipe, sub, poses, device, names, ks):
     return out
 
 
-def evaluate_fgs(batches, device, dataset, result_path=None, max_points=None, seed=0, verify=None):
+def evaluate_fgs(batches, device, dataset, result_path=None, max_points=None, seed=0, verify=None, fuse=None):
     """The reference's `--method fgs` loop (evaluation.py:182-203, 286-320) over batches of synthetic pairs: the observed-block clouds
     of both views (util.depth2pc_dev, as _default_record builds them), ONE batched FPFH + fast global registration call per batch
     (baselines.fast_global_registration_dev), then per pair the overlap statistics; pairs with overlap < 0.1 are skipped without a
     record (evaluation.py:190-191).  Returns the record list (the reference's keys + 'status'); written to result_path if given."""
     from . import _lib, baselines
     reg = lambda pcs, valid: baselines.fast_global_registration_dev(pcs, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)[:2]
-    return _evaluate_baseline(batches, device, dataset, reg, result_path, verify=verify)
+    return _evaluate_baseline(batches, device, dataset, reg, result_path, verify=verify, fuse=fuse)
 
 
-def evaluate_gs(batches, device, dataset, result_path=None, max_points=None, seed=0, verify=None):
+def evaluate_gs(batches, device, dataset, result_path=None, max_points=None, seed=0, verify=None, fuse=None):
     """The reference's `--method gs` loop: as evaluate_fgs, with ONE batched FPFH + RANSAC call per batch
     (baselines.global_registration_dev, baselines.py:52-81)."""
     from . import _lib, baselines
     reg = lambda pcs, valid: baselines.global_registration_dev(pcs, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)[:2]
-    return _evaluate_baseline(batches, device, dataset, reg, result_path, verify=verify)
+    return _evaluate_baseline(batches, device, dataset, reg, result_path, verify=verify, fuse=fuse)
 
 
-def evaluate_cgs(batches, device, dataset, result_path=None, max_points=None, seed=0, verify=None):
+def evaluate_cgs(batches, device, dataset, result_path=None, max_points=None, seed=0, verify=None, fuse=None):
     """The reference's `--method cgs` loop: as evaluate_gs, with the RANSAC pose of every pair refined by the three coloured ICP levels
     (baselines.color_registration_dev, baselines.py:110-168).  The colours are the observed block of `rgb` in the clouds' point order,
     quantised as the reference does: clip(rgb * 255, 0, 255) to uint8 (evaluation.py:168), then / 255 (util.py:53)."""
     from . import _lib, baselines
     reg = lambda pcs, valid, colors: baselines.color_registration_dev(pcs, colors, valid, max_points=max_points or _lib.FGR_MAX_POINTS, seed=seed)[:2]
-    return _evaluate_baseline(batches, device, dataset, reg, result_path, with_colors=True, verify=verify)
+    return _evaluate_baseline(batches, device, dataset, reg, result_path, with_colors=True, verify=verify, fuse=fuse)
 
 
 def observed_colors(rgb):
@@ -550,10 +643,10 @@ def observed_colors(rgb):
     return np.ascontiguousarray(q[:, :, :, h:2 * h].transpose(0, 2, 3, 1).reshape(len(q), h * h, 3)) / 255.
 
 
-def _evaluate_baseline(batches, device, dataset, register, result_path, with_colors=False, verify=None):
+def _evaluate_baseline(batches, device, dataset, register, result_path, with_colors=False, verify=None, fuse=None):
     """register(pcs, valid) -> (pose [B,4,4], status [B]) tensors for the observed-block clouds of a batch; with_colors: register(pcs,
     valid, colors [2B,P,3] f64).  verify="observed": the records gain evaluate_pairs' visibility fields for the baseline's one pose (vis_level
-    is 0); a baseline completes nothing, so there is no "completed"."""
+    is 0); a baseline completes nothing, so there is no "completed".  fuse=voxel: evaluate_pairs' fusion fields for the baseline's pose."""
     import torch
     from . import util
     if verify not in (None, "observed"):
@@ -575,6 +668,7 @@ def _evaluate_baseline(batches, device, dataset, register, result_path, with_col
         if verify is not None:
             vcounts, _, vsc = util.pose_visibility_dev(pcs, valid, observed_depth(depth, dataset), pose[:, None], dataset)
             vcounts, vsc = vcounts.sum(2).cpu().numpy(), {k: v.cpu().numpy() for k, v in vsc.items()}
+        fus = _fuse_fields(observed_depth(depth, dataset), pose, R_gts, dataset, fuse) if fuse is not None else None
         pcs, valid = pcs.cpu().numpy(), valid.cpu().numpy().astype(bool)
         for q in range(n):
             R_gt_44 = R_gts[q]
@@ -592,6 +686,8 @@ def _evaluate_baseline(batches, device, dataset, register, result_path, with_col
                 rec.update(vis_agreement=float(vsc["agreement"][q, 0]), vis_violation_rate=float(vsc["violation_rate"][q, 0]),
                            vis_observed=float(vsc["observed"][q, 0]), vis_counts=vcounts[q, 0].copy(), vis_level=0,
                            R_pred_44_selected=rec['R_pred_44'].copy())
+            if fus is not None:
+                rec.update(fus[q])
             stats.append(rec)
     if result_path is not None:
         save_results(result_path, stats)
@@ -907,6 +1003,12 @@ def _cli_parser_completion():
                          "and the JSON line vis_spearman_rot, vis_spearman_trans (rank correlation of vis_agreement with err_ad / err_t) and "
                          "vis_selected (per bucket the mean rotation error of the level the check selects next to the last level's); "
                          "--mine-pairs --verify observed: the mined entries gain vis_agreement")
+    ap.add_argument("--fuse", type=float, default=None, metavar="VOXEL",
+                    help="TSDF fusion at this voxel size (DESIGN.md 4.16).  --method ours (one GPU, given keypoints) / fgs / gs / cgs: every "
+                         "record gains fuse_accuracy, fuse_completeness (the pair fused under its estimate against the same fusion under R_gt) "
+                         "and fuse_points, the JSON line their medians and fuse_spearman_rot (rank correlation of fuse_accuracy with err_ad).  "
+                         "--mine-pairs --fuse: each scene's views are fused under the ground-truth poses; the line gains fuse_wall_err_median / "
+                         "_p90 (voxels, against the room's walls) and fuse_points, and <exp>.scene<k>.ply is written when --exp is given")
     return ap
 
 
@@ -934,6 +1036,14 @@ def main(argv=None):
         if args.gpus > 1 or (not args.mine_pairs and args.method == "ours" and args.keypoint_mode != "given"):
             raise SystemExit("--verify runs on one GPU (--gpus 1) with given keypoints: the check is not sharded")
 
+    if args.fuse is not None:
+        if args.descriptor_eval or args.completion_eval or args.from_frames:
+            raise SystemExit("--fuse applies to the pose evaluation (--method ours / fgs / gs / cgs) and to --mine-pairs")
+        if not (np.isfinite(args.fuse) and args.fuse > 0):
+            raise SystemExit("--fuse takes a voxel size > 0")
+        if args.gpus > 1 or (not args.mine_pairs and args.method == "ours" and args.keypoint_mode != "given"):
+            raise SystemExit("--fuse runs on one GPU (--gpus 1) with given keypoints: the fusion is not sharded")
+
     if args.mine_pairs:
         if args.gpus > 1:
             raise SystemExit("--mine-pairs runs on one GPU (--gpus 1)")
@@ -943,11 +1053,23 @@ def main(argv=None):
         from . import _lib, synth
         dev = _lib.require_gpu()
         entries = []
+        wall, fuse_points, plys = [], 0, []
         t0 = time.perf_counter()
         for s in range(args.scenes):
             sc = synth.render_scene(args.seed + s, args.scene_views, args.dataset)
             entries += mine_pairs(sc["depth"], sc["R"], args.dataset, f"scene{args.seed + s}", min_overlap=args.min_overlap, device=dev,
                                   verify=args.verify)
+            if args.fuse is not None:
+                from . import util
+                up = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
+                surf = fuse_views(up(sc["depth"]), up(sc["rgb"]), sc["R"], args.dataset, args.fuse)
+                n = int(surf["n_points"][0].item())
+                pts = surf["points"][0, :n].cpu().numpy()
+                wall.append(wall_error(pts, sc["half"], args.fuse))
+                fuse_points += n
+                if args.exp is not None:
+                    plys.append(f"{args.exp}.scene{s}.ply")
+                    util.save_ply(plys[-1], pts, surf["normals"][0, :n], surf["colors"][0, :n])
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         path = None if args.exp is None else save_data_list(args.exp + ".datalist.npy", {"test": entries})
@@ -957,6 +1079,10 @@ def main(argv=None):
         if args.verify is not None:
             line["vis_agreement_mean_per_bucket"] = {k: float(np.nanmean([e['vis_agreement'] for e in entries if overlap_bucket(e['overlap']) == k] or [np.nan]))
                                                      for k in OVERLAPS}
+        if args.fuse is not None:
+            e = np.concatenate(wall) if wall else np.zeros(0)
+            line.update(fuse=args.fuse, fuse_wall_err_median=float(np.median(e)) if e.size else float("nan"),
+                        fuse_wall_err_p90=float(np.percentile(e, 90)) if e.size else float("nan"), fuse_points=fuse_points, fuse_ply=plys)
         print(json.dumps(line), flush=True)
         return
 
@@ -1062,17 +1188,20 @@ def main(argv=None):
                    for k in range(0, args.pairs, args.batch)]
         path = None if args.exp is None else args.exp + ".result.npy"
         t0 = time.perf_counter()
-        stats = {"fgs": evaluate_fgs, "gs": evaluate_gs, "cgs": evaluate_cgs}[m](batches, dev, args.dataset, result_path=path, verify=args.verify)
+        stats = {"fgs": evaluate_fgs, "gs": evaluate_gs, "cgs": evaluate_cgs}[m](batches, dev, args.dataset, result_path=path, verify=args.verify,
+                                                                                 fuse=args.fuse)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         line = {"method": m, "pairs": args.pairs, "records": len(stats), "seconds": dt, "result_file": path,
                 "dataset": args.dataset, "stats": summarize(stats)}
         if args.verify is not None:
             line.update(verify=args.verify, **verify_summary(stats))
+        if args.fuse is not None:
+            line.update(fuse=args.fuse, **fuse_summary(stats))
         print(json.dumps(line), flush=True)
         return
 
-    if args.verify is not None:                   # --method ours: the unsharded loop, which keeps every level's pose (and output) for the check
+    if args.verify is not None or args.fuse is not None:      # --method ours: the unsharded loop, which keeps every level's pose (and output) for the check
         import torch
         from types import SimpleNamespace
         from . import _lib, params, weights
@@ -1090,11 +1219,14 @@ def main(argv=None):
         path = None if args.exp is None else args.exp + ".result.npy"
         t0 = time.perf_counter()
         stats = evaluate_pairs(pipe, (_batch_take(b, np.arange(_batch_size(b))) for b in lazy), dev, result_path=path, normals=args.normals,
-                               verify=args.verify)
+                               verify=args.verify, fuse=args.fuse)
         torch.cuda.synchronize()
         line = {"pairs": len(stats), "seconds": time.perf_counter() - t0, "n_gpus": 1, "result_file": path, "dataset": ds,
                 "stats": summarize(stats), "verify": args.verify}
-        line.update(verify_summary(stats))
+        if args.verify is not None:
+            line.update(verify_summary(stats))
+        if args.fuse is not None:
+            line.update(fuse=args.fuse, **fuse_summary(stats))
         print(json.dumps(line), flush=True)
         return
 

@@ -42,6 +42,7 @@ Operator                    replaces (reference file:line)
   frames_to_pano            the depth/ and rgb/ panoramas the ScanNet loader reads next to its frames, datasets/ScanNet.py:211-230 (built from the frames)
   overlap                   the two KDTree queries of util.point_cloud_overlap, util.py:21-40 (batched over directed cloud pairs, one grid per cloud)
   visibility                no counterpart: the free-space check of a relative pose against the partner's depth panorama
+  tsdf_fuse, tsdf_surface   no counterpart: posed depth panoramas merged into a TSDF volume and its surface cloud
   affinity_topk             rpmodule.py:342-379
   match_pairs               RelativePoseEstimation_helper, rpmodule.py:317-508
 """
@@ -109,6 +110,14 @@ _lib.define("overlap(Tensor pc, Tensor? valid, Tensor query_cloud, Tensor ref_cl
 # (query cloud -> reference view's frame) -> counts i32 [Q,6], margin_sum i64 [Q], cls u8 [Q,P]
 _lib.define("visibility(Tensor pc, Tensor? valid, Tensor depth, Tensor query_cloud, Tensor ref_view, Tensor pose, int dataset, "
             "float tol_abs=0.05, float tol_rel=0.02, int radius=1) -> (Tensor, Tensor, Tensor)")
+# depth f32 [V,h,4h], rgb f32 [V,3,h,4h] (optional), pose f64 [V,4,4] world -> camera, view_begin integer [S+1] and origin f64 [S,3] (both read
+# on the host), dims = (nx, ny, nz); trunc 0 = 4 voxel -> tsdf_sum, weight i32 [S,nz,ny,nx], color_sum i32 [S,3,nz,ny,nx] (empty without rgb)
+_lib.define("tsdf_fuse(Tensor depth, Tensor? rgb, Tensor pose, Tensor view_begin, Tensor origin, int[] dims, float voxel, int dataset, "
+            "float trunc=0.0) -> (Tensor, Tensor, Tensor)")
+# the state of tsdf_fuse -> points, normals f64 [S,max_points,3], colors f32 [S,max_points,3] (empty without color_sum), valid u8 [S,max_points],
+# n_points i32 [S]
+_lib.define("tsdf_surface(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Tensor origin, float voxel, int min_weight=1, "
+            "int max_points=65536) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 _lib.define("affinity_topk(Tensor feat_s, Tensor weight_s, Tensor feat_t, Tensor weight_t, Tensor ns, Tensor nt, "
             "float[] params, int topK, bool want_wij) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("match_pairs(Tensor pc_s, Tensor normal_s, Tensor feat_s, Tensor weight_s, Tensor pc_t, Tensor normal_t, "
@@ -266,6 +275,19 @@ def _visibility(pc, valid, depth, query_cloud, ref_view, pose, dataset, tol_abs=
                                 int(radius), want_class=True)
 
 
+def _tsdf_fuse(depth, rgb, pose, view_begin, origin, dims, voxel, dataset, trunc=0.0):
+    st = _util.tsdf_fuse_dev(depth, rgb, pose, view_begin, origin.cpu().numpy(), tuple(int(v) for v in dims), float(voxel), _INV_DATASET[int(dataset)],
+                             None if float(trunc) == 0.0 else float(trunc))
+    return st["tsdf_sum"], st["weight"], (depth.new_empty(0, dtype=torch.int32) if st["color_sum"] is None else st["color_sum"])
+
+
+def _tsdf_surface(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_points=65536):
+    S, nz, ny, nx = tsdf_sum.shape
+    st = {"tsdf_sum": tsdf_sum, "weight": weight, "color_sum": color_sum, "origin": origin.cpu().numpy(), "dims": (nx, ny, nz), "voxel": float(voxel)}
+    points, normals, colors, valid, n = _util.tsdf_surface_dev(st, int(min_weight), int(max_points))
+    return points, normals, (tsdf_sum.new_empty(0, dtype=torch.float32) if colors is None else colors), valid, n
+
+
 def _affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     wij, cj, cw, keff = _rp.affinity_topk(feat_s.contiguous(), weight_s.contiguous(), feat_t.contiguous(), weight_t.contiguous(),
                                           ns.contiguous(), nt.contiguous(), _para(params, topK), want_wij=bool(want_wij))
@@ -288,7 +310,8 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("global_registration", _global_registration), ("colored_icp", _colored_icp), ("color_registration", _color_registration),
                    ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank),
                    ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals),
-                   ("frames_to_pano", _frames_to_pano), ("overlap", _overlap), ("visibility", _visibility)):
+                   ("frames_to_pano", _frames_to_pano), ("overlap", _overlap), ("visibility", _visibility),
+                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -423,6 +446,19 @@ def _m_visibility(pc, valid, depth, query_cloud, ref_view, pose, dataset, tol_ab
     return pc.new_empty(Q, 6, dtype=torch.int32), pc.new_empty(Q, dtype=torch.int64), pc.new_empty(Q, P, dtype=torch.uint8)
 
 
+def _m_tsdf_fuse(depth, rgb, pose, view_begin, origin, dims, voxel, dataset, trunc=0.0):
+    S, (nx, ny, nz) = view_begin.shape[0] - 1, dims
+    return (depth.new_empty(S, nz, ny, nx, dtype=torch.int32), depth.new_empty(S, nz, ny, nx, dtype=torch.int32),
+            depth.new_empty(0, dtype=torch.int32) if rgb is None else depth.new_empty(S, 3, nz, ny, nx, dtype=torch.int32))
+
+
+def _m_tsdf_surface(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_points=65536):
+    S, cap = tsdf_sum.shape[0], int(max_points)
+    return (tsdf_sum.new_empty(S, cap, 3, dtype=torch.float64), tsdf_sum.new_empty(S, cap, 3, dtype=torch.float64),
+            tsdf_sum.new_empty(0, dtype=torch.float32) if color_sum is None else tsdf_sum.new_empty(S, cap, 3, dtype=torch.float32),
+            tsdf_sum.new_empty(S, cap, dtype=torch.uint8), tsdf_sum.new_empty(S, dtype=torch.int32))
+
+
 def _m_affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     B, ns_max, nt_max = feat_s.shape[0], feat_s.shape[1], feat_t.shape[1]
     wij = feat_s.new_empty(B, ns_max, nt_max, dtype=torch.float32) if want_wij else feat_s.new_empty(0)
@@ -442,10 +478,11 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("global_registration", _m_global_registration), ("colored_icp", _m_colored_icp), ("color_registration", _m_color_registration),
                    ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank),
                    ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals),
-                   ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap), ("visibility", _m_visibility)):
+                   ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap), ("visibility", _m_visibility),
+                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
        "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals",
-       "frames_to_pano", "overlap", "visibility")
+       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface")

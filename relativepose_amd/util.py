@@ -603,6 +603,200 @@ def visibility_matrix_dev(pc, valid, depth, R, dataset, tol_abs=0.05, tol_rel=0.
     return counts, margin, visibility_scores(counts, margin)
 
 
+def _tsdf_host_geometry(origin, dims, S):
+    origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1, 3)
+    if origin.shape[0] != S or len(dims) != 3:
+        raise ValueError("one origin (x, y, z) per scene and dims = (nx, ny, nz)")
+    return origin, tuple(int(v) for v in dims)
+
+
+def tsdf_fuse_dev(depth, rgb, R, view_begin, origin, dims, voxel, dataset, trunc=None, state=None):
+    """relpose_tsdf_fuse (include/relpose.h): integrate posed depth panoramas into one TSDF volume per scene.  depth
+    [V,h,4h] f32 and rgb [V,3,h,4h] f32 (or None) CUDA tensors; R [V,4,4] float64 world -> camera poses (host array or CUDA tensor: the
+    loaders' R); view_begin: S + 1 ascending view offsets (read on the host; scene s owns the views view_begin[s] .. view_begin[s+1]-1, at
+    most 4096 per call); origin [S,3] and dims = (nx, ny, nz) on the host: the corner of voxel (0, 0, 0) and the voxel counts, shared by all
+    scenes, like voxel and trunc (default 4 voxel).
+    -> the state {"tsdf_sum" i32 [S,nz,ny,nx], "weight" i32, "color_sum" i32 [S,3,nz,ny,nx] or None, "origin", "dims", "voxel", "trunc",
+    "dataset"}.  state=None allocates and stores; a given state (of the same geometry) is added to -- the volume does not depend on how the
+    views are split over calls, nor on their order.  The caller keeps a voxel's weight <= 65535.  The call waits for the stream once."""
+    import torch
+    _lib.require_gpu()
+    if depth.dim() != 3 or depth.shape[2] != 4 * depth.shape[1] or depth.dtype != torch.float32:
+        raise ValueError("tsdf_fuse_dev takes depth [V,h,4h] float32")
+    V, h = int(depth.shape[0]), int(depth.shape[1])
+    dev = depth.device
+    if rgb is not None and (tuple(rgb.shape) != (V, 3, h, 4 * h) or rgb.dtype != torch.float32 or rgb.device != dev):
+        raise ValueError("tsdf_fuse_dev takes rgb [V,3,h,4h] float32 on depth's device")
+    vb = np.ascontiguousarray(view_begin.cpu().numpy() if hasattr(view_begin, "cpu") else view_begin, dtype=np.int32).reshape(-1)
+    S = len(vb) - 1
+    if S < 1:
+        raise ValueError("tsdf_fuse_dev takes view_begin [S + 1] with S >= 1")
+    origin, dims = _tsdf_host_geometry(origin, dims, S)
+    voxel = float(voxel)
+    trunc = 4.0 * voxel if trunc is None else float(trunc)
+    pose = R if hasattr(R, "data_ptr") else torch.from_numpy(np.ascontiguousarray(R, dtype=np.float64).reshape(-1, 4, 4)).to(dev)
+    if tuple(pose.shape) != (V, 4, 4) or pose.dtype != torch.float64 or pose.device != dev:
+        raise ValueError("tsdf_fuse_dev takes one float64 4x4 pose per view")
+    nx, ny, nz = dims
+    if state is None:
+        state = {"tsdf_sum": torch.empty(S, nz, ny, nx, dtype=torch.int32, device=dev), "weight": torch.empty(S, nz, ny, nx, dtype=torch.int32, device=dev),
+                 "color_sum": None if rgb is None else torch.empty(S, 3, nz, ny, nx, dtype=torch.int32, device=dev),
+                 "origin": origin.copy(), "dims": dims, "voxel": voxel, "trunc": trunc, "dataset": dataset}
+        accumulate = 0
+    else:
+        if (tuple(state["tsdf_sum"].shape) != (S, nz, ny, nx) or state["dims"] != dims or state["voxel"] != voxel or state["trunc"] != trunc
+                or not np.array_equal(state["origin"], origin) or (state["color_sum"] is None) != (rgb is None)
+                or dataset_id(state["dataset"]) != dataset_id(dataset)):
+            raise ValueError("tsdf_fuse_dev: the state was built with another geometry, truncation, dataset or without / with colours")
+        accumulate = 1
+    if V == 0:
+        if not accumulate:
+            for k in ("tsdf_sum", "weight", "color_sum"):
+                if state[k] is not None:
+                    state[k].zero_()
+        return state
+    L = _lib.lib()
+    nbytes = L.relpose_tsdf_fuse_workspace_bytes(S, V, h, nx, ny, nz)
+    if nbytes == 0:
+        raise ValueError("tsdf_fuse_dev: sizes outside relpose_tsdf_fuse's limits")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dc, rc, pc_ = depth.contiguous(), (None if rgb is None else rgb.contiguous()), pose.contiguous()
+    a = _lib.TsdfFuseArgs()
+    a.struct_size = _lib.C.sizeof(_lib.TsdfFuseArgs)
+    a.n_scenes, a.n_views, a.h, a.dataset = S, V, h, dataset_id(dataset)
+    a.nx, a.ny, a.nz, a.accumulate = nx, ny, nz, accumulate
+    a.depth, a.rgb, a.pose = dc.data_ptr(), (0 if rc is None else rc.data_ptr()), pc_.data_ptr()
+    a.view_begin_host, a.origin_host = vb.ctypes.data, origin.ctypes.data
+    a.voxel, a.trunc = voxel, trunc
+    a.tsdf_sum, a.weight = state["tsdf_sum"].data_ptr(), state["weight"].data_ptr()
+    a.color_sum = 0 if rgb is None else state["color_sum"].data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.stream = _lib.stream_ptr()
+    rc_ = L.relpose_tsdf_fuse(_lib.C.byref(a))
+    if rc_ == -1:
+        raise ValueError("relpose_tsdf_fuse: invalid arguments (view_begin not ascending from 0 to V, more than 4096 views in a scene, h odd, "
+                         "a non-finite origin, voxel or trunc not > 0, or sizes outside the limits)")
+    _lib.check(rc_, "relpose_tsdf_fuse")
+    return state
+
+
+def tsdf_surface_dev(state, min_weight=1, max_points=None):
+    """relpose_tsdf_surface: the zero crossings of tsdf_fuse_dev's state as an oriented, coloured point cloud per scene.
+    -> (points [S,cap,3] f64, normals [S,cap,3] f64, colors [S,cap,3] f32 or None, valid [S,cap] u8, n_points [S] i32) CUDA tensors in
+    overlap_dev's pc / valid layout; cap = max_points.  n_points counts every crossing and may exceed cap: only the first cap, in ascending
+    voxel order, are written; rows at and beyond n_points are zero with valid 0.  max_points=None sizes cap to the largest scene with a
+    counting call first (cap at least 1).  The normals point towards the space the sensors saw through."""
+    import torch
+    _lib.require_gpu()
+    ts, wt, cs = state["tsdf_sum"], state["weight"], state["color_sum"]
+    S, nz, ny, nx = (int(v) for v in ts.shape)
+    dev = ts.device
+    origin = np.ascontiguousarray(state["origin"], dtype=np.float64).reshape(S, 3)
+    L = _lib.lib()
+    nbytes = L.relpose_tsdf_surface_workspace_bytes(S, nx, ny, nz)
+    if nbytes == 0 or int(min_weight) < 1:
+        raise ValueError("tsdf_surface_dev: sizes outside relpose_tsdf_surface's limits, or min_weight < 1")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    tsc, wtc, csc = ts.contiguous(), wt.contiguous(), (None if cs is None else cs.contiguous())
+
+    def call(cap, colours):
+        points = torch.zeros(S, cap, 3, dtype=torch.float64, device=dev)
+        normals = torch.zeros(S, cap, 3, dtype=torch.float64, device=dev)
+        colors = torch.zeros(S, cap, 3, dtype=torch.float32, device=dev) if colours else None
+        valid = torch.empty(S, cap, dtype=torch.uint8, device=dev)
+        n_points = torch.empty(S, dtype=torch.int32, device=dev)
+        a = _lib.TsdfSurfaceArgs()
+        a.struct_size = _lib.C.sizeof(_lib.TsdfSurfaceArgs)
+        a.n_scenes, a.nx, a.ny, a.nz, a.min_weight, a.cap = S, nx, ny, nz, int(min_weight), cap
+        a.tsdf_sum, a.weight, a.color_sum = tsc.data_ptr(), wtc.data_ptr(), (0 if csc is None else csc.data_ptr())
+        a.origin_host, a.voxel = origin.ctypes.data, float(state["voxel"])
+        a.points, a.normals, a.colors = points.data_ptr(), normals.data_ptr(), (colors.data_ptr() if colours else 0)
+        a.valid, a.n_points = valid.data_ptr(), n_points.data_ptr()
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+        a.stream = _lib.stream_ptr()
+        rc_ = L.relpose_tsdf_surface(_lib.C.byref(a))
+        if rc_ == -1:
+            raise ValueError("relpose_tsdf_surface: invalid arguments (max_points < 1 or S max_points >= 2^29, or sizes outside the limits)")
+        _lib.check(rc_, "relpose_tsdf_surface")
+        return points, normals, colors, valid, n_points
+
+    if max_points is None:
+        max_points = max(1, int(call(1, False)[4].max().item()))
+    return call(int(max_points), cs is not None)
+
+
+def tsdf_bounds_dev(depth, R, dataset, voxel, pad=3, view_begin=None):
+    """The box tsdf_fuse_dev should be given: per scene, around every pixel with data of its views unprojected (pano2pc_dev) and moved into the
+    world frame by the inverse of its pose R [V,4,4] (host float64, world -> camera), widened by `pad` voxels on every side.
+    view_begin=None: one scene of all views.  -> (origin [S,3] host float64, dims (nx, ny, nz): the maximum over the batch, so every scene
+    gets the same volume shape).  A scene without a valid pixel gets the origin -pad voxel and one voxel plus the padding."""
+    import torch
+    V = int(depth.shape[0])
+    vb = np.array([0, V]) if view_begin is None else np.asarray(view_begin.cpu().numpy() if hasattr(view_begin, "cpu") else view_begin).reshape(-1)
+    S = len(vb) - 1
+    voxel = float(voxel)
+    origin = np.full((S, 3), -pad * voxel)
+    dims = np.full(3, 1 + 2 * pad, np.int64)
+    if V:
+        # the skybox's own unprojection: the scannet branch of relpose_pano2pc scales x and y by the kinect intrinsics, which the projection
+        # of relpose_tsdf_fuse (csrc/skybox.h) does not; matterport has scannet's face order.  pano2pc marks every suncg pixel valid, so
+        # the validity is the fuse rule's: finite and > 0.
+        pc, _ = pano2pc_dev(depth, "suncg" if dataset_id(dataset) == DATASETS["suncg"] else "matterport")      # [V,3,P] camera frame, face-major
+        h = int(depth.shape[1])
+        faces = depth.reshape(V, h, 4, h).permute(0, 2, 1, 3).reshape(V, 4 * h * h)
+        valid = torch.isfinite(faces) & (faces > 0)
+        Rh = np.ascontiguousarray(R.cpu().numpy() if hasattr(R, "cpu") else R, dtype=np.float64).reshape(V, 4, 4)
+        inv = torch.from_numpy(np.stack([np.linalg.inv(Rh[v]) for v in range(V)])).to(depth.device)
+        pw = torch.matmul(inv[:, :3, :3], pc) + inv[:, :3, 3:4]
+        ok = valid.unsqueeze(1)
+        big = torch.full_like(pw, float("inf"))
+        lo = torch.where(ok, pw, big).amin(2).cpu().numpy()                                           # [V,3]
+        hi = torch.where(ok, pw, -big).amax(2).cpu().numpy()
+        for s in range(S):
+            if vb[s + 1] > vb[s]:
+                l, u = lo[vb[s]:vb[s + 1]].min(0), hi[vb[s]:vb[s + 1]].max(0)
+                if np.isfinite(l).all() and np.isfinite(u).all():
+                    origin[s] = l - pad * voxel
+                    dims = np.maximum(dims, np.ceil((u - l) / voxel).astype(np.int64) + 2 * pad + 1)
+    return origin, tuple(int(v) for v in dims)
+
+
+def save_ply(path, points, normals=None, colors=None):
+    """Write a binary little-endian PLY point cloud: points [N,3] (float32 x y z in the file), normals [N,3] (nx ny nz) and colors [N,3] in
+    [0, 1] (uchar red green blue) if given; arrays or tensors.  Returns N."""
+    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+    p = host(points).reshape(-1, 3)
+    N = p.shape[0]
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {N}", "property float x", "property float y", "property float z"]
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    rec = np.zeros(N, dtype=np.dtype(fields))
+    for a, k in enumerate("xyz"):
+        rec[k] = p[:, a]
+    if normals is not None:
+        n = host(normals).reshape(-1, 3)
+        if n.shape[0] != N:
+            raise ValueError("save_ply: one normal per point")
+        for a, k in enumerate(("nx", "ny", "nz")):
+            rec[k] = n[:, a]
+    if colors is not None:
+        c = host(colors).reshape(-1, 3)
+        if c.shape[0] != N:
+            raise ValueError("save_ply: one colour per point")
+        q = np.rint(np.clip(np.nan_to_num(c.astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
+        for a, k in enumerate(("red", "green", "blue")):
+            rec[k] = q[:, a]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+    return N
+
+
 def depth2pc(depth, dataList):
     """util.py:468: depth numpy = one h x h face (suncg / matterport) or the 66x88 kinect crop (scannet)
     -> (pc [k,3] of the non-zero depths, mask)."""
