@@ -99,10 +99,17 @@ void relpose_default_params(RelposeParams* p_host);
  *                                   computes nor stores an (image, stream, 8 x 32 tile) block of A1 whose inputs are all +-0 and whose
  *                                   zeros an earlier forward on the workspace left there (it stores +0.0 once otherwise) (default),
  *                                   1 = a separate occupancy pass, every launched block computed and stored (same bits); read by every
- *                                   forward (the plans are the same); without the zero-tile lists (RELPOSE_TUNE_ZERO_TILES = 1) 1 is what runs */
+ *                                   forward (the plans are the same); without the zero-tile lists (RELPOSE_TUNE_ZERO_TILES = 1) 1 is what runs
+ *   RELPOSE_TUNE_CONV4_ROWS         0 = SCNet's conv4 computes, per K slice (= encoder stream), only the rows whose 3 x 3 occupancy blocks hold a
+ *                                   non-zero input value plus one representative per BatchNorm group and edge class, on a row-list launch, where
+ *                                   that list is sparse enough to pay; the split-K reduce reads the other rows through a map (default),
+ *                                   1 = every row on the strip kernel and no extra launches, 2 = the row-list launch for every slice whatever
+ *                                   its density (same bits all three; a slice whose stream holds a non-finite input value always
+ *                                   stays on the strip kernel); 0 / 2 need the occupancy words (RELPOSE_TUNE_ZERO_TILES = 0); read
+ *                                   when a forward looks up its plan (0 and 2 share one) */
 enum { RELPOSE_TUNE_AFFINITY_KERNEL = 0, RELPOSE_TUNE_FIT_MAX_PRODUCTS = 1, RELPOSE_TUNE_FIT_CLUSTER = 2,
        RELPOSE_TUNE_FIT_GLOBAL_VECTORS = 3, RELPOSE_TUNE_FIT_FIXED_CHECKS = 4, RELPOSE_TUNE_HEADS_KERNEL = 5, RELPOSE_TUNE_DECONV_STRIP = 6,
-       RELPOSE_TUNE_ZERO_TILES = 7, RELPOSE_TUNE_CONV1_ZERO = 8, RELPOSE_TUNE_COUNT = 9 };
+       RELPOSE_TUNE_ZERO_TILES = 7, RELPOSE_TUNE_CONV1_ZERO = 8, RELPOSE_TUNE_CONV4_ROWS = 9, RELPOSE_TUNE_COUNT = 10 };
 int relpose_set_tuning(int32_t key, int32_t value);
 const char* relpose_version(void);
 /* ------------------------------------------------------------------ matcher
@@ -1182,7 +1189,8 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args);
 /* Multiply-accumulates one forward of a plan family executes (host-only, no device access): flags as above, self_cached != 0 = the plan
  * a forward takes when it finds its self_tag on the workspace.  The full forward (flags 0, self_cached 0) counts every member of
  * model/mymodel.py:259-380; the level-0 plan and the self-stream cache count what they really launch.  bench.py divides the two for
- * its plan-aware in-loop roofline ("roofline.in_loop"). */
+ * its plan-aware in-loop roofline ("roofline.in_loop").  It is the STATIC plan that is counted: the patches and rows that the zero-tile lists
+ * and conv4's row lists drop depend on the input and stay counted (relpose_scnet_zero_tiles / relpose_scnet_conv4_rows report them). */
 int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n_images, int32_t flags, int32_t self_cached, double* macs_host);
 
 /* Which kernel the plain plan of n_images runs `layer` ("deconv4", ...) on under the current precision and tuning knobs (host-only, a dry-run
@@ -1201,6 +1209,12 @@ int relpose_scnet_zero_tiles(RelposeSCNet* net, void* workspace, void* stream, i
  * non-finite conv1 weight).  occ_host, if not NULL, receives that forward's occupancy words [n_images][6][28] (RELPOSE_EINVAL if it ran
  * without the zero-tile lists).  Synchronises `stream` (the forward's).  For tests and profiles. */
 int relpose_scnet_conv1_zero(RelposeSCNet* net, void* workspace, void* stream, int64_t* counts_host, uint32_t* occ_host);
+
+/* conv4's rows in the last forward (RELPOSE_TUNE_CONV4_ROWS): counts_host[18] = per K slice ks = encoder stream ks {rows computed, rows
+ * dropped (read from their representative by the split-K reduce), 1 if the slice ran on the row-list launch else 0}.  A slice on the strip
+ * kernel computes all its rows (a shared slice of the level-0 plan has 2 x 784); a slice the self-stream cache did not compute reports
+ * {0, 0, 0}.  counts_host[0] = -1 (the rest 0) if the forward ran without row lists.  Synchronises `stream`.  For tests and profiles. */
+int relpose_scnet_conv4_rows(RelposeSCNet* net, void* workspace, void* stream, int64_t* counts_host);
 
 /* Debug: copy a raw (pre-BatchNorm) layer output of the last forward, NHWC float32, to out (device).
  * Returns the number of floats written (or needed if out is NULL), <0 if unknown. */

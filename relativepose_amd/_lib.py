@@ -291,6 +291,7 @@ SIGNATURES = {
     "relpose_scnet_layer_kernel": (c_int, [c_void_p, c_char_p, c_int]),
     "relpose_scnet_zero_tiles": (c_int, [c_void_p, c_void_p, c_void_p, C.POINTER(c_int64)]),
     "relpose_scnet_conv1_zero": (c_int, [c_void_p, c_void_p, c_void_p, C.POINTER(c_int64), c_void_p]),
+    "relpose_scnet_conv4_rows": (c_int, [c_void_p, c_void_p, c_void_p, C.POINTER(c_int64)]),
     "relpose_scnet_read_tap": (c_int64, [c_void_p, c_char_p, c_void_p, c_void_p, c_void_p]),
     "relpose_scnet_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int,
                                       C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_int64), c_void_p]),
@@ -339,7 +340,7 @@ def _build_locked():
 
 # relpose_set_tuning keys (include/relpose.h RELPOSE_TUNE_*)
 TUNE_KEYS = {"affinity_kernel": 0, "fit_max_products": 1, "fit_cluster": 2, "fit_global_vectors": 3, "fit_fixed_checks": 4,
-             "heads_kernel": 5, "deconv_strip": 6, "zero_tiles": 7, "conv1_zero": 8}
+             "heads_kernel": 5, "deconv_strip": 6, "zero_tiles": 7, "conv1_zero": 8, "conv4_rows": 9}
 AFFINITY_KERNELS = {"auto": 0, "rows": 1, "tile": 2, "lds": 3, "pool": 4}
 
 

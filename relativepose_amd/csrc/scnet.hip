@@ -109,6 +109,15 @@ struct ConvDesc {
     const int* zt_count;
     const int* zt_list;
     const int2* zt_fill;
+    // conv4 row lists (RELPOSE_TUNE_CONV4_ROWS, conv4_row_list_kernel; null = every row on the strip kernel, the reduce reads row m itself):
+    // c4_cnt[ks][G] rows listed per K slice and BatchNorm group, c4_list[ks][G][2 hw] their indices, c4_map[ks][M] the row whose partial
+    // sums stand for row m of slice ks (read by the reduce for the slices that took the list path; a slice on the strip kernel has every
+    // row computed, and the strip kernel's rows beside a NaN BatchNorm group are not all copies of their class: a masked tap is 0 x a value
+    // it loads from the tile's first group), c4_hdr[6][2] {rows listed, list path taken} as the last forward that computed the slice left them
+    const int* c4_cnt;
+    const int* c4_list;
+    const int* c4_map;
+    int* c4_hdr;
 };
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return fmaxf(v, slope * v); }   // slope in (0,1]
@@ -180,9 +189,26 @@ __device__ __forceinline__ void rp_split_mma(floatx16 (&acc)[MI][NI], const floa
 // scale/shift, B weights) are issued BEFORE the MFMAs of tile kt and consumed AFTER them, so their
 // latency hides under 64 MFMAs; the loader is branch-free (clamped addresses + selects) so hipcc
 // keeps the loads in flight across the MFMA block.
-template <int WM, int WN, int MI, int NI, bool SSLDS, bool UNI = false, int SPLIT = 0>
+//
+// ROWS (conv4's row lists, RELPOSE_TUNE_CONV4_ROWS): the M tile is 128 entries of a (K slice, BatchNorm group) row list instead of 128
+// consecutive rows -- blockIdx.x = group * tiles per group + tile, so a tile lies in ONE group (conv4_row_list_kernel keeps a list per
+// group: UNI scale / shift).  The K loop runs conv_s2_strip_kernel's order -- chunk outer, then plane (p, q), then the plane's four taps
+// (rows_tap) -- with the same staged values and the same rp_tile_mma calls, and the epilogue writes each row's partial sums to its own place
+// in partial[ks][M][cout_pad]: every accumulator sees the strip kernel's MFMAs in the strip kernel's order (same bits).  Here the two
+// integer arguments are `ninner` = the K slices no launch computes (ConvDesc::skip_slices of the plan) and `mt_max` = the density
+// threshold theta in 1 / 1024: slice ks takes this kernel iff rows listed * 1024 < theta * rows and no group of its stream holds a
+// non-finite value; workgroup (0, 0) writes the choice to c4_hdr and, as skip bits, to the descriptor the strip kernel launched NEXT
+// reads (its workgroups of those slices exit).  (A non-finite stream makes its BatchNorm group NaN in every row; which NaN bit pattern
+// comes out of a chain of NaN operands is a property of a kernel's instruction selection, not of the arithmetic, so those rows keep
+// the one kernel that has always computed them and the bits stay those of RELPOSE_TUNE_CONV4_ROWS = 1.)
+__device__ __forceinline__ int rows_tap(int s) {       // step s of a chunk -> tap ky * 4 + kx: plane s >> 2 = (p, q), tap s & 3 of the plane
+    const int p = s >> 3, q = (s >> 2) & 1, ty = (s >> 1) & 1, tx = s & 1;
+    return (p ? 2 * ty : 1 + 2 * ty) * 4 + (q ? 2 * tx : 1 + 2 * tx);
+}
+template <int WM, int WN, int MI, int NI, bool SSLDS, bool UNI = false, int SPLIT = 0, bool ROWS = false>
 __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * WN == 8 || MI == 1) ? 4 : (SSLDS ? 3 : 2))) void conv_igemm_kernel(const ConvDesc* __restrict__ descs, int ninner, int mt_max) {
     constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
+    static_assert(!ROWS || (SSLDS && UNI && SPLIT != 1), "row lists: one BatchNorm group per tile, the strip kernel's operand modes");
     constexpr int LD = RowLd<SPLIT>::v;                 // LDS row stride (floats); three-piece bf16 rows: [32 hi | 32 mid | 32 lo | pad]
     constexpr bool S3 = SPLIT >= 4;
     // Block order.  ninner == 1: member-major (each member's weights stay L2-resident while it runs).
@@ -190,7 +216,8 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
     // the 4 phases of a spatial tile run back to back on the SAME XCD (blocks are dealt round-robin to the
     // 8 XCDs), so the tile is fetched from HBM once and re-used from that XCD's L2 by the other phases.
     int zmem, mtile;
-    if (ninner == 1) { zmem = blockIdx.x / mt_max; mtile = blockIdx.x - zmem * mt_max; }
+    if (ROWS) { zmem = 0; mtile = blockIdx.x; }
+    else if (ninner == 1) { zmem = blockIdx.x / mt_max; mtile = blockIdx.x - zmem * mt_max; }
     else {
         const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, t8 = (mt_max + 7) >> 3;
         const int inner = slot % ninner, rest = slot / ninner;
@@ -198,6 +225,28 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
         mtile = (rest % t8) * 8 + xcd;
     }
     const ConvDesc d = descs[zmem];                   // block-uniform: scalar loads
+    int rows_g = 0, rows_n = 0, rows_t0 = 0;          // ROWS: the tile's BatchNorm group, its list's length and the tile's first entry
+    if constexpr (ROWS) {
+        const int G = d.Nimg >> 1, tpg = (2 * d.Hp * d.Wp + BM - 1) / BM;
+        const int ksr = blockIdx.y / d.ntiles_n;
+        int take = 0;                                 // bit ks: slice ks takes the list path
+        for (int q = 0; q < d.ksplit; ++q) {
+            if ((ninner >> q) & 1) continue;
+            const int ng = ((d.shared_slices >> q) & 1) ? 1 : G;
+            int listed = 0, nonfin = 0;               // (bit 30 of a count: the group's stream holds a non-finite value)
+            for (int g = 0; g < ng; ++g) { const int c = d.c4_cnt[q * G + g]; listed += c & 0x3fffffff; nonfin |= c >> 30; }
+            const bool lp = !nonfin && (long long)listed * 1024 < (long long)mt_max * ng * 2 * d.Hp * d.Wp;
+            take |= lp ? 1 << q : 0;
+            if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { d.c4_hdr[2 * q] = listed; d.c4_hdr[2 * q + 1] = lp; }
+        }
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
+            *const_cast<int*>(&descs[0].skip_slices) = ninner | take;      // (nobody in this launch reads the field; the strip kernel is next)
+        if (!((take >> ksr) & 1)) return;
+        rows_g = mtile / tpg; rows_t0 = (mtile - rows_g * tpg) * BM;
+        if (((d.shared_slices >> ksr) & 1) && rows_g > 0) return;
+        rows_n = d.c4_cnt[ksr * G + rows_g];          // (a listed slice has no flag bits in its counts)
+        if (rows_t0 >= rows_n) return;
+    } else
     if (mtile * BM >= d.M) return;                    // groups share a grid; shorter members exit
     constexpr int NT = WM * WN * 64;                    // threads per block (4 or 8 waves)
     constexpr int RPI = NT / KQ;                        // tile rows covered per loader iteration
@@ -216,7 +265,7 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
     const int ks = blockIdx.y / d.ntiles_n;
     const int m0 = mtile * BM, n0 = (blockIdx.y - ks * d.ntiles_n) * BN;
     const int hw = d.Hp * d.Wp;
-    const int g0 = (m0 / hw) >> 1;                      // first BatchNorm group touched by this tile
+    const int g0 = ROWS ? rows_g : (m0 / hw) >> 1;      // first BatchNorm group touched by this tile
 
     // Per tile row (computed once, by one thread per row): pixel index of the (tap 0,0) origin, a 16-bit mask
     // of the taps that fall inside the image (everything else is zero padding) packed with the BatchNorm
@@ -224,7 +273,8 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
     const int kq = tid % KQ, lrow = tid / KQ;
     int* rtab = reinterpret_cast<int*>(&As[0]);      // [BM][2] {base, mask | grp << 16}
     for (int row_ = tid; row_ < BM; row_ += NT) {
-        const int m = m0 + row_;
+        int m = m0 + row_;
+        if constexpr (ROWS) m = rows_t0 + row_ < rows_n ? d.c4_list[((size_t)ks * (d.Nimg >> 1) + rows_g) * 2 * hw + rows_t0 + row_] : d.M;
         int pix = -1, base = 0, mg = 0, slot = -1;
         if (m < d.M) {
             const int img = m / hw, rem = m - img * hw;
@@ -235,18 +285,20 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
             base = (img * d.Hin + y0) * d.Win + x0;
             int msk = 0;
             for (int t = 0; t < d.ntaps; ++t) {
-                const int iy = y0 + descs[zmem].offy[t], ix = x0 + descs[zmem].offx[t];
+                const int to = ROWS ? rows_tap(t) : t;                 // (ROWS: mask bit and tapdelta entry t = step t of a chunk)
+                const int iy = y0 + descs[zmem].offy[to], ix = x0 + descs[zmem].offx[to];
                 msk |= ((iy >= 0) & (iy < d.Hin) & (ix >= 0) & (ix < d.Win)) ? (1 << t) : 0;
             }
             mg = msk | ((SSLDS ? ((img >> 1) - g0) * d.Cin : (img >> 1)) << 16);
+            if constexpr (ROWS) pix = m;                              // the epilogue's row of partial[ks]
         }
         rowpix[row_] = pix; rowslot[row_] = (signed char)slot;
         rtab[2 * row_] = base; rtab[2 * row_ + 1] = mg;
     }
-    if (tid < 16) tapdelta[tid] = (int)descs[zmem].offy[tid] * d.Win + (int)descs[zmem].offx[tid];
+    if (tid < 16) { const int to = ROWS ? rows_tap(tid) : tid; tapdelta[tid] = (int)descs[zmem].offy[to] * d.Win + (int)descs[zmem].offx[to]; }
     if (SSLDS) {
         // scale/shift of every (group, input channel) this tile can touch; both sources concatenated
-        const int ng = min(((min(m0 + BM, d.M) - 1) / hw >> 1) - g0 + 1, SS_CAP / d.Cin);
+        const int ng = ROWS ? 1 : min(((min(m0 + BM, d.M) - 1) / hw >> 1) - g0 + 1, SS_CAP / d.Cin);
         for (int idx = tid; idx < ng * d.Cin; idx += NT) {
             const int g = g0 + idx / d.Cin, c = idx % d.Cin;
             const bool s1 = c >= d.src[0].C;
@@ -288,7 +340,8 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
     // line Cin/32 k-tiles later, after the other workgroups of the XCD had flushed the 4 MB L2 (16x HBM re-fetch on
     // deconv2, PMC).  The weight rows stay [tap][Cin].
     const int cpt = d.Cin / BK;                         // channel chunks per tap
-    int tap = d.tap_inner ? kt_begin % d.ntaps : kt_begin / cpt, c0 = (d.tap_inner ? kt_begin / d.ntaps : kt_begin % cpt) * BK;
+    const bool tap_in = ROWS || d.tap_inner;
+    int tap = tap_in ? kt_begin % d.ntaps : kt_begin / cpt, c0 = (tap_in ? kt_begin / d.ntaps : kt_begin % cpt) * BK;
     __syncthreads();       // tapdelta / rowpix / sstab / rtab visible
 #pragma unroll
     for (int it = 0; it < A_IT; ++it) {
@@ -325,12 +378,12 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
             const float* q = reinterpret_cast<const float*>(sss_ + (size_t)g0 * sst_ + cc_);                      \
             qu0 = rp_ldg4(q); qu1 = rp_ldg4(q + 4);                                                               \
         }                                                                                                         \
-        const int kof_ = (tap * d.Cin + c0) * (S3 ? 3 : 2) / 2;                                                   \
+        const int kof_ = ((ROWS ? rows_tap(tap) : tap) * d.Cin + c0) * (S3 ? 3 : 2) / 2;                          \
         _Pragma("unroll") for (int it = 0; it < B_IT; ++it) {                                                     \
             rb[it] = rp_ldg4(b_src[it] + kof_);                                                                   \
             if (S3) { const float2 l_ = rp_ldg2(b_src[it] + kof_ + 32 - kq * 2); rbl[S3 ? it : 0] = l_; }          \
         }                                                                                                         \
-        if (d.tap_inner) { ++tap; if (tap == d.ntaps) { tap = 0; c0 += BK; } }                                    \
+        if (tap_in) { ++tap; if (tap == d.ntaps) { tap = 0; c0 += BK; } }                                         \
         else { c0 += BK; if (c0 == d.Cin) { c0 = 0; ++tap; } }                                                    \
     }
 
@@ -444,7 +497,8 @@ __global__ __launch_bounds__(WM * WN * 64, (NI == 4 || SPLIT >= 4) ? 2 : ((WM * 
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * MI * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                int m = m0 + wm * MI * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if constexpr (ROWS) { m = rowpix[m - m0]; if (m < 0) continue; }
                 if (m >= d.M) continue;
 #pragma unroll
                 for (int j = 0; j < NI; ++j) rp_stg(po + (size_t)m * d.cout_pad + n0 + wn * NI * 32 + j * 32 + (lane & 31), acc[i][j][r]);
@@ -1636,7 +1690,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvDesc* __re
         const int img = m / hw, rem = m - img * hw;
         const int msh = (img & 1) * hw + rem;                     // the row of a shared slice (ConvDesc::shared_slices)
         for (int ks = 0; ks < d.ksplit; ++ks) {
-            const float4 v = rp_ldg4(d.partial + ((size_t)ks * d.M + (((d.shared_slices >> ks) & 1) ? msh : m)) * d.cout_pad + c4);
+            int mr = ((d.shared_slices >> ks) & 1) ? msh : m;
+            if (d.c4_map && d.c4_hdr[2 * ks + 1]) mr = d.c4_map[(size_t)ks * d.M + mr];       // conv4 row lists: the row computed in this one's stead (same bits)
+            const float4 v = rp_ldg4(d.partial + ((size_t)ks * d.M + mr) * d.cout_pad + c4);
             a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
         }
         const int yp = rem / d.Wp, xp = rem - yp * d.Wp;
@@ -2132,7 +2188,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const ConvDesc
             const int img = m / hw, rem = m - img * hw;
             const int msh = (img & 1) * hw + rem;                 // the row of a shared slice (ConvDesc::shared_slices)
             for (int ks = 0; ks < d.ksplit; ++ks) {
-                const float4 v = rp_ldg4(d.partial + ((size_t)ks * d.M + (((d.shared_slices >> ks) & 1) ? msh : m)) * d.cout_pad + c4);
+                int mr = ((d.shared_slices >> ks) & 1) ? msh : m;
+                if (d.c4_map && d.c4_hdr[2 * ks + 1]) mr = d.c4_map[(size_t)ks * d.M + mr];   // conv4 row lists: the row computed in this one's stead (same bits)
+                const float4 v = rp_ldg4(d.partial + ((size_t)ks * d.M + mr) * d.cout_pad + c4);
                 a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
             }
             const int yp = rem / d.Wp, xp = rem - yp * d.Wp;
@@ -2420,6 +2478,79 @@ __global__ __launch_bounds__(128) void zero_tile_list_kernel(const unsigned* __r
     if (tid < cnt[1] && base[1] + tid < cap) fills[base[1] + tid] = fl[tid];
 }
 
+// ---- conv4 row lists (RELPOSE_TUNE_CONV4_ROWS) ----------------------------------------------------------------------------
+// conv4's K slice q is stream block q of A3, so a row of a slice's partial sums depends on one stream.  Output pixel (oy, ox) of the 28 x 28
+// grid reads A3 rows 2oy - 1 .. 2oy + 2, A2 rows 4oy - 3 .. 4oy + 6, A1 rows 8oy - 7 .. 8oy + 14 and X0 rows 8oy - 8 .. 8oy + 15: exactly
+// the occupancy blocks oy - 1 .. oy + 1 (the same in x).  Where those 3 x 3 blocks of occ[img][q] are empty (and the group's stream holds
+// no non-finite value) the row's partial sums depend on its edge class only -- first / last / other row x column: only o = 0 and o = 27 see
+// zero padding at any of the four layers -- bit for bit.  Per BatchNorm group, slice and class the lowest such row is the representative.
+// One workgroup = one (group, slice): the rows to compute (everything but the redundant non-representatives), in ascending order, as the
+// group's own list -- a tile of conv_igemm_kernel<ROWS> then lies in one group, no count is shared between workgroups (no atomics, nothing to
+// clear) and the order is fixed; a list's last tile is partly empty (at most 127 of a launched group's rows) -- and map[q][m] = the row whose
+// partial sums the split-K reduce reads for row m; bit 30 of the count flags a non-finite value in the group's stream (nothing of it is
+// redundant, and the whole slice then stays on the strip kernel: conv_igemm_kernel<ROWS>).  nimg[q] = 0: slice q is not computed in this plan (the self-stream cache: its map stays
+// what the forward that filled the cache left, like its partial sums); nimg[q] = 2 with G > 1: a shared slice (level 0), group 0 only.
+constexpr int C4R_N = RS / ZT_BLK, C4R_HW = C4R_N * C4R_N;      // conv4's output grid: one pixel per occupancy block
+static_assert(C4R_N == ZT_NB, "conv4's grid is the occupancy grid");
+constexpr int C4R_THETA_1024 = 717;      // list path iff rows listed < theta rows, theta = 0.70 in 1 / 1024 (profiles/conv4_rows_layers.txt)
+inline size_t c4r_ints(int n) { return 16 + (size_t)6 * (n / 2) + (size_t)12 * n * C4R_HW; }      // hdr[6][2], cnt[6][G], list[6][M], map[6][M]
+__global__ __launch_bounds__(256) void conv4_row_list_kernel(const unsigned* __restrict__ occ, ZtMembers mem, int G, int* __restrict__ cnt,
+                                                             int* __restrict__ list, int* __restrict__ map) {
+    constexpr int R = 2 * C4R_HW, PER = (R + 255) / 256;
+    const int g = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    if (mem.nimg[q] == 0) return;
+    if (2 * g >= mem.nimg[q]) { if (tid == 0) cnt[q * G + g] = 0; return; }
+    __shared__ unsigned ow[2 * ZT_NB];
+    __shared__ int rep[9], nonfin, scan[256];
+    __shared__ unsigned char red[R];
+    if (tid == 0) nonfin = 0;
+    if (tid < 9) rep[tid] = R;
+    __syncthreads();
+    if (tid < 2 * ZT_NB) {
+        const unsigned v = occ[((size_t)(2 * g + tid / ZT_NB) * 6 + q) * ZT_NB + tid % ZT_NB];
+        ow[tid] = v;
+        if (v >> 31) nonfin = 1;
+    }
+    __syncthreads();
+    auto cls_of = [](int r) {
+        const int rem = r % C4R_HW, oy = rem / C4R_N, ox = rem - oy * C4R_N;
+        return 3 * (oy == 0 ? 0 : (oy == C4R_N - 1 ? 2 : 1)) + (ox == 0 ? 0 : (ox == C4R_N - 1 ? 2 : 1));
+    };
+    for (int r = tid; r < R; r += 256) {
+        const int img = r / C4R_HW, rem = r - img * C4R_HW, oy = rem / C4R_N, ox = rem - oy * C4R_N;
+        const int bx0 = max(ox - 1, 0), bx1 = min(ox + 2, C4R_N);
+        const unsigned mask = ((1u << bx1) - 1u) & ~((1u << bx0) - 1u);
+        unsigned any = 0u;
+        for (int by = max(oy - 1, 0); by < min(oy + 2, C4R_N); ++by) any |= ow[img * ZT_NB + by] & mask;
+        const bool rd = any == 0u && !nonfin;
+        red[r] = rd ? 1 : 0;
+        if (rd) atomicMin(&rep[cls_of(r)], r);
+    }
+    __syncthreads();
+    // thread tid owns rows PER tid .. PER tid + PER - 1: ordered compaction
+    const int r0 = tid * PER, r1 = min(r0 + PER, R);
+    int keep = 0;
+    for (int r = r0; r < r1; ++r) keep += (!red[r] || rep[cls_of(r)] == r) ? 1 : 0;
+    scan[tid] = keep;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int v = tid >= off ? scan[tid - off] : 0;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    int pos = scan[tid] - keep;
+    if (tid == 255) cnt[q * G + g] = scan[255] | (nonfin ? 1 << 30 : 0);
+    int* lst = list + ((size_t)q * G + g) * R;
+    int* mp = map + ((size_t)q * G + g) * R;             // (map[q][M], M = G R: group g's rows start at g R; a shared slice has group 0 only)
+    for (int r = r0; r < r1; ++r) {
+        const int rp = rep[cls_of(r)];
+        const bool k = !red[r] || rp == r;
+        if (k) lst[pos++] = g * R + r;
+        mp[r] = g * R + (k ? r : rp);
+    }
+}
+
 // After a conv_s2_tile_kernel launch with lists: workgroup i of member blockIdx.y copies the output tile(s) and the BatchNorm record of fill
 // entry i's representative to the dropped patch (pair), pixel (r, c) <- pixel (r, c), every output channel.
 template <bool PAIR>
@@ -2661,7 +2792,7 @@ struct RelposeSCNet {
     size_t w1_off = 0;           // conv1_mfma_kernel's weights inside d_w
     size_t wh_off = 0, bh_off = 0;   // fused-heads weight image and bias vector inside d_w
     std::map<std::pair<void*, int>, void*> plans;   // (workspace, n) -> Plan* (each with its own device descriptor table)
-    struct SelfState { uint64_t tag = 0, gen = 0; int n = 0, H = 0, W = 0; bool pose_only = false; };
+    struct SelfState { uint64_t tag = 0, gen = 0; int n = 0, H = 0, W = 0; bool pose_only = false; bool c4_rows = false; };   // c4_rows: it left conv4's self-slice maps
     std::map<void*, SelfState> self_state;          // workspace -> whose self-view streams it holds (relpose_scnet_forward4)
     std::map<std::string, Layer> layers;
     std::map<std::string, Buf> bufs;
@@ -2671,6 +2802,9 @@ struct RelposeSCNet {
     int last_n = 0;
     // relpose_scnet_zero_tiles: the last forward's list counts (device, null = it ran without lists) and the workgroups its conv2 / conv3 launches cover
     const int* last_zt_counts = nullptr;
+    // relpose_scnet_conv4_rows: the last forward's {rows listed, list path} per K slice (device, null = no lists) and the rows of each slice
+    const int* last_c4_hdr = nullptr;
+    int last_c4_nimg[6] = {0, 0, 0, 0, 0, 0};
     int64_t last_zt_units[2] = {0, 0};
     // conv1's zero units (RELPOSE_TUNE_CONV1_ZERO): 0 * w is NaN for a non-finite weight, so conv1 skips only when its packed weights are all
     // finite (relpose_scnet_finalize); a1z_state = the workspaces whose a1_zero bytes are known to describe the A1 they hold, under which
@@ -2957,6 +3091,9 @@ struct Plan {
     bool zt = false;             // zero-tile lists (RELPOSE_TUNE_ZERO_TILES = 0 and conv2 / conv3 on conv_s2_tile_kernel)
     int zt_nimg[6] = {0, 0, 0, 0, 0, 0};   // images of stream q's conv2 / conv3 launch member (ZtMembers)
     int64_t zt_units[2] = {0, 0};          // workgroups of the conv2 / conv3 tile-kernel launches
+    bool c4_rows = false;                  // conv4 row lists (RELPOSE_TUNE_CONV4_ROWS != 1, occupancy words, conv4 on the strip kernel)
+    int c4_desc = -1, c4_skip = 0;         // conv4's descriptor and the K slices the plan does not compute
+    int c4_nimg[6] = {0, 0, 0, 0, 0, 0};   // images of K slice q's rows (0 = not computed, 2 = a shared slice)
 };
 
 struct Builder {
@@ -2981,6 +3118,7 @@ struct Builder {
     int probe_desc = -1;
     int* zt = nullptr;          // zero-tile counts + lists in the workspace (behind the occupancy words); null = no lists (knob, dry runs)
     int zt_layer = -1;          // 0 / 1 while the members of conv2 / conv3 are added (conv() sets it from the layer name)
+    int* c4r = nullptr;         // conv4's row lists in the workspace (c4r_ints); null = none (knob, no occupancy words, dry runs)
 
     float* buf(const std::string& b);
     float2* ssb(const std::string& b);
@@ -3279,6 +3417,15 @@ void Builder::end_group() {
         if (ok) {
             if (shared_slices && (d.Cin / BK) % ksplit == 0) plan->descs[first].shared_slices = shared_slices;     // (slices = whole channel ranges here)
             if (skip_slices && (d.Cin / BK) % ksplit == 0) plan->descs[first].skip_slices = skip_slices;
+            // conv4 row lists: slice ks = stream ks of the occupancy words (six 128-channel blocks of A3 on the 28 x 28 grid); the list
+            // launch (conv_igemm_kernel<ROWS>) precedes the strip kernel inside this op, the reduce reads through the map
+            if (c4r && plan->zt && force_ksplit == 6 && ksplit == 6 && d.Cin == 6 * 128 && d.Hp == C4R_N && d.Wp == C4R_N && d.Nimg == n && cp == 256) {
+                ConvDesc& dd = plan->descs[first];
+                const size_t Mr = (size_t)n * C4R_HW;
+                dd.c4_hdr = c4r; dd.c4_cnt = c4r + 16; dd.c4_list = c4r + 16 + 6 * G; dd.c4_map = c4r + 16 + 6 * G + 6 * Mr;
+                plan->c4_rows = true; plan->c4_desc = first; plan->c4_skip = dd.skip_slices;
+                for (int q = 0; q < 6; ++q) plan->c4_nimg[q] = ((dd.skip_slices >> q) & 1) ? 0 : (((dd.shared_slices >> q) & 1) ? 2 : n);
+            }
             Op o; o.type = OP_CONV_STRIP; o.first = first; o.count = 1; o.cfg = 0; o.split = net->prec;
             o.grid = dim3((unsigned)((d.M + 127) / 128), (cp / 128) * ksplit, 1);
             plan->ops.push_back(o);
@@ -3473,7 +3620,7 @@ void free_plan(RelposeSCNet* net) {
     net->a1z_state.clear();
 }
 
-struct WsOffsets { size_t act, ss, partial, splitk, statp, persist, snap, zt, total; };
+struct WsOffsets { size_t act, ss, partial, splitk, statp, persist, snap, zt, c4r, total; };
 
 WsOffsets ws_offsets(RelposeSCNet* net, int n) {
     Plan dry;
@@ -3489,6 +3636,7 @@ WsOffsets ws_offsets(RelposeSCNet* net, int n) {
     o.persist = off; off += rp_align(dry.persist_floats * sizeof(float));
     o.snap = off; off += rp_align(dry.snap_floats * sizeof(float));
     o.zt = off; off += rp_align(zt_ints(n) * sizeof(int));      // occupancy words, then the zero-tile counts and lists (worst case)
+    o.c4r = off; off += rp_align(c4r_ints(n) * sizeof(int));    // conv4's row lists and maps: the self slices' maps live as long as `persist`
     o.total = off;
     return o;
 }
@@ -3697,6 +3845,9 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     const bool pose_only = (flags & RELPOSE_FWD_POSE_OUTPUTS) != 0 && !variant;
     Plan* plan = nullptr;
     RelposeSCNet::SelfState commit;          // what the workspace holds once this forward is through
+    const bool zt_on = g_rp_tune[RELPOSE_TUNE_ZERO_TILES] != 1;
+    const bool c4_on = zt_on && g_rp_tune[RELPOSE_TUNE_CONV4_ROWS] != 1;
+    commit.c4_rows = c4_on;
     commit.tag = self_tag; commit.n = n; commit.H = H; commit.W = W; commit.pose_only = pose_only; commit.gen = ws_gen;
     if (flags & RELPOSE_FWD_NEW_WORKSPACE) net->self_state.erase(workspace);      // the memory behind this pointer is not what the last forward left
     // Self-stream cache: the previous forward on this workspace carried the same non-zero tag (and shape, and -- when the caller names its
@@ -3707,10 +3858,9 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     net->self_state[workspace] = RelposeSCNet::SelfState();
     // (the accumulator snapshots are laid out per plan family: a pose-outputs forward has fewer decoder heads)
     bool self_cached = self_tag != 0 && prev.tag == self_tag && prev.n == n && prev.H == H && prev.W == W && prev.pose_only == pose_only && !zero_warp &&
-                       prev.gen == ws_gen;
+                       prev.gen == ws_gen && prev.c4_rows == c4_on;     // (a forward without conv4's row lists computes every row of the self slices, one with them leaves their maps)
     int snap_mode = 0;
-    const bool zt_on = g_rp_tune[RELPOSE_TUNE_ZERO_TILES] != 1;
-    const int ds_key = ((g_rp_tune[RELPOSE_TUNE_DECONV_STRIP] == 1 ? 1 : 0) << 28) | ((zt_on ? 0 : 1) << 29);       // the builder reads the knobs: one plan per value
+    const int ds_key = ((g_rp_tune[RELPOSE_TUNE_DECONV_STRIP] == 1 ? 1 : 0) << 28) | ((zt_on ? 0 : 1) << 29) | ((c4_on ? 0 : 1) << 30);       // the builder reads the knobs: one plan per value
     for (int attempt = 0; attempt < 2 && !plan; ++attempt) {
         // a tagged forward that computes the self streams also leaves the accumulator snapshots of the skip-connection halves
         snap_mode = self_cached ? 2 : (self_tag != 0 ? 1 : 0);
@@ -3732,6 +3882,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         B.persist = (float*)(ws + o.persist);
         B.snapbuf = (float*)(ws + o.snap); B.snap_mode = snap_mode; p->snap_mode = snap_mode;
         B.zt = zt_on ? (int*)(ws + o.zt) + zt_occ_ints(n) : nullptr;
+        B.c4r = c4_on ? (int*)(ws + o.c4r) : nullptr;
         build_plan(net, n, B);
         if (B.rc) {
             delete p;
@@ -3793,7 +3944,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     else
         hipLaunchKernelGGL(resize_in_kernel, dim3(2048), dim3(256), 0, s, x, act + net->bufs["X0"].off * n, n, H, W, plan->self_cached ? 8 : 0);
     mark(-3);
-    net->last_zt_counts = nullptr;
+    net->last_zt_counts = nullptr; net->last_c4_hdr = nullptr;
     net->last_zt_units[0] = plan->zt_units[0]; net->last_zt_units[1] = plan->zt_units[1];
     net->last_c1_units = 0; net->last_c1_codes = false; net->last_occ = plan->zt;
     if (plan->zt) {
@@ -3804,6 +3955,16 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         if (!occ_fused)
             hipLaunchKernelGGL(x0_occupancy_kernel, dim3(n * ZT_NB), dim3(256), 0, s, act + net->bufs["X0"].off * n, occ, ztp, plan->self_cached ? 8 : 0);
         hipLaunchKernelGGL(zero_tile_list_kernel, dim3(G, 6, 2), dim3(128), 0, s, occ, ztp, zm, n * ZT_PPI);
+        if (plan->c4_rows) {
+            // conv4's row lists and maps from the same words (nothing reads them before conv4)
+            const ConvDesc& d4 = plan->descs[plan->c4_desc];
+            ZtMembers cm;
+            for (int q = 0; q < 6; ++q) cm.nimg[q] = plan->c4_nimg[q];
+            hipLaunchKernelGGL(conv4_row_list_kernel, dim3(G, 6), dim3(256), 0, s, occ, cm, G, const_cast<int*>(d4.c4_cnt), const_cast<int*>(d4.c4_list),
+                               const_cast<int*>(d4.c4_map));
+            net->last_c4_hdr = d4.c4_hdr;
+            for (int q = 0; q < 6; ++q) net->last_c4_nimg[q] = plan->c4_nimg[q];
+        }
         mark(-2);
         net->last_zt_counts = ztp;
     }
@@ -3882,7 +4043,18 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
 #define RP_L_STRIP(SP_) hipLaunchKernelGGL((conv_s2_strip_kernel<4, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first)
 #define RP_L_DSTRIP(SP_) hipLaunchKernelGGL((deconv_strip_kernel<4, SP_>), op.grid, dim3(256), 0, s, plan->d_descs + op.first, op.mt_max)
             if (op.cfg == 1) RP_TILE_SPLIT(RP_L_DSTRIP);        // the phases of a transposed conv (deconv4, deconv5)
-            else RP_TILE_SPLIT(RP_L_STRIP);
+            else {
+                if (plan->c4_rows && op.first == plan->c4_desc) {
+                    // conv4's listed rows first (RELPOSE_TUNE_CONV4_ROWS: 0 = the slices sparser than theta, 2 = every slice); its workgroup (0, 0)
+                    // marks those slices as skipped for the strip kernel that follows (ConvDesc::skip_slices on the device)
+                    const dim3 rg((unsigned)(G * ((2 * C4R_HW + 127) / 128)), op.grid.y, 1);
+                    const int theta = g_rp_tune[RELPOSE_TUNE_CONV4_ROWS] == 2 ? (1 << 20) : C4R_THETA_1024;
+#define RP_L_ROWS(SP_) hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, true, true, SP_, true>), rg, dim3(256), 0, s, plan->d_descs + op.first, plan->c4_skip, theta)
+                    RP_TILE_SPLIT(RP_L_ROWS);
+#undef RP_L_ROWS
+                }
+                RP_TILE_SPLIT(RP_L_STRIP);
+            }
 #undef RP_L_STRIP
 #undef RP_L_DSTRIP
             mark(-1);
@@ -4021,7 +4193,9 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
 
 // Multiply-accumulates one forward of the given plan family EXECUTES (descriptor-based: rows x K x Cout of every launched member, with the
 // slices / chunks / members the level-0 plan and the self-stream cache leave out removed) -- bench.py's plan-aware in-loop roofline divides
-// it by the same count of the full plan.  Host-only (a dry-run plan build: no device memory is touched).
+// it by the same count of the full plan.  Host-only (a dry-run plan build: no device memory is touched).  It counts the STATIC plan: the
+// patches and rows that the zero-tile lists and conv4's row lists drop depend on the input and stay counted (relpose_scnet_zero_tiles,
+// relpose_scnet_conv4_rows report them per forward).
 int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n, int32_t flags, int32_t self_cached, double* macs_out) {
     if (!net || !net->finalized || !macs_out || n <= 0 || (n & 1)) return RELPOSE_EINVAL;
     if (net->variant()) { flags = 0; self_cached = 0; }          // (constructor variants run the plain plan whatever the flags)
@@ -4105,6 +4279,27 @@ int relpose_scnet_zero_tiles(RelposeSCNet* net, void* workspace, void* stream, i
         int64_t c = 0, f = 0;
         for (int q = 0; q < 6; ++q) { c += h[(l * 6 + q) * 2]; f += h[(l * 6 + q) * 2 + 1]; }
         counts_host[2 * l] = c; counts_host[2 * l + 1] = f;
+    }
+    return 0;
+}
+
+int relpose_scnet_conv4_rows(RelposeSCNet* net, void* workspace, void* stream, int64_t* counts_host) {
+    if (!net || !net->finalized || !workspace || !counts_host || net->last_n <= 0) return RELPOSE_EINVAL;
+    for (int i = 0; i < 18; ++i) counts_host[i] = 0;
+    if (!net->last_c4_hdr) {                            // the forward ran without row lists: conv4's strip kernel computed every launched row
+        counts_host[0] = -1;
+        return 0;
+    }
+    const char* lo = (const char*)workspace + ws_offsets(net, net->last_n).c4r;
+    if ((const char*)net->last_c4_hdr != lo) return RELPOSE_EINVAL;
+    int h[12];
+    RP_HIP(hipMemcpyAsync(h, net->last_c4_hdr, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    RP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    for (int q = 0; q < 6; ++q) {
+        const int64_t rows = (int64_t)net->last_c4_nimg[q] * C4R_HW;
+        if (rows == 0) continue;                        // a cached slice: nothing computed, nothing dropped in this forward
+        const bool lp = h[2 * q + 1] != 0;
+        counts_host[3 * q] = lp ? h[2 * q] : rows; counts_host[3 * q + 1] = lp ? rows - h[2 * q] : 0; counts_host[3 * q + 2] = lp ? 1 : 0;
     }
     return 0;
 }

@@ -271,6 +271,16 @@ class SCNet(torch.nn.Module):
         counts = (int(v[0]), int(v[1]), int(v[2]))
         return (counts, occ.astype(np.int64)) if occupancy else counts
 
+    def conv4_rows(self):
+        """[(computed, dropped, list_path)] * 6: per K slice (= encoder stream) of conv4 in the last forward, the rows computed, the rows
+        the split-K reduce read from a representative instead, and whether the slice ran on the row-list launch; None if the forward ran
+        without row lists (relpose_scnet_conv4_rows; synchronises the current stream)."""
+        v = (C.c_int64 * 18)()
+        _lib.check(_lib.lib().relpose_scnet_conv4_rows(self._h, _lib.ptr(self._ws), _lib.stream_ptr(), v), "relpose_scnet_conv4_rows")
+        if v[0] < 0:
+            return None
+        return [(int(v[3 * q]), int(v[3 * q + 1]), bool(v[3 * q + 2])) for q in range(6)]
+
     def layer_on_strip_kernel(self, layer, n):
         """True if ``layer`` runs on deconv_strip_kernel (either launch form)."""
         return self.layer_kernel(layer, n) in (1, 2)
