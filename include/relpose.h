@@ -1068,6 +1068,91 @@ typedef struct RelposeTsdfSurfaceArgs {
 size_t relpose_tsdf_surface_workspace_bytes(int32_t n_scenes, int32_t nx, int32_t ny, int32_t nz);
 int relpose_tsdf_surface(const RelposeTsdfSurfaceArgs* args);
 
+/* -------------------------------------------------------------------- robust synchronisation of pose graphs
+ * The pair drivers give a relative pose per pair of views; some are grossly wrong.  relpose_pose_sync turns the relative poses of n_scenes
+ * scenes into one absolute pose per view and one confidence per relative pose: graduated Geman-McClure re-weighting around a linearised
+ * rotation and translation averaging, initialised on a maximum-weight spanning tree.  The contract is the project's own (DESIGN.md 4.17;
+ * tests/sync_model.py restates it in numpy, on whole arrays and as plain loops).  The geometry is float64, every operation rounded on its
+ * own; no atomics, no eigen-solver, no stopping rule: the number of iterations is known at launch.  One workgroup per scene, one launch.
+ * Invalid arguments return RELPOSE_EINVAL before anything is enqueued or any output is touched.
+ *
+ *   layout           scene s owns the views view_begin[s] .. view_begin[s+1]-1 and the edges edge_begin[s] .. edge_begin[s+1]-1; both
+ *                    [n_scenes + 1] i32 in HOST memory, ascending from 0 to n_views / n_edges.  At most 64 views and 4096 edges per scene;
+ *                    a scene may have no views or no edges.  1 <= n_scenes < 2^24.
+ *   edges            src, dst [n_edges] i32, view indices LOCAL to the scene; T [n_edges, 4, 4] f64 row-major, T ~ X_dst inv(X_src) for world ->
+ *                    camera poses X (what the pair drivers produce: R_gt = R_t inv(R_s), evaluation.py:227; the bottom row is not read);
+ *                    w0 [n_edges] f64, the prior weight.  Several edges may join the same two views.
+ *   edge_state       [n_edges] i32: 0 = used, else the edge is ignored and the code is the FIRST of: RELPOSE_SYNC_BAD_INDEX (src or dst outside
+ *                    0 .. M-1), RELPOSE_SYNC_SELF_EDGE (src == dst), RELPOSE_SYNC_BAD_WEIGHT (w0 not finite or <= 0), RELPOSE_SYNC_BAD_POSE (an
+ *                    entry of T's top three rows not finite).  The other outputs are what they are without the ignored edges.
+ *   components       M steps of Prim: each adds the used edge of largest w0 (ties: the smaller index) that joins a visited and an unvisited
+ *                    view and marks it in tree [n_edges] i32; where none does, the smallest unvisited view starts a component and is its
+ *                    gauge (pose = identity).  component [n_views] i32: the smallest view index (local) connected to the view by used
+ *                    edges.  n_components [n_scenes] i32.
+ *   state            per view R (3x3) and u = R^T t; every 3x3 product entry is (a0 b0 + a1 b1) + a2 b2.  Along a tree edge from a visited
+ *                    src i: R_j = R_ij R_i, u_j = u_i + R_j^T t_ij; from a visited dst j: R_i = R_ij^T R_j, u_i = u_j - R_j^T t_ij.
+ *   schedule         mu = mu0; after every iteration mu = fmax(mu / div, 1.0).  The iterations with mu > 1 run, then n_final more at
+ *                    mu = 1 (defaults 64, 1.4, 10: 13 + 10).  More than RELPOSE_SYNC_MAX_ITERATIONS in total is RELPOSE_EINVAL.
+ *   iteration        1. per used edge: omega = log(R_j^T (R_ij R_i)), rho = R_j^T t_ij - (u_j - u_i).
+ *                    2. conf = 1 / (q q), q = 1 + (|omega|^2 / sigma_r^2 + |rho|^2 / sigma_t^2) / mu^2 (robust = 0: conf = 1); w = w0 conf.
+ *                    3. L = the graph Laplacian of w, the rows and columns of the gauge views replaced by the identity (which leaves the
+ *                       other entries what they are with those rows removed); row v is summed along v's adjacency list, its used edges
+ *                       in ascending index: L_vv = sum w, L_vo = 0 - w - w .., b_v = sum of +w omega where v is the edge's dst, -w omega
+ *                       where it is its src (0 for a gauge).  Right-looking Cholesky of the lower triangle (column k: d_k = sqrt(L_kk),
+ *                       l_ik = L_ik / d_k, L_ij -= l_ik l_jk for k < j <= i), then both substitutions column by column
+ *                       (x_k = y_k / d_k, y_i -= l_ik x_k): L d = b.  R_v = R_v exp(d_v) for every non-gauge view.
+ *                    4. with the new rotations, the same factor solves L u = b' with b' summed like b from R_j^T t_ij.
+ *   log              v = (E21 - E12, E02 - E20, E10 - E01), n = |v|, c = ((E00 + E11 + E22) - 1) / 2, th = atan2(n / 2, c), omega = v (th / n).
+ *                    n < 1e-6 and c > 0: omega = v / 2.  n < 1e-6 and c <= 0 (near pi): the axis from the symmetric part, at the first
+ *                    largest diagonal entry k a_k = sqrt(max((E_kk - c) / (1 - c), 0)), a_m = (E_km + E_mk) / ((2 (1 - c)) a_k), negated if
+ *                    a . v < 0; omega = th a.
+ *   exp              th^2 = |d|^2; A = sin(th) / th, B = (2 sin(th / 2)^2) / th^2; th^2 < 1e-8: A = 1 - th^2 / 6, B = 0.5 - th^2 / 24;
+ *                    X = I + A [d]x + B [d]x^2 entry by entry: X00 = 1 - B (d1 d1 + d2 d2), X01 = B (d0 d1) - A d2, X02 = B (d0 d2) + A d1, ..
+ *   outputs          pose [n_views, 4, 4] f64 world -> camera in its component's gauge: [R | R u; 0 0 0 1].  confidence [n_edges] f64: conf
+ *                    of the last iteration (1 if none ran), 0 for ignored edges.  res_rot, res_trans [n_edges] f64: |omega|, |rho| under
+ *                    the final poses, NaN for ignored edges.  cost [n_scenes] f64: sum of w0 r^2 / (1 + r^2) under the final poses with
+ *                    mu = 1 (robust = 0: w0 r^2), per view over the edges it is the dst of in ascending index, then over the views in
+ *                    ascending order.  last_step [n_scenes] f64: the largest |component of d| of the last iteration (0 if none ran).
+ *   determinism      a scene's result is bitwise repeatable and does not depend on the batch around it or its place in it.
+ *   degenerate       weights that underflow to 0 around a view make L singular there: the poses of that component are then NaN.
+ *   workspace        relpose_pose_sync_workspace(n_scenes, n_views, n_edges) bytes (0 outside the limits), 256-byte aligned: the device
+ *                    copies of the offsets, the weights and residuals per edge and the adjacency lists.
+ * The call waits for `stream` once, at its end: the host arrays are the caller's again when it returns. */
+enum { RELPOSE_SYNC_MAX_VIEWS = 64, RELPOSE_SYNC_MAX_EDGES = 4096, RELPOSE_SYNC_MAX_ITERATIONS = 100000 };
+enum { RELPOSE_SYNC_USED = 0, RELPOSE_SYNC_BAD_INDEX = 1, RELPOSE_SYNC_SELF_EDGE = 2, RELPOSE_SYNC_BAD_WEIGHT = 3, RELPOSE_SYNC_BAD_POSE = 4 };
+typedef struct RelposePoseSyncArgs {
+    uint32_t struct_size;       /* sizeof(RelposePoseSyncArgs) as the caller compiled it */
+    int32_t n_scenes;
+    int32_t n_views;            /* over all scenes */
+    int32_t n_edges;            /* over all scenes */
+    int32_t n_final;
+    int32_t robust;             /* 1: Geman-McClure, 0: plain least squares */
+    int32_t reserved0, reserved1;
+    const int32_t* view_begin_host;
+    const int32_t* edge_begin_host;
+    const int32_t* src;
+    const int32_t* dst;
+    const double* T;
+    const double* w0;
+    double sigma_r, sigma_t;    /* radians, metres: finite, > 0 */
+    double mu0, div;            /* mu0 >= 1, div > 1 */
+    double* pose;
+    int32_t* component;
+    int32_t* tree;
+    int32_t* edge_state;
+    double* confidence;
+    double* res_rot;
+    double* res_trans;
+    int32_t* n_components;
+    double* cost;
+    double* last_step;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposePoseSyncArgs;
+size_t relpose_pose_sync_workspace(int32_t n_scenes, int32_t n_views, int32_t n_edges);
+int relpose_pose_sync(const RelposePoseSyncArgs* args);
+
 /* -------------------------------------------------------------------- SCNet
  * Replaces SCNet (model/mymodel.py:141-380).  relpose_scnet_create builds the configuration evaluation.py runs
  * (skipLayer=1, batchnorm=1, outputType 'rgbdnsf'); relpose_scnet_create_ex (round 6) the other constructor variants. */

@@ -213,6 +213,18 @@ class TsdfSurfaceArgs(C.Structure):
                 ("valid", c_void_p), ("n_points", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
 
 
+class PoseSyncArgs(C.Structure):
+    """RelposePoseSyncArgs (include/relpose.h): the argument block of relpose_pose_sync."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("n_views", c_int), ("n_edges", c_int), ("n_final", c_int), ("robust", c_int),
+                ("reserved0", c_int), ("reserved1", c_int), ("view_begin_host", c_void_p), ("edge_begin_host", c_void_p), ("src", c_void_p),
+                ("dst", c_void_p), ("T", c_void_p), ("w0", c_void_p), ("sigma_r", c_double), ("sigma_t", c_double), ("mu0", c_double),
+                ("div", c_double), ("pose", c_void_p), ("component", c_void_p), ("tree", c_void_p), ("edge_state", c_void_p),
+                ("confidence", c_void_p), ("res_rot", c_void_p), ("res_trans", c_void_p), ("n_components", c_void_p), ("cost", c_void_p),
+                ("last_step", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
+SYNC_MAX_VIEWS = 64                 # RELPOSE_SYNC_MAX_VIEWS, per scene
+SYNC_MAX_EDGES = 4096               # RELPOSE_SYNC_MAX_EDGES, per scene
 TSDF_MAX_VIEWS = 4096               # per scene per relpose_tsdf_fuse call
 TSDF_MAX_WEIGHT = 65535             # the caller's bound on a voxel's weight across accumulating calls
 
@@ -277,6 +289,8 @@ SIGNATURES = {
     "relpose_tsdf_fuse": (c_int, [C.POINTER(TsdfFuseArgs)]),
     "relpose_tsdf_surface_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "relpose_tsdf_surface": (c_int, [C.POINTER(TsdfSurfaceArgs)]),
+    "relpose_pose_sync_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "relpose_pose_sync": (c_int, [C.POINTER(PoseSyncArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),
     "relpose_scnet_create_ex": (c_void_p, [C.POINTER(SCNetConfig)]),
     "relpose_scnet_destroy": (None, [c_void_p]),

@@ -27,6 +27,7 @@ SOURCES = [
     ("overlap.hip", ["-ffp-contract=off"]),        # overlap statistics: hits and the closest-pair distance must agree with tests/overlap_model.py bit for bit
     ("visibility.hip", ["-ffp-contract=off"]),     # visibility consistency: classes and margins must agree with tests/visibility_model.py bit for bit
     ("tsdf.hip", ["-ffp-contract=off"]),           # TSDF fusion: the integer volume and the surface must agree with tests/tsdf_model.py bit for bit
+    ("posesync.hip", ["-ffp-contract=off"]),       # pose synchronisation: every f64 operation rounds as tests/sync_model.py states it
     ("scnet.hip", []),
 ]
 

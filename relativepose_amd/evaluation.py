@@ -22,6 +22,9 @@ unchanged" is realised by the build's own eval_pairs-style harness).
   fuse_views / reconstruction_scores / fuse_summary / wall_error, evaluate_pairs(fuse=...)
                           no counterpart: the posed views merged into a TSDF volume and its surface cloud, and what a pose error does to
                           it (util.tsdf_fuse_dev / tsdf_surface_dev)
+  synchronize_scene / absolute_pose_errors / evaluate_scenes / scenes_summary
+                          no counterpart: a scene's relative poses synchronised into one pose per view, which pair estimates that
+                          distrusts, and the scene fused under the result (util.pose_graph / pose_sync_dev)
 
 The metrics are host numpy like the reference's (a handful of 3x3 products per pair); overlap and pc_nearest of a batch come from one
 grid-based GPU call (util.point_cloud_overlap_dev), bitwise the values of the per-pair brute-force yardstick
@@ -694,6 +697,144 @@ def _evaluate_baseline(batches, device, dataset, register, result_path, with_col
     return stats
 
 
+def synchronize_scene(pairs, poses, M, weights=None, device=None, **sync):
+    """One scene's relative poses -> one absolute pose per view: util.pose_graph(pairs, poses, weights) builds the edges
+    (several poses per pair become competing edges), util.pose_sync_dev solves (`sync` = its keyword overrides: sigma_r, sigma_t, mu0, div,
+    n_final, robust).  pairs / poses / weights as util.pose_graph's (poses=None: `pairs` are records).
+    -> host arrays {"pose" [M,4,4] world -> camera in each component's gauge, "component" [M], "n_components", "cost", "last_step", and per
+    edge "src", "dst", "pair", "w0", "confidence", "res_rot", "res_trans", "tree", "edge_state"; "pair_confidence" [len(pairs)]: the largest
+    confidence among the pair's edges}."""
+    from . import util
+    src, dst, T, w0, pair = util.pose_graph(pairs, poses, weights)
+    out = util.pose_sync_dev(T, src, dst, w0, np.array([0, int(M)], np.int32), np.array([0, len(src)], np.int32), device=device, **sync)
+    res = {k: v.cpu().numpy() for k, v in out.items()}
+    for k in ("n_components", "cost", "last_step"):
+        res[k] = res[k][0].item()
+    res.update(src=src, dst=dst, pair=pair, w0=w0)
+    pc = np.zeros(len(pairs))
+    np.maximum.at(pc, pair, res["confidence"])
+    res["pair_confidence"] = pc
+    return res
+
+
+def absolute_pose_errors(pose_hat, R, component=None):
+    """Synchronised poses against ground truth: pose_hat [M,4,4] world -> camera in each component's gauge (synchronize_scene's "pose"), R
+    [M,4,4] the loaders' world -> camera poses, component [M] (None: one component whose gauge is view 0).  View k is compared with
+    R_k inv(R_gauge).  -> (rotation error in degrees [M], translation error in metres [M])."""
+    pose_hat, R = np.asarray(pose_hat, np.float64).reshape(-1, 4, 4), np.asarray(R, np.float64).reshape(-1, 4, 4)
+    M = len(R)
+    comp = np.zeros(M, np.int64) if component is None else np.asarray(component).reshape(-1)
+    rot, tr = np.zeros(M), np.zeros(M)
+    for k in range(M):
+        want = np.matmul(R[k], np.linalg.inv(R[comp[k]]))
+        rot[k] = angular_distance_np(pose_hat[k, :3, :3], want[:3, :3])[0]
+        tr[k] = np.linalg.norm(pose_hat[k, :3, 3] - want[:3, 3])
+    return rot, tr
+
+
+SCENE_BAD_ROT, SCENE_BAD_TRANS = 10.0, 0.3       # a pair estimate is wrong beyond 10 degrees or 0.3 m
+
+
+def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, dataset=None, keypoints=200, seed=0, exp=None, **sync):
+    """Scenes of posed views -> estimated pairs -> synchronised absolute poses -> what they do to the reconstruction.
+    scenes: synth.render_scene dicts; pipe_or_method: a RelativePosePipeline, or "fgs" / "gs" / "cgs" (then `dataset` names the scenes').
+    Per scene: mine_pairs, the pair method on the mined pairs through evaluate_pairs / evaluate_fgs / _gs / _cgs as they are (verify and
+    the baselines' overlap rule included: a pair without a record contributes no edge), the graph (util.pose_graph; w0 = the record's
+    vis_agreement where verify gave one, else 1; a selected level that differs from the last enters as a second edge), synchronize_scene.
+    -> one dict per scene: 'views', 'pairs' (mined), 'records' (the pair records, untouched), 'edges', 'n_components', 'component', 'pose'
+    [M,4,4], 'abs_err_rot' / 'abs_err_t' [M] (absolute_pose_errors) with their '_median' and '_max', 'pair_confidence' per record,
+    'downweighted_share' (records with confidence < 0.5), 'bad_share' (records off by more than 10 degrees or 0.3 m), 'bad_downweighted' /
+    'good_downweighted' (the share of each kind that is down-weighted; NaN for an empty kind), 'cost', 'last_step'.
+    fuse=voxel: 'fuse_accuracy' / 'fuse_completeness' (reconstruction_scores of fuse_views of the largest component's views under the
+    synchronised poses against the same fusion under R_k inv(R_gauge)), 'fuse_points', 'fuse_views'; exp: the surface is written to
+    <exp>.scene<k>.ply."""
+    import torch
+    from . import synth, util
+    method = pipe_or_method if isinstance(pipe_or_method, str) else None
+    if method is not None and method not in ("fgs", "gs", "cgs"):
+        raise ValueError("evaluate_scenes takes a RelativePosePipeline or one of 'fgs', 'gs', 'cgs'")
+    ds = dataset if method is not None else pipe_or_method.dataset
+    if ds is None:
+        raise ValueError("evaluate_scenes needs the dataset of the scenes for a baseline method")
+    out = []
+    for k, sc in enumerate(scenes):
+        M = len(sc["depth"])
+        entries = mine_pairs(sc["depth"], sc["R"], ds, f"scene{k}", device=device)
+        ij = [(e['id_src'], e['id_tgt']) for e in entries]
+        recs = []
+        if ij:
+            sel = lambda key: np.stack([sc[key][[i, j]] for i, j in ij])
+            batch = {key: sel(key) for key in ("rgb", "norm", "depth", "R")}
+            if method is None:
+                h = sc["depth"].shape[1]
+                kps = [synth.make_keypoints(1, keypoints, 7919 * (seed + 131 * k + b) + 13, pipe_or_method.mask_method, h=h) for b in range(len(ij))]
+                batch["pts"], batch["ptw"] = np.concatenate([p[0] for p in kps]), np.concatenate([p[1] for p in kps])
+            parts = [{key: v[b0:b0 + 32] for key, v in batch.items()} for b0 in range(0, len(ij), 32)]      # 32 pairs per batch of the pair method
+            if method is None:
+                recs = evaluate_pairs(pipe_or_method, parts, device, verify=verify)
+            else:
+                recs = {"fgs": evaluate_fgs, "gs": evaluate_gs, "cgs": evaluate_cgs}[method](parts, device, ds, verify=verify)
+        gts = [np.matmul(sc["R"][j], np.linalg.inv(sc["R"][i])) for i, j in ij]       # a record's pair: the one with its R_gt
+        pair_of = []
+        for r in recs:
+            d = [np.abs(g - r['R_gt']).max() for g in gts]
+            pair_of.append(int(np.argmin(d)))
+        poses, weights = [], []
+        for r in recs:
+            P = [r['R_pred_44']]
+            if 'R_pred_44_selected' in r and not np.array_equal(r['R_pred_44_selected'], r['R_pred_44']):
+                P.append(r['R_pred_44_selected'])
+            poses.append(np.stack(P))
+            weights.append(r.get('vis_agreement', 1.0))
+        sy = synchronize_scene([ij[p] for p in pair_of], poses, M, weights, device=device, **sync)
+        rot, tr = absolute_pose_errors(sy["pose"], sc["R"], sy["component"])
+        conf = sy["pair_confidence"]
+        bad = np.array([r['err_ad'] > SCENE_BAD_ROT or r['err_t'] > SCENE_BAD_TRANS for r in recs], bool)
+        down = conf < 0.5
+        share = lambda m: float(down[m].mean()) if m.any() else float("nan")
+        rec = {'scene': k, 'views': M, 'pairs': len(ij), 'records': recs, 'edges': len(sy["src"]), 'n_components': sy["n_components"],
+               'component': sy["component"], 'pose': sy["pose"], 'abs_err_rot': rot, 'abs_err_t': tr,
+               'abs_err_rot_median': float(np.median(rot)) if M else float("nan"), 'abs_err_rot_max': float(rot.max()) if M else float("nan"),
+               'abs_err_t_median': float(np.median(tr)) if M else float("nan"), 'abs_err_t_max': float(tr.max()) if M else float("nan"),
+               'pair_confidence': conf, 'downweighted_share': float(down.mean()) if len(recs) else float("nan"),
+               'bad_share': float(bad.mean()) if len(recs) else float("nan"), 'bad_downweighted': share(bad), 'good_downweighted': share(~bad),
+               'cost': sy["cost"], 'last_step': sy["last_step"]}
+        if fuse is not None and M:
+            comp = sy["component"]
+            g = int(np.bincount(comp, minlength=M).argmax())
+            views = np.nonzero(comp == g)[0]
+            up = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(device)
+            depth = up(sc["depth"][views])
+            rgb = up(sc["rgb"][views]) if exp is not None else None
+            inv_g = np.linalg.inv(sc["R"][g])
+            est = fuse_views(depth, rgb, sy["pose"][views], ds, fuse)
+            ref = fuse_views(depth, None, np.stack([np.matmul(sc["R"][v], inv_g) for v in views]), ds, fuse)
+            acc, cmp_ = reconstruction_scores(est, ref)
+            n = int(est["n_points"][0].item())
+            rec.update(fuse_accuracy=float(acc[0]), fuse_completeness=float(cmp_[0]), fuse_points=n, fuse_views=len(views))
+            if exp is not None:
+                rec['fuse_ply'] = f"{exp}.scene{k}.ply"
+                util.save_ply(rec['fuse_ply'], est["points"][0, :n], est["normals"][0, :n], est["colors"][0, :n])
+        out.append(rec)
+    return out
+
+
+def scenes_summary(recs):
+    """What the CLI reports about evaluate_scenes' records: medians over the scenes and the down-weighting shares over all pair records."""
+    med = lambda v: float(np.nanmedian(v)) if len(v) and not np.all(np.isnan(v)) else float("nan")
+    conf = np.concatenate([r['pair_confidence'] for r in recs]) if recs else np.zeros(0)
+    bad = np.array([p['err_ad'] > SCENE_BAD_ROT or p['err_t'] > SCENE_BAD_TRANS for r in recs for p in r['records']], bool)
+    share = lambda m: float((conf[m] < 0.5).mean()) if m.any() else float("nan")
+    out = {"abs_err_rot_median": med([r['abs_err_rot_median'] for r in recs]), "abs_err_rot_max": med([r['abs_err_rot_max'] for r in recs]),
+           "abs_err_t_median": med([r['abs_err_t_median'] for r in recs]), "abs_err_t_max": med([r['abs_err_t_max'] for r in recs]),
+           "pair_records": int(len(conf)), "bad_share": float(bad.mean()) if len(bad) else float("nan"),
+           "bad_downweighted": share(bad), "good_downweighted": share(~bad), "components_max": max([r['n_components'] for r in recs] or [0])}
+    if recs and 'fuse_accuracy' in recs[0]:
+        out.update(fuse_accuracy_median=med([r['fuse_accuracy'] for r in recs]), fuse_completeness_median=med([r['fuse_completeness'] for r in recs]),
+                   fuse_points=int(sum(r['fuse_points'] for r in recs)), fuse_ply=[r['fuse_ply'] for r in recs if 'fuse_ply' in r])
+    return out
+
+
 def evaluate_descriptors(batches, net, device, dataset, mask_method, seed=0, n_eval=100, sift_baseline=False, **corres):
     """The reference's descriptor metric (evalDLDescriptor, mainPanoCompletion2view.py:383-414) over batches of pairs with ground-truth
     poses: per batch the level-0 forward the pipeline builds (masked own view, zero warped view), the descriptor = the feature channels
@@ -1009,6 +1150,12 @@ def _cli_parser_completion():
                          "and fuse_points, the JSON line their medians and fuse_spearman_rot (rank correlation of fuse_accuracy with err_ad).  "
                          "--mine-pairs --fuse: each scene's views are fused under the ground-truth poses; the line gains fuse_wall_err_median / "
                          "_p90 (voxels, against the room's walls) and fuse_points, and <exp>.scene<k>.ply is written when --exp is given")
+    ap.add_argument("--reconstruct", action="store_true",
+                    help="--method ours / fgs / gs / cgs on --scenes scenes of --scene-views views (synth.render_scene, seeds --seed, --seed + 1, "
+                         "...): mine each scene's pairs, estimate them, synchronise the relative poses into one pose per view "
+                         "(util.pose_sync_dev, DESIGN.md 4.17) and print one JSON line with the absolute pose errors, the share of wrong pair "
+                         "estimates that were down-weighted and, with --fuse, the reconstruction scores of the scenes fused under the "
+                         "synchronised poses; --verify observed weights the edges by vis_agreement; --exp writes <exp>.scene<k>.ply")
     return ap
 
 
@@ -1043,6 +1190,41 @@ def main(argv=None):
             raise SystemExit("--fuse takes a voxel size > 0")
         if args.gpus > 1 or (not args.mine_pairs and args.method == "ours" and args.keypoint_mode != "given"):
             raise SystemExit("--fuse runs on one GPU (--gpus 1) with given keypoints: the fusion is not sharded")
+
+    if args.reconstruct:
+        if args.mine_pairs or args.descriptor_eval or args.completion_eval or args.from_frames or args.pair_source != "pairs":
+            raise SystemExit("--reconstruct is a mode of its own: it mines, estimates and synchronises the pairs of its scenes")
+        if args.gpus > 1 or args.keypoint_mode != "given":
+            raise SystemExit("--reconstruct runs on one GPU (--gpus 1) with given keypoints: it is not sharded over ranks")
+        if args.scenes < 1 or args.scene_views < 2 or args.scene_views > 64:
+            raise SystemExit("--reconstruct takes --scenes >= 1 and 2 <= --scene-views <= 64")
+        if args.method != "ours" and args.dataset == "scannet":
+            raise SystemExit(f"--method {args.method}: the synthetic ScanNet views have no full-resolution depth, which the reference's baselines use")
+        import torch
+        from . import _lib, synth
+        dev = _lib.require_gpu()
+        ds = args.dataset
+        who = args.method
+        if args.method == "ours":
+            from types import SimpleNamespace
+            from . import params, weights
+            from .model import SCNet
+            from .pipeline import RelativePosePipeline
+            mm, S, tanh = ("kinect", 21, 0) if ds == "scannet" else ("second", 21 if ds == "matterport" else 15, 1)
+            net = SCNet(SimpleNamespace(batchnorm=1, useTanh=tanh, skipLayer=1, outputType="rgbdnsf", snumclass=S))
+            net.load_state_dict(weights.make_state_dict(7, S))
+            net.set_precision(args.precision)
+            who = RelativePosePipeline(net, ds, mm, params.final_params(ds), completion=args.completion)
+        t0 = time.perf_counter()
+        scenes = [synth.render_scene(args.seed + s, args.scene_views, ds) for s in range(args.scenes)]
+        recs = evaluate_scenes(who, scenes, dev, verify=args.verify, fuse=args.fuse, dataset=ds, keypoints=args.keypoints, seed=args.seed,
+                               exp=args.exp)
+        torch.cuda.synchronize()
+        line = {"reconstruct": True, "method": args.method, "dataset": ds, "scenes": args.scenes, "views": args.scene_views,
+                "seconds": time.perf_counter() - t0, "verify": args.verify, "fuse": args.fuse}
+        line.update(scenes_summary(recs))
+        print(json.dumps(line), flush=True)
+        return
 
     if args.mine_pairs:
         if args.gpus > 1:

@@ -43,6 +43,7 @@ Operator                    replaces (reference file:line)
   overlap                   the two KDTree queries of util.point_cloud_overlap, util.py:21-40 (batched over directed cloud pairs, one grid per cloud)
   visibility                no counterpart: the free-space check of a relative pose against the partner's depth panorama
   tsdf_fuse, tsdf_surface   no counterpart: posed depth panoramas merged into a TSDF volume and its surface cloud
+  pose_sync                 no counterpart: the relative poses of a scene's pairs synchronised into one pose per view
   affinity_topk             rpmodule.py:342-379
   match_pairs               RelativePoseEstimation_helper, rpmodule.py:317-508
 """
@@ -118,6 +119,12 @@ _lib.define("tsdf_fuse(Tensor depth, Tensor? rgb, Tensor pose, Tensor view_begin
 # n_points i32 [S]
 _lib.define("tsdf_surface(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Tensor origin, float voxel, int min_weight=1, "
             "int max_points=65536) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
+# T f64 [E,4,4], src / dst integer [E] (local to the scene), w0 f64 [E], view_begin / edge_begin integer [S+1] (read on the host), n_views =
+# view_begin[-1] (an argument so that the Meta function knows the shapes) -> pose f64 [V,4,4],
+# component i32 [V], tree, edge_state i32 [E], confidence, res_rot, res_trans f64 [E], n_components i32 [S], cost, last_step f64 [S]
+_lib.define("pose_sync(Tensor T, Tensor src, Tensor dst, Tensor w0, Tensor view_begin, Tensor edge_begin, int n_views, float sigma_r=0.1, float sigma_t=0.1, "
+            "float mu0=64.0, float div=1.4, int n_final=10, bool robust=True) "
+            "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 _lib.define("affinity_topk(Tensor feat_s, Tensor weight_s, Tensor feat_t, Tensor weight_t, Tensor ns, Tensor nt, "
             "float[] params, int topK, bool want_wij) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("match_pairs(Tensor pc_s, Tensor normal_s, Tensor feat_s, Tensor weight_s, Tensor pc_t, Tensor normal_t, "
@@ -288,6 +295,17 @@ def _tsdf_surface(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_
     return points, normals, (tsdf_sum.new_empty(0, dtype=torch.float32) if colors is None else colors), valid, n
 
 
+POSE_SYNC_OUTPUTS = ("pose", "component", "tree", "edge_state", "confidence", "res_rot", "res_trans", "n_components", "cost", "last_step")
+
+
+def _pose_sync(T, src, dst, w0, view_begin, edge_begin, n_views, sigma_r=0.1, sigma_t=0.1, mu0=64.0, div=1.4, n_final=10, robust=True):
+    if int(view_begin[-1]) != int(n_views):
+        raise ValueError("pose_sync: n_views is not view_begin's last entry")
+    out =_util.pose_sync_dev(T, src, dst, w0, view_begin, edge_begin, float(sigma_r), float(sigma_t), float(mu0), float(div), int(n_final),
+                              bool(robust))
+    return tuple(out[k] for k in POSE_SYNC_OUTPUTS)
+
+
 def _affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     wij, cj, cw, keff = _rp.affinity_topk(feat_s.contiguous(), weight_s.contiguous(), feat_t.contiguous(), weight_t.contiguous(),
                                           ns.contiguous(), nt.contiguous(), _para(params, topK), want_wij=bool(want_wij))
@@ -311,7 +329,7 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank),
                    ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals),
                    ("frames_to_pano", _frames_to_pano), ("overlap", _overlap), ("visibility", _visibility),
-                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface)):
+                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("pose_sync", _pose_sync)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -459,6 +477,12 @@ def _m_tsdf_surface(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, ma
             tsdf_sum.new_empty(S, cap, dtype=torch.uint8), tsdf_sum.new_empty(S, dtype=torch.int32))
 
 
+def _m_pose_sync(T, src, dst, w0, view_begin, edge_begin, n_views, sigma_r=0.1, sigma_t=0.1, mu0=64.0, div=1.4, n_final=10, robust=True):
+    E, S, V = T.shape[0], view_begin.shape[0] - 1, int(n_views)
+    f64, i32 = (lambda *s: T.new_empty(*s, dtype=torch.float64)), (lambda *s: T.new_empty(*s, dtype=torch.int32))
+    return f64(V, 4, 4), i32(V), i32(E), i32(E), f64(E), f64(E), f64(E), i32(S), f64(S), f64(S)
+
+
 def _m_affinity_topk(feat_s, weight_s, feat_t, weight_t, ns, nt, params, topK, want_wij):
     B, ns_max, nt_max = feat_s.shape[0], feat_s.shape[1], feat_t.shape[1]
     wij = feat_s.new_empty(B, ns_max, nt_max, dtype=torch.float32) if want_wij else feat_s.new_empty(0)
@@ -479,10 +503,10 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank),
                    ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals),
                    ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap), ("visibility", _m_visibility),
-                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface)):
+                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("pose_sync", _m_pose_sync)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
        "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals",
-       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface")
+       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "pose_sync")

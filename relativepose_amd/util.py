@@ -761,6 +761,88 @@ def tsdf_bounds_dev(depth, R, dataset, voxel, pad=3, view_begin=None):
     return origin, tuple(int(v) for v in dims)
 
 
+def pose_sync_dev(T, src, dst, w0, view_begin, edge_begin, sigma_r=0.1, sigma_t=0.1, mu0=64.0, div=1.4, n_final=10, robust=True, device=None):
+    """relpose_pose_sync (include/relpose.h): the relative poses of S scenes' view pairs -> one absolute pose per view and one
+    confidence per relative pose.  T [E,4,4] f64 (T ~ R_dst inv(R_src) for world -> camera R: what the pair drivers produce), src / dst [E]
+    view indices local to the scene, w0 [E] f64 prior weights: host arrays or CUDA tensors; view_begin / edge_begin: S + 1 ascending offsets
+    (read on the host; at most 64 views and 4096 edges per scene).
+    -> {"pose" [V,4,4] f64 in each component's gauge (its smallest view = identity), "component" [V] i32 (local), "tree", "edge_state" [E]
+    i32, "confidence", "res_rot", "res_trans" [E] f64, "n_components" [S] i32, "cost", "last_step" [S] f64} CUDA tensors.  One launch; the
+    call waits for the stream once."""
+    import torch
+    dev = device if device is not None else next((t.device for t in (T, src, dst, w0) if hasattr(t, "data_ptr") and t.is_cuda), None)
+    dev = torch.device(dev) if dev is not None else _lib.require_gpu()
+    _lib.require_gpu()
+
+    def put(v, dt, npdt, tail):
+        t = v if hasattr(v, "data_ptr") else torch.from_numpy(np.ascontiguousarray(v, dtype=npdt))
+        return t.to(device=dev, dtype=dt).reshape((t.numel() // int(np.prod(tail, dtype=np.int64)),) + tail).contiguous()
+
+    Td = put(T, torch.float64, np.float64, (4, 4))
+    E = int(Td.shape[0])
+    sd, dd, wd = put(src, torch.int32, np.int32, ()), put(dst, torch.int32, np.int32, ()), put(w0, torch.float64, np.float64, ())
+    host = lambda v: np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.int32).reshape(-1)
+    vb, eb = host(view_begin), host(edge_begin)
+    S = len(vb) - 1
+    if S < 1 or len(eb) != S + 1 or sd.numel() != E or dd.numel() != E or wd.numel() != E:
+        raise ValueError("pose_sync_dev takes view_begin and edge_begin [S + 1] with S >= 1 and one src, dst, T and w0 per edge")
+    V = int(vb[-1])
+    L = _lib.lib()
+    nbytes = L.relpose_pose_sync_workspace(S, V, E)
+    if nbytes == 0 or int(eb[-1]) != E:
+        raise ValueError("pose_sync_dev: sizes outside relpose_pose_sync's limits (64 views and 4096 edges per scene), or edge_begin does not end at E")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+    out = {"pose": f64(V, 4, 4), "component": i32(V), "tree": i32(E), "edge_state": i32(E), "confidence": f64(E), "res_rot": f64(E),
+           "res_trans": f64(E), "n_components": i32(S), "cost": f64(S), "last_step": f64(S)}
+    pad = f64(16)                                                  # an empty tensor has no address: the entry is never read or written
+    addr = lambda t: t.data_ptr() if t.numel() else pad.data_ptr()
+    a = _lib.PoseSyncArgs()
+    a.struct_size = _lib.C.sizeof(_lib.PoseSyncArgs)
+    a.n_scenes, a.n_views, a.n_edges, a.n_final, a.robust = S, V, E, int(n_final), int(bool(robust))
+    a.view_begin_host, a.edge_begin_host = vb.ctypes.data, eb.ctypes.data
+    a.src, a.dst, a.T, a.w0 = addr(sd), addr(dd), addr(Td), addr(wd)
+    a.sigma_r, a.sigma_t, a.mu0, a.div = float(sigma_r), float(sigma_t), float(mu0), float(div)
+    for k, t in out.items():
+        setattr(a, k, addr(t))
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    with torch.cuda.device(dev):
+        a.stream = _lib.stream_ptr()
+        rc_ = L.relpose_pose_sync(_lib.C.byref(a))
+    if rc_ == -1:
+        raise ValueError("relpose_pose_sync: invalid arguments (offsets not ascending from 0, more than 64 views or 4096 edges in a scene, "
+                         "sigma not > 0, div not > 1, mu0 < 1, n_final < 0, or more than 100000 iterations)")
+    _lib.check(rc_, "relpose_pose_sync")
+    return out
+
+
+def pose_graph(pairs, poses, weights=None):
+    """The edge arrays of ONE scene for pose_sync_dev (host code).  pairs: [(src, dst)] view indices, one per estimated pair -- or a list of
+    records (dicts with "src", "dst", "pose" or "poses", and optionally "vis_agreement"), in which case `poses` is None.  poses: per pair one
+    4x4 pose T ~ R_dst inv(R_src) or several [K,4,4] (the levels of a recurrence, or several methods' estimates): every pose becomes an edge
+    of its own, so competing hypotheses for a pair meet in the graph.  weights: per pair a scalar or one value per pose; default the
+    record's "vis_agreement" where present and finite and > 0, otherwise 1.
+    -> (src [E] i32, dst [E] i32, T [E,4,4] f64, w0 [E] f64, pair [E] i32: the index of the edge's pair)."""
+    if poses is None:
+        recs = list(pairs)
+        pairs = [(int(r["src"]), int(r["dst"])) for r in recs]
+        poses = [r["poses"] if "poses" in r else r["pose"] for r in recs]
+        if weights is None:
+            weights = [r.get("vis_agreement", 1.0) for r in recs]
+    if len(poses) != len(pairs) or (weights is not None and len(weights) != len(pairs)):
+        raise ValueError("pose_graph takes one pose (or stack of poses) and one weight per pair")
+    src, dst, T, w0, pair = [], [], [], [], []
+    for k, (i, j) in enumerate(pairs):
+        P = np.asarray(poses[k], dtype=np.float64).reshape(-1, 4, 4)
+        w = np.ones(len(P)) if weights is None or weights[k] is None else np.broadcast_to(np.asarray(weights[k], dtype=np.float64), (len(P),))
+        for n in range(len(P)):
+            src.append(int(i)); dst.append(int(j)); T.append(P[n]); pair.append(k)
+            w0.append(float(w[n]) if np.isfinite(w[n]) and w[n] > 0 else 1.0)
+    return (np.array(src, np.int32).reshape(-1), np.array(dst, np.int32).reshape(-1), np.array(T, np.float64).reshape(-1, 4, 4),
+            np.array(w0, np.float64).reshape(-1), np.array(pair, np.int32).reshape(-1))
+
+
 def save_ply(path, points, normals=None, colors=None):
     """Write a binary little-endian PLY point cloud: points [N,3] (float32 x y z in the file), normals [N,3] (nx ny nz) and colors [N,3] in
     [0, 1] (uchar red green blue) if given; arrays or tensors.  Returns N."""
