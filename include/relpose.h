@@ -1068,6 +1068,60 @@ typedef struct RelposeTsdfSurfaceArgs {
 size_t relpose_tsdf_surface_workspace_bytes(int32_t n_scenes, int32_t nx, int32_t ny, int32_t nz);
 int relpose_tsdf_surface(const RelposeTsdfSurfaceArgs* args);
 
+/* One indexed triangle mesh per scene from relpose_tsdf_fuse's state: marching cubes (tests/mesh_model.py restates the
+ * contract in numpy).  The crossings relpose_tsdf_surface emits are exactly the vertices of such a mesh; this call adds the triangles.
+ *   vertices         points, normals, colors, valid, n_points with capacity cap: in content and order exactly what relpose_tsdf_surface
+ *                    writes for the same state, min_weight, origin, voxel and cap.  A vertex that no triangle uses is kept (its edge
+ *                    touches no complete cell).
+ *   cells            cell (i, j, k), i < nx-1, j < ny-1, k < nz-1, contributes iff all eight corner voxels are known.  Corner c (0..7) sits
+ *                    at offset (c & 1, c >> 1 & 1, c >> 2 & 1); case = the mask with bit c set iff t(corner c) < 0.  Edge 4a + u + 2v runs
+ *                    along axis a from the corner whose offsets on the other two axes, ascending, are (u, v); its vertex is the crossing
+ *                    that corner's voxel owns on axis a, and that vertex's index is the index of the voxel's first crossing plus the
+ *                    number of lower axes on which the voxel has one.
+ *   table            per case a list of at most 5 triangles of edge ids, generated by tools/gen_mc_table.py into csrc/mc_table.h from a
+ *                    face rule: on each cube face, corners counter-clockwise seen from outside, every maximal run of negative corners
+ *                    gives one directed segment from the crossing edge that enters the run to the one that leaves it; the segments
+ *                    close into loops (ordered by smallest edge id); each loop is a fan from the vertex with the fewest in-face fan
+ *                    diagonals (ties: smallest edge id).  Two cells sharing a face draw the same segments on it: the mesh has no holes
+ *                    between cells, and (p1 - p0) x (p2 - p0) points where t grows, as the normals do.
+ *   triangles        [n_scenes, cap_tri, 3] i32 indices into the scene's vertex list; cells in ascending linear index (x fastest), within a
+ *                    cell in the table's order.  n_triangles [n_scenes] i32 may exceed cap_tri: only the first cap_tri are written, rows
+ *                    beyond are not touched.  The indices are the true vertex indices even where they are >= cap: the CALLER checks
+ *                    n_points <= cap before using the mesh.  Where t == 0 at a corner several vertices coincide and a triangle has zero
+ *                    area; it is kept, and its three indices are still distinct.
+ *   limits           relpose_tsdf_surface's, and 5 (nx-1) (ny-1) (nz-1) < 2^31; 1 <= cap_tri; n_scenes * cap_tri < 2^29.  A volume with a
+ *                    dimension of 1 has no cells and no triangles.
+ *   workspace        relpose_tsdf_mesh_workspace_bytes(n_scenes, nx, ny, nz) bytes (0 for sizes outside the limits), 256-byte aligned: both
+ *                    counts per workgroup, the device copy of origin, and per voxel the index of its first vertex and one flag byte
+ * No atomics: a scene's result is bitwise repeatable and independent of the batch around it.  Invalid arguments return RELPOSE_EINVAL
+ * before anything is enqueued or any output is touched.  Four launches: count, scan, vertices, triangles.  The call waits for `stream`
+ * once, at its end. */
+typedef struct RelposeTsdfMeshArgs {
+    uint32_t struct_size;       /* sizeof(RelposeTsdfMeshArgs) as the caller compiled it */
+    int32_t n_scenes;
+    int32_t nx, ny, nz;
+    int32_t min_weight;
+    int32_t cap;
+    int32_t cap_tri;
+    const int32_t* tsdf_sum;
+    const int32_t* weight;
+    const uint32_t* color_sum;
+    const double* origin_host;
+    double voxel;
+    double* points;
+    double* normals;
+    float* colors;
+    uint8_t* valid;
+    int32_t* n_points;
+    int32_t* triangles;
+    int32_t* n_triangles;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeTsdfMeshArgs;
+size_t relpose_tsdf_mesh_workspace_bytes(int32_t n_scenes, int32_t nx, int32_t ny, int32_t nz);
+int relpose_tsdf_mesh(const RelposeTsdfMeshArgs* args);
+
 /* -------------------------------------------------------------------- robust synchronisation of pose graphs
  * The pair drivers give a relative pose per pair of views; some are grossly wrong.  relpose_pose_sync turns the relative poses of n_scenes
  * scenes into one absolute pose per view and one confidence per relative pose: graduated Geman-McClure re-weighting around a linearised

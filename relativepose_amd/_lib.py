@@ -213,6 +213,15 @@ class TsdfSurfaceArgs(C.Structure):
                 ("valid", c_void_p), ("n_points", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
 
 
+class TsdfMeshArgs(C.Structure):
+    """RelposeTsdfMeshArgs (include/relpose.h): the argument block of relpose_tsdf_mesh."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("nx", c_int), ("ny", c_int), ("nz", c_int), ("min_weight", c_int),
+                ("cap", c_int), ("cap_tri", c_int), ("tsdf_sum", c_void_p), ("weight", c_void_p), ("color_sum", c_void_p),
+                ("origin_host", c_void_p), ("voxel", c_double), ("points", c_void_p), ("normals", c_void_p), ("colors", c_void_p),
+                ("valid", c_void_p), ("n_points", c_void_p), ("triangles", c_void_p), ("n_triangles", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
 class PoseSyncArgs(C.Structure):
     """RelposePoseSyncArgs (include/relpose.h): the argument block of relpose_pose_sync."""
     _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("n_views", c_int), ("n_edges", c_int), ("n_final", c_int), ("robust", c_int),
@@ -289,6 +298,8 @@ SIGNATURES = {
     "relpose_tsdf_fuse": (c_int, [C.POINTER(TsdfFuseArgs)]),
     "relpose_tsdf_surface_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "relpose_tsdf_surface": (c_int, [C.POINTER(TsdfSurfaceArgs)]),
+    "relpose_tsdf_mesh_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "relpose_tsdf_mesh": (c_int, [C.POINTER(TsdfMeshArgs)]),
     "relpose_pose_sync_workspace": (c_size_t, [c_int, c_int, c_int]),
     "relpose_pose_sync": (c_int, [C.POINTER(PoseSyncArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),

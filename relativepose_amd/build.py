@@ -27,6 +27,7 @@ SOURCES = [
     ("overlap.hip", ["-ffp-contract=off"]),        # overlap statistics: hits and the closest-pair distance must agree with tests/overlap_model.py bit for bit
     ("visibility.hip", ["-ffp-contract=off"]),     # visibility consistency: classes and margins must agree with tests/visibility_model.py bit for bit
     ("tsdf.hip", ["-ffp-contract=off"]),           # TSDF fusion: the integer volume and the surface must agree with tests/tsdf_model.py bit for bit
+    ("mesh.hip", ["-ffp-contract=off"]),           # marching cubes: the vertices are tsdf.hip's surface bit for bit (tsdf_surf.h), the triangles tests/mesh_model.py's
     ("posesync.hip", ["-ffp-contract=off"]),       # pose synchronisation: every f64 operation rounds as tests/sync_model.py states it
     ("scnet.hip", []),
 ]

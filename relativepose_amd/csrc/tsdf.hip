@@ -13,6 +13,8 @@
 //   tsdf_scan_kernel      one workgroup per scene: the exclusive scan of the workgroups' counts in place, and the scene's total.
 //   tsdf_write_kernel     the count pass again, an ordered scan inside the workgroup, and the points, normals and colours of the first
 //                         `cap` crossings; its threads also write `valid`.
+// The surface's device code (a voxel's value and gradient, its crossings, the scan and the write body) stands in tsdf_surf.h, which
+// mesh.hip shares: relpose_tsdf_mesh's vertices are this cloud bit for bit.
 // Every loop has a bound known at launch.
 #include <hip/hip_runtime.h>
 
@@ -25,15 +27,16 @@
 #include "cloud_prims.h"
 #include "common.h"
 #include "skybox.h"
+#include "tsdf_surf.h"
 
 namespace {
 
-constexpr int kTile = 256;                       // voxels per workgroup
+constexpr int kTile = kTsdfTile;                 // voxels per workgroup
 constexpr int kChunk = 32;                       // views whose poses are in LDS at a time
-constexpr int kScanThreads = 1024;
+constexpr int kScanThreads = kTsdfScanThreads;
 constexpr int kMaxViews = 4096;                  // per scene per call: 4096 * 32768 = 2^27 fits the int a thread sums in
 constexpr double kMaxDepth = 32768.0;            // visibility.hip's: a voxel at or beyond it is outside the view
-constexpr double kFix = 32768.0;                 // tsdf_sum counts t in 1 / 32768
+constexpr double kFix = kTsdfFix;
 
 struct FuseBufs {
     int h, dataset, nx, ny, accumulate;
@@ -47,22 +50,6 @@ struct FuseBufs {
     int* tsdf;                                   // [S, nz, ny, nx]
     int* weight;
     unsigned* color;                             // [S, 3, nz, ny, nx] or NULL
-};
-
-struct SurfBufs {
-    int nx, ny, nz, min_weight, cap;
-    unsigned nvox, nblk;
-    double voxel;
-    const int* tsdf;
-    const int* weight;
-    const unsigned* color;                       // or NULL
-    const double* origin;                        // [S, 3] device copy
-    double* points;                              // [S, cap, 3]
-    double* normals;
-    float* colors;                               // [S, cap, 3] or NULL
-    uint8_t* valid;                              // [S, cap]
-    int* n_points;                               // [S]
-    int* blk;                                    // [S, nblk]: the workgroups' counts, then their exclusive scan
 };
 
 __device__ __forceinline__ bool depth_ok(float z) { return z > 0.0f && z <= FLT_MAX; }      // not 0, negative, NaN or inf
@@ -144,43 +131,6 @@ __global__ __launch_bounds__(kTile) void tsdf_fuse_kernel(FuseBufs b) {
 }
 
 // ------------------------------------------------------------------------------------------------------- 2. surface
-// t of voxel (i, j, k) of the scene whose first voxel is `base`; false for a voxel outside the volume or below min_weight
-__device__ __forceinline__ bool tsdf_value(const SurfBufs& b, size_t base, int i, int j, int k, double& t, unsigned& local) {
-    if (i < 0 || i >= b.nx || j < 0 || j >= b.ny || k < 0 || k >= b.nz) return false;
-    local = ((unsigned)k * (unsigned)b.ny + (unsigned)j) * (unsigned)b.nx + (unsigned)i;
-    const int w = b.weight[base + local];
-    if (w < b.min_weight) return false;
-    t = (double)b.tsdf[base + local] / (kFix * (double)w);
-    return true;
-}
-
-// central differences where both neighbours are known, one-sided where one is, 0 where none is
-__device__ __forceinline__ void tsdf_gradient(const SurfBufs& b, size_t base, int i, int j, int k, double t, double g[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int di = c == 0, dj = c == 1, dk = c == 2;
-        double tp = 0.0, tm = 0.0;
-        unsigned l;
-        const bool kp = tsdf_value(b, base, i + di, j + dj, k + dk, tp, l), km = tsdf_value(b, base, i - di, j - dj, k - dk, tm, l);
-        g[c] = kp && km ? (tp - tm) * 0.5 : (kp ? tp - t : (km ? t - tm : 0.0));
-    }
-}
-
-// the crossings of voxel e with its positive-axis neighbours as a 3-bit mask (bit = axis)
-__device__ __forceinline__ int tsdf_crossings(const SurfBufs& b, size_t base, bool in, int i, int j, int k, double& ta, double tb[3]) {
-    int mask = 0;
-    unsigned l;
-    if (in && tsdf_value(b, base, i, j, k, ta, l)) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            tb[c] = 0.0;
-            if (tsdf_value(b, base, i + (c == 0), j + (c == 1), k + (c == 2), tb[c], l) && ((ta >= 0 && tb[c] < 0) || (ta < 0 && tb[c] >= 0)))
-                mask |= 1 << c;
-        }
-    }
-    return mask;
-}
-
 __global__ __launch_bounds__(kTile) void tsdf_count_kernel(SurfBufs b) {
     __shared__ int s_wsum[16];
     const unsigned s = blockIdx.x / b.nblk, blk = blockIdx.x - s * b.nblk;
@@ -196,88 +146,23 @@ __global__ __launch_bounds__(kTile) void tsdf_count_kernel(SurfBufs b) {
 __global__ __launch_bounds__(kScanThreads) void tsdf_scan_kernel(SurfBufs b) {
     __shared__ int s_wsum[16];
     const unsigned s = blockIdx.x;
-    int* cnt = b.blk + (size_t)s * b.nblk;
-    int run = 0;
-    for (unsigned b0 = 0; b0 < b.nblk; b0 += kScanThreads) {         // nblk is the call's
-        const unsigned x = b0 + threadIdx.x;
-        const int v = x < b.nblk ? cnt[x] : 0;
-        int total;
-        const int ex = rp_block_excl_scan(v, s_wsum, total);
-        if (x < b.nblk) cnt[x] = run + ex;
-        run += total;
-    }
+    const int run = tsdf_scan_counts(b.blk + (size_t)s * b.nblk, b.nblk, s_wsum);
     if (threadIdx.x == 0) b.n_points[s] = run;                       // <= 3 nvox < 2^31
 }
 
 __global__ __launch_bounds__(kTile) void tsdf_write_kernel(SurfBufs b) {
     __shared__ int s_wsum[16];
-    const unsigned s = blockIdx.x / b.nblk, blk = blockIdx.x - s * b.nblk;
-    const unsigned e = blk * kTile + threadIdx.x;
-    const unsigned iu = e % (unsigned)b.nx, r = e / (unsigned)b.nx;
-    const int i = (int)iu, j = (int)(r % (unsigned)b.ny), k = (int)(r / (unsigned)b.ny);
-    const size_t base = (size_t)s * b.nvox;
-    const int cap = b.cap, n = b.n_points[s];
-    for (unsigned x = e; x < (unsigned)cap; x += b.nblk * kTile) b.valid[(size_t)s * cap + x] = (uint8_t)((int)x < n);
-    double ta = 0.0, tb[3];
-    const int mask = tsdf_crossings(b, base, e < b.nvox, i, j, k, ta, tb);
-    int total;
-    int off = b.blk[(size_t)s * b.nblk + blk] + rp_block_excl_scan(__popc(mask), s_wsum, total);
-    if (!mask) return;                                               // (no barrier follows)
-    const double* org = b.origin + 3 * s;
-    const double ctr[3] = {org[0] + ((double)i + 0.5) * b.voxel, org[1] + ((double)j + 0.5) * b.voxel, org[2] + ((double)k + 0.5) * b.voxel};
-    double ga[3];
-    tsdf_gradient(b, base, i, j, k, ta, ga);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (!(mask >> c & 1)) continue;
-        const int o = off++;
-        if (o >= cap) continue;
-        const int bi = i + (c == 0), bj = j + (c == 1), bk = k + (c == 2);
-        const double sc = ta / (ta - tb[c]);
-        double gb[3];
-        tsdf_gradient(b, base, bi, bj, bk, tb[c], gb);
-        double nv[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) nv[a] = ga[a] + sc * (gb[a] - ga[a]);
-        const double nn = sqrt((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
-        const int idx = c == 0 ? i : (c == 1 ? j : k);
-        double* pt = b.points + ((size_t)s * cap + o) * 3;
-        double* nm = b.normals + ((size_t)s * cap + o) * 3;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            pt[a] = a == c ? org[a] + (((double)idx + 0.5) + sc) * b.voxel : ctr[a];
-            nm[a] = nn > 0.0 ? nv[a] / nn : nv[a];
-        }
-        if (b.colors) {
-            const unsigned la = ((unsigned)k * (unsigned)b.ny + (unsigned)j) * (unsigned)b.nx + iu;
-            const unsigned lb = ((unsigned)bk * (unsigned)b.ny + (unsigned)bj) * (unsigned)b.nx + (unsigned)bi;
-            const double wa = 255.0 * (double)b.weight[base + la], wb = 255.0 * (double)b.weight[base + lb];
-            const unsigned* col = b.color + (size_t)s * 3 * b.nvox;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const double ca = (double)col[(size_t)ch * b.nvox + la] / wa, cb = (double)col[(size_t)ch * b.nvox + lb] / wb;
-                b.colors[((size_t)s * cap + o) * 3 + ch] = (float)(ca + sc * (cb - ca));
-            }
-        }
-    }
+    int first;
+    tsdf_write_body(b, s_wsum, first);
 }
 
 // ------------------------------------------------------------------------------------------------------- host
-bool volume_ok(long long S, long long nx, long long ny, long long nz) {
-    if (S < 1 || nx < 1 || ny < 1 || nz < 1) return false;
-    const long long lim = 1ll << 31;
-    if (nx >= lim || ny >= lim || nz >= lim || nx * ny >= lim || nx * ny * nz >= lim) return false;
-    return S * (nx * ny * nz) < lim;
-}
-
 bool views_ok(long long V, long long h) {
     if (V < 1 || h < 2 || h > 8192 || (h & 1)) return false;
     return V * h * 4 * h < (1ll << 31);
 }
 
 bool finite_pos(double v) { return std::isfinite(v) && v > 0.0; }
-
-unsigned blocks_of(long long nvox) { return (unsigned)((nvox + kTile - 1) / kTile); }
 
 size_t carve_fuse(int S, char* base, const int*& view_begin, const double*& origin) {
     size_t off = 0;
@@ -298,7 +183,7 @@ size_t carve_surface(int S, unsigned nblk, char* base, int*& blk, const double*&
 }  // namespace
 
 extern "C" size_t relpose_tsdf_fuse_workspace_bytes(int32_t n_scenes, int32_t n_views, int32_t h, int32_t nx, int32_t ny, int32_t nz) {
-    if (!volume_ok(n_scenes, nx, ny, nz) || !views_ok(n_views, h)) return 0;
+    if (!tsdf_volume_ok(n_scenes, nx, ny, nz) || !views_ok(n_views, h)) return 0;
     const int* vb;
     const double* org;
     return carve_fuse(n_scenes, nullptr, vb, org);
@@ -313,7 +198,7 @@ extern "C" int relpose_tsdf_fuse(const RelposeTsdfFuseArgs* args_in) {
     if (a.dataset != RELPOSE_SUNCG && a.dataset != RELPOSE_MATTERPORT && a.dataset != RELPOSE_SCANNET) return RELPOSE_EINVAL;
     if ((a.accumulate != 0 && a.accumulate != 1) || a.reserved0 != 0) return RELPOSE_EINVAL;
     if (!finite_pos(a.voxel) || !finite_pos(a.trunc)) return RELPOSE_EINVAL;
-    if (!volume_ok(a.n_scenes, a.nx, a.ny, a.nz) || !views_ok(a.n_views, a.h)) return RELPOSE_EINVAL;
+    if (!tsdf_volume_ok(a.n_scenes, a.nx, a.ny, a.nz) || !views_ok(a.n_views, a.h)) return RELPOSE_EINVAL;
     if (a.view_begin_host[0] != 0 || a.view_begin_host[a.n_scenes] != a.n_views) return RELPOSE_EINVAL;
     for (int s = 0; s < a.n_scenes; ++s) {
         const long long n = (long long)a.view_begin_host[s + 1] - a.view_begin_host[s];
@@ -326,7 +211,7 @@ extern "C" int relpose_tsdf_fuse(const RelposeTsdfFuseArgs* args_in) {
     carve_fuse(a.n_scenes, (char*)a.workspace, k.view_begin, k.origin);
     k.h = a.h; k.dataset = a.dataset; k.nx = a.nx; k.ny = a.ny; k.accumulate = a.accumulate;
     k.nvox = (unsigned)((long long)a.nx * a.ny * a.nz);
-    k.nblk = blocks_of(k.nvox);
+    k.nblk = tsdf_blocks_of(k.nvox);
     k.voxel = a.voxel; k.trunc = a.trunc;
     k.depth = a.depth; k.rgb = a.rgb; k.pose = a.pose;
     k.tsdf = a.tsdf_sum; k.weight = a.weight; k.color = a.color_sum;
@@ -340,10 +225,10 @@ extern "C" int relpose_tsdf_fuse(const RelposeTsdfFuseArgs* args_in) {
 }
 
 extern "C" size_t relpose_tsdf_surface_workspace_bytes(int32_t n_scenes, int32_t nx, int32_t ny, int32_t nz) {
-    if (!volume_ok(n_scenes, nx, ny, nz) || 3ll * nx * ny * nz >= (1ll << 31)) return 0;
+    if (!tsdf_volume_ok(n_scenes, nx, ny, nz) || 3ll * nx * ny * nz >= (1ll << 31)) return 0;
     int* blk;
     const double* org;
-    return carve_surface(n_scenes, blocks_of((long long)nx * ny * nz), nullptr, blk, org);
+    return carve_surface(n_scenes, tsdf_blocks_of((long long)nx * ny * nz), nullptr, blk, org);
 }
 
 extern "C" int relpose_tsdf_surface(const RelposeTsdfSurfaceArgs* args_in) {
@@ -353,13 +238,13 @@ extern "C" int relpose_tsdf_surface(const RelposeTsdfSurfaceArgs* args_in) {
     if (!a.tsdf_sum || !a.weight || !a.origin_host || !a.points || !a.normals || !a.valid || !a.n_points || !a.workspace) return RELPOSE_EINVAL;
     if (a.colors && !a.color_sum) return RELPOSE_EINVAL;
     if (a.min_weight < 1 || a.cap < 1 || a.reserved0 != 0 || !finite_pos(a.voxel)) return RELPOSE_EINVAL;
-    if (!volume_ok(a.n_scenes, a.nx, a.ny, a.nz) || 3ll * a.nx * a.ny * a.nz >= (1ll << 31)) return RELPOSE_EINVAL;
+    if (!tsdf_volume_ok(a.n_scenes, a.nx, a.ny, a.nz) || 3ll * a.nx * a.ny * a.nz >= (1ll << 31)) return RELPOSE_EINVAL;
     if ((long long)a.n_scenes * a.cap >= (1ll << 29)) return RELPOSE_EINVAL;
     for (int e = 0; e < 3 * a.n_scenes; ++e)
         if (!std::isfinite(a.origin_host[e])) return RELPOSE_EINVAL;
     SurfBufs k{};
     k.nvox = (unsigned)((long long)a.nx * a.ny * a.nz);
-    k.nblk = blocks_of(k.nvox);
+    k.nblk = tsdf_blocks_of(k.nvox);
     if (a.workspace_bytes < carve_surface(a.n_scenes, k.nblk, nullptr, k.blk, k.origin) || ((uintptr_t)a.workspace & 255)) return RELPOSE_EINVAL;
     carve_surface(a.n_scenes, k.nblk, (char*)a.workspace, k.blk, k.origin);
     k.nx = a.nx; k.ny = a.ny; k.nz = a.nz; k.min_weight = a.min_weight; k.cap = a.cap;

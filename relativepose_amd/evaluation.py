@@ -22,6 +22,9 @@ unchanged" is realised by the build's own eval_pairs-style harness).
   fuse_views / reconstruction_scores / fuse_summary / wall_error, evaluate_pairs(fuse=...)
                           no counterpart: the posed views merged into a TSDF volume and its surface cloud, and what a pose error does to
                           it (util.tsdf_fuse_dev / tsdf_surface_dev)
+  fuse_views(mesh=True) / mesh_stats / mesh_summary
+                          no counterpart: the fused volume as an indexed triangle mesh and what kind of surface it is (util.tsdf_mesh_dev,
+                          DESIGN.md 4.18)
   synchronize_scene / absolute_pose_errors / evaluate_scenes / scenes_summary
                           no counterpart: a scene's relative poses synchronised into one pose per view, which pair estimates that
                           distrusts, and the scene fused under the result (util.pose_graph / pose_sync_dev)
@@ -285,18 +288,50 @@ def verify_summary(stats):
     return out
 
 
-def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, max_points=None, view_begin=None):
+def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, max_points=None, view_begin=None, mesh=False):
     """Merge posed depth panoramas into one surface cloud per scene: depth [V,h,4h] f32 and rgb [V,3,h,4h] f32 (or None)
     CUDA tensors, R [V,4,4] host float64 world -> camera poses (the loaders' R), view_begin as util.tsdf_fuse_dev's (None: one scene).  The box
     is util.tsdf_bounds_dev's, the volume util.tsdf_fuse_dev's, the cloud util.tsdf_surface_dev's.
-    -> {"points" [S,cap,3] f64, "normals", "colors" (or None), "valid" [S,cap] u8, "n_points" [S] i32, "origin", "dims", "voxel", "state"}."""
+    -> {"points" [S,cap,3] f64, "normals", "colors" (or None), "valid" [S,cap] u8, "n_points" [S] i32, "origin", "dims", "voxel", "state"}.
+    mesh=True: the same five tensors from util.tsdf_mesh_dev, and "triangles" [S,cap_tri,3] i32, "n_triangles" [S] i32."""
     from . import util
     vb = np.array([0, int(depth.shape[0])], np.int32) if view_begin is None else view_begin
     origin, dims = util.tsdf_bounds_dev(depth, R, dataset, voxel, pad, vb)
     state = util.tsdf_fuse_dev(depth, rgb, R, vb, origin, dims, voxel, dataset, trunc)
+    if mesh:
+        out = util.tsdf_mesh_dev(state, min_weight, max_points)
+        out.update(origin=origin, dims=dims, voxel=float(voxel), state=state)
+        return out
     points, normals, colors, valid, n = util.tsdf_surface_dev(state, min_weight, max_points)
     return {"points": points, "normals": normals, "colors": colors, "valid": valid, "n_points": n, "origin": origin, "dims": dims,
             "voxel": float(voxel), "state": state}
+
+
+def mesh_stats(mesh):
+    """What a mesh of fuse_views(mesh=True) / util.tsdf_mesh_dev is, per scene, on the host in float64: -> a list of {"triangles", "area" (the
+    sum of |(p1 - p0) x (p2 - p0)| / 2), "border_edges" (undirected edges with one triangle: the rim of the observed surface),
+    "nonmanifold_edges" (undirected edges with more than two triangles, or with two that run the same way: expected 0)}."""
+    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+    pts, tri, nt = host(mesh["points"]).astype(np.float64), host(mesh["triangles"]).astype(np.int64), host(mesh["n_triangles"])
+    out = []
+    for s in range(pts.shape[0]):
+        t = tri[s, :min(int(nt[s]), tri.shape[1])]
+        p = pts[s]
+        area = float(np.linalg.norm(np.cross(p[t[:, 1]] - p[t[:, 0]], p[t[:, 2]] - p[t[:, 0]]), axis=1).sum() * 0.5) if len(t) else 0.0
+        d = np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]]) if len(t) else np.zeros((0, 2), np.int64)
+        big = int(d.max()) + 1 if len(d) else 1
+        und, inv, cnt = np.unique(d.min(1) * big + d.max(1), return_inverse=True, return_counts=True)
+        fwd = np.bincount(inv.reshape(-1), weights=(d[:, 0] < d[:, 1]).astype(np.float64), minlength=len(und))      # of them, low -> high
+        manifold = (cnt == 1) | ((cnt == 2) & (fwd == 1))
+        out.append({"triangles": int(len(t)), "area": area, "border_edges": int((cnt == 1).sum()), "nonmanifold_edges": int((~manifold).sum())})
+    return out
+
+
+def mesh_summary(stats):
+    """the CLI's medians of mesh_stats over scenes"""
+    med = lambda k: float(np.median([m[k] for m in stats])) if stats else float("nan")
+    return {"mesh_triangles_median": med("triangles"), "mesh_area_median": med("area"), "mesh_border_edges_median": med("border_edges"),
+            "mesh_nonmanifold_edges": int(sum(m["nonmanifold_edges"] for m in stats))}
 
 
 def reconstruction_scores(est, ref, max_dist=0.08):
@@ -735,7 +770,7 @@ def absolute_pose_errors(pose_hat, R, component=None):
 SCENE_BAD_ROT, SCENE_BAD_TRANS = 10.0, 0.3       # a pair estimate is wrong beyond 10 degrees or 0.3 m
 
 
-def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, dataset=None, keypoints=200, seed=0, exp=None, **sync):
+def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, dataset=None, keypoints=200, seed=0, exp=None, mesh=False, **sync):
     """Scenes of posed views -> estimated pairs -> synchronised absolute poses -> what they do to the reconstruction.
     scenes: synth.render_scene dicts; pipe_or_method: a RelativePosePipeline, or "fgs" / "gs" / "cgs" (then `dataset` names the scenes').
     Per scene: mine_pairs, the pair method on the mined pairs through evaluate_pairs / evaluate_fgs / _gs / _cgs as they are (verify and
@@ -747,7 +782,7 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
     'good_downweighted' (the share of each kind that is down-weighted; NaN for an empty kind), 'cost', 'last_step'.
     fuse=voxel: 'fuse_accuracy' / 'fuse_completeness' (reconstruction_scores of fuse_views of the largest component's views under the
     synchronised poses against the same fusion under R_k inv(R_gauge)), 'fuse_points', 'fuse_views'; exp: the surface is written to
-    <exp>.scene<k>.ply."""
+    <exp>.scene<k>.ply.  mesh=True (with fuse): 'mesh' = mesh_stats of the estimate's fusion, and <exp>.scene<k>.mesh.ply next to the cloud."""
     import torch
     from . import synth, util
     method = pipe_or_method if isinstance(pipe_or_method, str) else None
@@ -807,7 +842,7 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
             depth = up(sc["depth"][views])
             rgb = up(sc["rgb"][views]) if exp is not None else None
             inv_g = np.linalg.inv(sc["R"][g])
-            est = fuse_views(depth, rgb, sy["pose"][views], ds, fuse)
+            est = fuse_views(depth, rgb, sy["pose"][views], ds, fuse, mesh=mesh)
             ref = fuse_views(depth, None, np.stack([np.matmul(sc["R"][v], inv_g) for v in views]), ds, fuse)
             acc, cmp_ = reconstruction_scores(est, ref)
             n = int(est["n_points"][0].item())
@@ -815,6 +850,12 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
             if exp is not None:
                 rec['fuse_ply'] = f"{exp}.scene{k}.ply"
                 util.save_ply(rec['fuse_ply'], est["points"][0, :n], est["normals"][0, :n], est["colors"][0, :n])
+            if mesh:
+                rec['mesh'] = mesh_stats(est)[0]
+                if exp is not None:
+                    rec['mesh_ply'] = f"{exp}.scene{k}.mesh.ply"
+                    util.save_ply(rec['mesh_ply'], est["points"][0, :n], est["normals"][0, :n], est["colors"][0, :n],
+                                  est["triangles"][0, :int(est["n_triangles"][0].item())])
         out.append(rec)
     return out
 
@@ -832,6 +873,8 @@ def scenes_summary(recs):
     if recs and 'fuse_accuracy' in recs[0]:
         out.update(fuse_accuracy_median=med([r['fuse_accuracy'] for r in recs]), fuse_completeness_median=med([r['fuse_completeness'] for r in recs]),
                    fuse_points=int(sum(r['fuse_points'] for r in recs)), fuse_ply=[r['fuse_ply'] for r in recs if 'fuse_ply' in r])
+    if recs and any('mesh' in r for r in recs):
+        out.update(mesh_summary([r['mesh'] for r in recs if 'mesh' in r]), mesh_ply=[r['mesh_ply'] for r in recs if 'mesh_ply' in r])
     return out
 
 
@@ -1156,6 +1199,10 @@ def _cli_parser_completion():
                          "(util.pose_sync_dev, DESIGN.md 4.17) and print one JSON line with the absolute pose errors, the share of wrong pair "
                          "estimates that were down-weighted and, with --fuse, the reconstruction scores of the scenes fused under the "
                          "synchronised poses; --verify observed weights the edges by vis_agreement; --exp writes <exp>.scene<k>.ply")
+    ap.add_argument("--mesh", action="store_true",
+                    help="--mine-pairs --fuse VOXEL / --reconstruct --fuse VOXEL: also extract each fused scene's triangle mesh (marching cubes, "
+                         "DESIGN.md 4.18); the JSON line gains the medians of mesh_stats (triangles, area, border edges) and the number of "
+                         "non-manifold edges, and <exp>.scene<k>.mesh.ply is written next to the cloud when --exp is given")
     return ap
 
 
@@ -1191,6 +1238,9 @@ def main(argv=None):
         if args.gpus > 1 or (not args.mine_pairs and args.method == "ours" and args.keypoint_mode != "given"):
             raise SystemExit("--fuse runs on one GPU (--gpus 1) with given keypoints: the fusion is not sharded")
 
+    if args.mesh and (args.fuse is None or not (args.mine_pairs or args.reconstruct)):
+        raise SystemExit("--mesh applies to --mine-pairs --fuse VOXEL and to --reconstruct --fuse VOXEL")
+
     if args.reconstruct:
         if args.mine_pairs or args.descriptor_eval or args.completion_eval or args.from_frames or args.pair_source != "pairs":
             raise SystemExit("--reconstruct is a mode of its own: it mines, estimates and synchronises the pairs of its scenes")
@@ -1218,7 +1268,7 @@ def main(argv=None):
         t0 = time.perf_counter()
         scenes = [synth.render_scene(args.seed + s, args.scene_views, ds) for s in range(args.scenes)]
         recs = evaluate_scenes(who, scenes, dev, verify=args.verify, fuse=args.fuse, dataset=ds, keypoints=args.keypoints, seed=args.seed,
-                               exp=args.exp)
+                               exp=args.exp, mesh=args.mesh)
         torch.cuda.synchronize()
         line = {"reconstruct": True, "method": args.method, "dataset": ds, "scenes": args.scenes, "views": args.scene_views,
                 "seconds": time.perf_counter() - t0, "verify": args.verify, "fuse": args.fuse}
@@ -1236,6 +1286,7 @@ def main(argv=None):
         dev = _lib.require_gpu()
         entries = []
         wall, fuse_points, plys = [], 0, []
+        meshes, mesh_plys = [], []
         t0 = time.perf_counter()
         for s in range(args.scenes):
             sc = synth.render_scene(args.seed + s, args.scene_views, args.dataset)
@@ -1244,7 +1295,7 @@ def main(argv=None):
             if args.fuse is not None:
                 from . import util
                 up = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
-                surf = fuse_views(up(sc["depth"]), up(sc["rgb"]), sc["R"], args.dataset, args.fuse)
+                surf = fuse_views(up(sc["depth"]), up(sc["rgb"]), sc["R"], args.dataset, args.fuse, mesh=args.mesh)
                 n = int(surf["n_points"][0].item())
                 pts = surf["points"][0, :n].cpu().numpy()
                 wall.append(wall_error(pts, sc["half"], args.fuse))
@@ -1252,6 +1303,12 @@ def main(argv=None):
                 if args.exp is not None:
                     plys.append(f"{args.exp}.scene{s}.ply")
                     util.save_ply(plys[-1], pts, surf["normals"][0, :n], surf["colors"][0, :n])
+                if args.mesh:
+                    meshes.append(mesh_stats(surf)[0])
+                    if args.exp is not None:
+                        mesh_plys.append(f"{args.exp}.scene{s}.mesh.ply")
+                        util.save_ply(mesh_plys[-1], pts, surf["normals"][0, :n], surf["colors"][0, :n],
+                                      surf["triangles"][0, :int(surf["n_triangles"][0].item())])
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         path = None if args.exp is None else save_data_list(args.exp + ".datalist.npy", {"test": entries})
@@ -1265,6 +1322,8 @@ def main(argv=None):
             e = np.concatenate(wall) if wall else np.zeros(0)
             line.update(fuse=args.fuse, fuse_wall_err_median=float(np.median(e)) if e.size else float("nan"),
                         fuse_wall_err_p90=float(np.percentile(e, 90)) if e.size else float("nan"), fuse_points=fuse_points, fuse_ply=plys)
+        if args.mesh:
+            line.update(mesh_summary(meshes), mesh_ply=mesh_plys)
         print(json.dumps(line), flush=True)
         return
 

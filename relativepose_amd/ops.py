@@ -42,6 +42,7 @@ Operator                    replaces (reference file:line)
   frames_to_pano            the depth/ and rgb/ panoramas the ScanNet loader reads next to its frames, datasets/ScanNet.py:211-230 (built from the frames)
   overlap                   the two KDTree queries of util.point_cloud_overlap, util.py:21-40 (batched over directed cloud pairs, one grid per cloud)
   visibility                no counterpart: the free-space check of a relative pose against the partner's depth panorama
+  tsdf_mesh                 no counterpart: tsdf_surface's cloud plus the triangles of a marching-cubes mesh over the same volume
   tsdf_fuse, tsdf_surface   no counterpart: posed depth panoramas merged into a TSDF volume and its surface cloud
   pose_sync                 no counterpart: the relative poses of a scene's pairs synchronised into one pose per view
   affinity_topk             rpmodule.py:342-379
@@ -119,6 +120,9 @@ _lib.define("tsdf_fuse(Tensor depth, Tensor? rgb, Tensor pose, Tensor view_begin
 # n_points i32 [S]
 _lib.define("tsdf_surface(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Tensor origin, float voxel, int min_weight=1, "
             "int max_points=65536) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
+# the state of tsdf_fuse -> tsdf_surface's five outputs, triangles i32 [S,max_triangles,3] (indices into the scene's vertex list), n_triangles i32 [S]
+_lib.define("tsdf_mesh(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Tensor origin, float voxel, int min_weight=1, "
+            "int max_points=65536, int max_triangles=131072) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 # T f64 [E,4,4], src / dst integer [E] (local to the scene), w0 f64 [E], view_begin / edge_begin integer [S+1] (read on the host), n_views =
 # view_begin[-1] (an argument so that the Meta function knows the shapes) -> pose f64 [V,4,4],
 # component i32 [V], tree, edge_state i32 [E], confidence, res_rot, res_trans f64 [E], n_components i32 [S], cost, last_step f64 [S]
@@ -295,6 +299,14 @@ def _tsdf_surface(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_
     return points, normals, (tsdf_sum.new_empty(0, dtype=torch.float32) if colors is None else colors), valid, n
 
 
+def _tsdf_mesh(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_points=65536, max_triangles=131072):
+    S, nz, ny, nx = tsdf_sum.shape
+    st = {"tsdf_sum": tsdf_sum, "weight": weight, "color_sum": color_sum, "origin": origin.cpu().numpy(), "dims": (nx, ny, nz), "voxel": float(voxel)}
+    m = _util.tsdf_mesh_dev(st, int(min_weight), int(max_points), int(max_triangles))
+    return (m["points"], m["normals"], (tsdf_sum.new_empty(0, dtype=torch.float32) if m["colors"] is None else m["colors"]), m["valid"], m["n_points"],
+            m["triangles"], m["n_triangles"])
+
+
 POSE_SYNC_OUTPUTS = ("pose", "component", "tree", "edge_state", "confidence", "res_rot", "res_trans", "n_components", "cost", "last_step")
 
 
@@ -329,7 +341,7 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank),
                    ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals),
                    ("frames_to_pano", _frames_to_pano), ("overlap", _overlap), ("visibility", _visibility),
-                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("pose_sync", _pose_sync)):
+                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("tsdf_mesh", _tsdf_mesh), ("pose_sync", _pose_sync)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -477,6 +489,12 @@ def _m_tsdf_surface(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, ma
             tsdf_sum.new_empty(S, cap, dtype=torch.uint8), tsdf_sum.new_empty(S, dtype=torch.int32))
 
 
+def _m_tsdf_mesh(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_points=65536, max_triangles=131072):
+    S = tsdf_sum.shape[0]
+    return _m_tsdf_surface(tsdf_sum, weight, color_sum, origin, voxel, min_weight, max_points) + (
+        tsdf_sum.new_empty(S, int(max_triangles), 3, dtype=torch.int32), tsdf_sum.new_empty(S, dtype=torch.int32))
+
+
 def _m_pose_sync(T, src, dst, w0, view_begin, edge_begin, n_views, sigma_r=0.1, sigma_t=0.1, mu0=64.0, div=1.4, n_final=10, robust=True):
     E, S, V = T.shape[0], view_begin.shape[0] - 1, int(n_views)
     f64, i32 = (lambda *s: T.new_empty(*s, dtype=torch.float64)), (lambda *s: T.new_empty(*s, dtype=torch.int32))
@@ -503,10 +521,10 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank),
                    ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals),
                    ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap), ("visibility", _m_visibility),
-                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("pose_sync", _m_pose_sync)):
+                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("tsdf_mesh", _m_tsdf_mesh), ("pose_sync", _m_pose_sync)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
        "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals",
-       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "pose_sync")
+       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "tsdf_mesh", "pose_sync")

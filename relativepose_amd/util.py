@@ -725,6 +725,58 @@ def tsdf_surface_dev(state, min_weight=1, max_points=None):
     return call(int(max_points), cs is not None)
 
 
+def tsdf_mesh_dev(state, min_weight=1, max_points=None, max_triangles=None):
+    """relpose_tsdf_mesh: tsdf_fuse_dev's state as one indexed triangle mesh per scene, marching cubes.
+    -> {"points", "normals", "colors", "valid", "n_points": tsdf_surface_dev's five tensors, bit for bit, with cap = max_points,
+    "triangles" [S,cap_tri,3] i32: indices into the scene's rows of points, "n_triangles" [S] i32} with cap_tri = max_triangles.  n_triangles
+    counts every triangle and may exceed cap_tri: only the first cap_tri, in ascending cell order, are written; the rows beyond are zero.  A
+    None cap is sized to the largest scene by a counting call first (at least 1).  A triangle may name any vertex of its scene, so a given
+    max_points below a scene's n_points raises ValueError.  The winding faces the space the sensors saw through, as the normals do."""
+    import torch
+    _lib.require_gpu()
+    ts, wt, cs = state["tsdf_sum"], state["weight"], state["color_sum"]
+    S, nz, ny, nx = (int(v) for v in ts.shape)
+    dev = ts.device
+    origin = np.ascontiguousarray(state["origin"], dtype=np.float64).reshape(S, 3)
+    L = _lib.lib()
+    nbytes = L.relpose_tsdf_mesh_workspace_bytes(S, nx, ny, nz)
+    if nbytes == 0 or int(min_weight) < 1:
+        raise ValueError("tsdf_mesh_dev: sizes outside relpose_tsdf_mesh's limits, or min_weight < 1")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    tsc, wtc, csc = ts.contiguous(), wt.contiguous(), (None if cs is None else cs.contiguous())
+
+    def call(cap, cap_tri, colours):
+        out = {"points": torch.zeros(S, cap, 3, dtype=torch.float64, device=dev), "normals": torch.zeros(S, cap, 3, dtype=torch.float64, device=dev),
+               "colors": torch.zeros(S, cap, 3, dtype=torch.float32, device=dev) if colours else None,
+               "valid": torch.empty(S, cap, dtype=torch.uint8, device=dev), "n_points": torch.empty(S, dtype=torch.int32, device=dev),
+               "triangles": torch.zeros(S, cap_tri, 3, dtype=torch.int32, device=dev), "n_triangles": torch.empty(S, dtype=torch.int32, device=dev)}
+        a = _lib.TsdfMeshArgs()
+        a.struct_size = _lib.C.sizeof(_lib.TsdfMeshArgs)
+        a.n_scenes, a.nx, a.ny, a.nz, a.min_weight, a.cap, a.cap_tri = S, nx, ny, nz, int(min_weight), cap, cap_tri
+        a.tsdf_sum, a.weight, a.color_sum = tsc.data_ptr(), wtc.data_ptr(), (0 if csc is None else csc.data_ptr())
+        a.origin_host, a.voxel = origin.ctypes.data, float(state["voxel"])
+        a.points, a.normals, a.colors = out["points"].data_ptr(), out["normals"].data_ptr(), (out["colors"].data_ptr() if colours else 0)
+        a.valid, a.n_points = out["valid"].data_ptr(), out["n_points"].data_ptr()
+        a.triangles, a.n_triangles = out["triangles"].data_ptr(), out["n_triangles"].data_ptr()
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+        a.stream = _lib.stream_ptr()
+        rc_ = L.relpose_tsdf_mesh(_lib.C.byref(a))
+        if rc_ == -1:
+            raise ValueError("relpose_tsdf_mesh: invalid arguments (a cap < 1 or S cap >= 2^29, or sizes outside the limits)")
+        _lib.check(rc_, "relpose_tsdf_mesh")
+        return out
+
+    if max_points is None or max_triangles is None:
+        n = call(1, 1, False)
+        max_points = max(1, int(n["n_points"].max().item())) if max_points is None else max_points
+        max_triangles = max(1, int(n["n_triangles"].max().item())) if max_triangles is None else max_triangles
+    out = call(int(max_points), int(max_triangles), cs is not None)
+    if int(out["n_points"].max().item()) > int(max_points):
+        raise ValueError(f"tsdf_mesh_dev: max_points = {int(max_points)} truncates a scene of {int(out['n_points'].max().item())} vertices; "
+                         "its triangles would name vertices that were not written")
+    return out
+
+
 def tsdf_bounds_dev(depth, R, dataset, voxel, pad=3, view_begin=None):
     """The box tsdf_fuse_dev should be given: per scene, around every pixel with data of its views unprojected (pano2pc_dev) and moved into the
     world frame by the inverse of its pose R [V,4,4] (host float64, world -> camera), widened by `pad` voxels on every side.
@@ -843,9 +895,10 @@ def pose_graph(pairs, poses, weights=None):
             np.array(w0, np.float64).reshape(-1), np.array(pair, np.int32).reshape(-1))
 
 
-def save_ply(path, points, normals=None, colors=None):
+def save_ply(path, points, normals=None, colors=None, faces=None):
     """Write a binary little-endian PLY point cloud: points [N,3] (float32 x y z in the file), normals [N,3] (nx ny nz) and colors [N,3] in
-    [0, 1] (uchar red green blue) if given; arrays or tensors.  Returns N."""
+    [0, 1] (uchar red green blue) if given; arrays or tensors.  faces [F,3] (integer indices into points): a mesh, `element face` with
+    `property list uchar int vertex_indices`.  Returns N."""
     host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
     p = host(points).reshape(-1, 3)
     N = p.shape[0]
@@ -873,9 +926,19 @@ def save_ply(path, points, normals=None, colors=None):
         q = np.rint(np.clip(np.nan_to_num(c.astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
         for a, k in enumerate(("red", "green", "blue")):
             rec[k] = q[:, a]
+    tail = b""
+    if faces is not None:
+        t = host(faces).reshape(-1, 3)
+        if t.size and (t.min() < 0 or t.max() >= N):
+            raise ValueError("save_ply: a face names a vertex that is not there")
+        header += [f"element face {t.shape[0]}", "property list uchar int vertex_indices"]
+        frec = np.zeros(t.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+        frec["n"], frec["v"] = 3, t
+        tail = frec.tobytes()
     with open(path, "wb") as f:
         f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
         f.write(rec.tobytes())
+        f.write(tail)
     return N
 
 
