@@ -1122,6 +1122,95 @@ typedef struct RelposeTsdfMeshArgs {
 size_t relpose_tsdf_mesh_workspace_bytes(int32_t n_scenes, int32_t nx, int32_t ny, int32_t nz);
 int relpose_tsdf_mesh(const RelposeTsdfMeshArgs* args);
 
+/* Frame-to-model alignment: refine the poses of n_views depth panoramas against relpose_tsdf_fuse's volumes, so that each view's measured
+ * points come to lie on the zero level of the volume it names (the KinectFusion tracking step, sampled at the measured points: no ray is
+ * marched).  The contract is the project's own (tests/align_model.py restates it in numpy, the per-point rule on whole arrays
+ * and as plain loops).  The geometry is float64, every operation rounded on its own; whatever is summed across points is an integer, so the
+ * result does not depend on the order of the points, on the decomposition into workgroups or on the batch around a view.  No atomics.
+ *
+ *   tsdf_sum, weight [n_scenes, nz, ny, nx] i32, origin_host [n_scenes, 3] f64 (HOST), voxel, min_weight (>= 1): relpose_tsdf_fuse's state
+ *   depth            [n_views, h, 4h] f32; pose [n_views, 4, 4] f64 row-major on the DEVICE, world -> camera (the last row is copied through)
+ *   scene_of_view_host [n_views] i32 in HOST memory, each in 0 .. n_scenes-1: several views may name one volume, a volume may have none
+ *   points           pixel p = row * 4h + column takes part iff p % stride == 0 and its depth is data (z > 0 && z <= FLT_MAX).  With
+ *                    slot = column / h, px = column % h, D = (double)z: xn = (2.0 * px) / h - 1.0, yn = 1.0 - (2.0 * row) / h -- the centre
+ *                    that relpose_visibility's projection rounds to, so a point of column px >= 1 and row >= 1 projects onto its own pixel
+ *                    (xn = -1 or yn = 1 lie on the face's open edge) -- and the camera point is Rs[face(dataset, slot)] (xn D, yn D, -D).
+ *   evaluation       W = the rigid inverse of the current pose T: W_ab = T_ba, W_a3 = -((T_0a T_03 + T_1a T_13) + T_2a T_23);
+ *                    q_a = ((W_a0 x + W_a1 y) + W_a2 z) + W_a3;  u_a = (q_a - origin_a) / voxel - 0.5, i0_a = floor(u_a), f_a = u_a - i0_a.
+ *                    The point is, in this order: OUTSIDE unless q is finite and 0 <= i0_a <= n_a - 2 on every axis (nothing is read for
+ *                    it); UNKNOWN if any of the 8 corners (i0 + (c & 1, c >> 1 & 1, c >> 2 & 1)) has weight < min_weight; SATURATED if any
+ *                    corner has |t| >= 1, t = (double)tsdf_sum / (32768.0 * (double)weight); USED otherwise.  For a used point, with t_c:
+ *                      d00 = t1 - t0, d10 = t3 - t2, d01 = t5 - t4, d11 = t7 - t6;  a00 = t0 + fx d00, a10 = t2 + fx d10, a01 = t4 + fx d01,
+ *                      a11 = t6 + fx d11;  c0 = a10 - a00, c1 = a11 - a01;  b0 = a00 + fy c0, b1 = a01 + fy c1;
+ *                      gz = b1 - b0;  r = b0 + fz gz;  gy = c0 + fz (c1 - c0);  e0 = d00 + fy (d10 - d00), e1 = d01 + fy (d11 - d01);
+ *                      gx = e0 + fz (e1 - e0)          (r: the trilinear value in units of trunc; g: its gradient per voxel)
+ *                      l_a = (q_a - c_a) / voxel, c_a = origin_a + (n_a * 0.5) * voxel;  J = (l x g, g) = (ly gz - lz gy, lz gx - lx gz,
+ *                      lx gy - ly gx, gx, gy, gz);  Jq_i = llrint(J_i * 2^8) for i < 3, llrint(J_i * 2^16) for i >= 3, rq = llrint(r * 2^16).
+ *   sums             [32] i64 per view and evaluation: the 21 products Jq_i Jq_j (i <= j, row-major), the 6 products Jq_i rq, rq rq, and
+ *                    the counts of OUTSIDE, UNKNOWN, SATURATED and USED points, each summed over the view's points.  No overflow: a used
+ *                    point lies inside the volume and n_a <= 2048, so |l_a| <= 1024; |t| < 1 at every corner, so |g_a| <= 2 and |r| < 1;
+ *                    |Jq_i| <= 4096 * 2^8 = 2^20 (i < 3) and 2^17 (i >= 3), |rq| <= 2^16; at most 2^22 points per view:
+ *                    every sum stays below 2^40 * 2^22 = 2^62.
+ *   step             A_ij = (double)sum / (s_i s_j), b_i = (double)sum / (s_i 2^16) with s = 2^8 (i < 3) or 2^16: one rounding from int64
+ *                    (exact below 2^53), the scales are exact.  A = V diag(lambda) V^T by cyclic Jacobi: 8 sweeps over (p, q), p < q,
+ *                    row-major; a pair with A_pq == 0 is skipped; theta = (A_qq - A_pp) / (2 A_pq), t = +-1 / (|theta| + sqrt(theta theta + 1))
+ *                    with theta's sign (+ for 0), c = 1 / sqrt(t t + 1), s = t c; A_pp -= t A_pq, A_qq += t A_pq, A_pq = 0, and for the
+ *                    other k: A_kp' = c A_kp - s A_kq, A_kq' = s A_kp + c A_kq (mirrored); V likewise for every row.
+ *                    Column k is taken iff n_used >= 6 and lambda_k > eig_min * n_used: coef_k = -((sum_i V_ik b_i) / lambda_k), summed from
+ *                    0 in ascending i; every other column is HELD (coef_k = 0).  delta_i = sum_k V_ik coef_k, from 0 in ascending k.
+ *   update           skipped (the pose is copied bit for bit) when n_used < 6.  Otherwise a = delta_0..2 * 0.5, aa = (a0 a0 + a1 a1) + a2 a2,
+ *                    the Cayley rotation Rd = ((1 - aa) I + 2 a a^T + 2 [a]x) / (1 + aa), entry by entry ((1 - aa) + 2.0 * (a_i a_i)) / (1 + aa)
+ *                    and (2.0 * (a_i a_j -+ a_k)) / (1 + aa);  d_i = (c_i - ((Rd_i0 c0 + Rd_i1 c1) + Rd_i2 c2)) + voxel * delta_{3+i}: the
+ *                    points move by x -> c + Rd (x - c) + voxel tau in the world frame, about the volume's centre.  The new pose is
+ *                    T' = T D^-1: R'_ij = (T_i0 Rd_j0 + T_i1 Rd_j1) + T_i2 Rd_j2, t'_i = T_i3 - ((R'_i0 d0 + R'_i1 d1) + R'_i2 d2).
+ *                    Only + - * / sqrt: the numpy model follows every bit.
+ *   iterations       iters + 1 evaluations (iters in 0..64); each but the last is followed by a step.  iters = 0 scores the poses as given.
+ *   outputs          pose_out [n_views, 4, 4] f64 (may be `pose` itself); of the LAST evaluation, at the returned pose: eig [n_views, 6] f64 =
+ *                    lambda / n_used ascending (0 without a used point), held [n_views] i32, sums [n_views, 32] i64;
+ *                    rms [n_views, 2] f64 = sqrt((double)sum(rq rq) / n_used) / 2^16 (0 without a used point) at the first and the last
+ *                    evaluation.  Optional, both or neither: trace_pose [n_views, iters + 1, 4, 4] f64 and trace_sums [n_views, iters + 1, 32]
+ *                    i64, the pose and the sums of every evaluation.
+ *   eig_min          finite, >= 0.  A direction the points do not constrain (a view that sees no wall across one axis) has a small
+ *                    lambda / n_used, and a Gauss-Newton step along it follows gradient noise; 0.0043 separates the two ranges measured on the
+ *                    synthetic rooms and is the default of the Python layers.
+ *   limits           relpose_tsdf_fuse's for h, n_views and the volume; nx, ny, nz <= 2048; stride >= 1; ceil(4 h h / stride) <= 2^22
+ *   workspace        relpose_tsdf_align_workspace_bytes(n_scenes, n_views, h, nx, ny, nz, stride) bytes (0 for sizes outside the limits),
+ *                    256-byte aligned: the device copies of origin and scene_of_view, and 32 i64 per workgroup of 1024 sampled pixels
+ * Invalid arguments return RELPOSE_EINVAL before anything is enqueued or any output is touched.  Two launches per evaluation whatever
+ * n_views is.  The call waits for `stream` once, at its end. */
+typedef struct RelposeTsdfAlignArgs {
+    uint32_t struct_size;       /* sizeof(RelposeTsdfAlignArgs) as the caller compiled it */
+    int32_t n_scenes;
+    int32_t n_views;
+    int32_t h;
+    int32_t dataset;
+    int32_t nx, ny, nz;
+    int32_t min_weight;
+    int32_t iters;
+    int32_t stride;
+    int32_t reserved0;
+    const int32_t* tsdf_sum;
+    const int32_t* weight;
+    const float* depth;
+    const double* pose;
+    const double* origin_host;
+    const int32_t* scene_of_view_host;
+    double voxel;
+    double eig_min;
+    double* pose_out;
+    double* eig;
+    int32_t* held;
+    int64_t* sums;
+    double* rms;
+    double* trace_pose;
+    int64_t* trace_sums;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeTsdfAlignArgs;
+size_t relpose_tsdf_align_workspace_bytes(int32_t n_scenes, int32_t n_views, int32_t h, int32_t nx, int32_t ny, int32_t nz, int32_t stride);
+int relpose_tsdf_align(const RelposeTsdfAlignArgs* args);
+
 /* -------------------------------------------------------------------- robust synchronisation of pose graphs
  * The pair drivers give a relative pose per pair of views; some are grossly wrong.  relpose_pose_sync turns the relative poses of n_scenes
  * scenes into one absolute pose per view and one confidence per relative pose: graduated Geman-McClure re-weighting around a linearised

@@ -28,6 +28,7 @@ SOURCES = [
     ("visibility.hip", ["-ffp-contract=off"]),     # visibility consistency: classes and margins must agree with tests/visibility_model.py bit for bit
     ("tsdf.hip", ["-ffp-contract=off"]),           # TSDF fusion: the integer volume and the surface must agree with tests/tsdf_model.py bit for bit
     ("mesh.hip", ["-ffp-contract=off"]),           # marching cubes: the vertices are tsdf.hip's surface bit for bit (tsdf_surf.h), the triangles tests/mesh_model.py's
+    ("tsdfalign.hip", ["-ffp-contract=off"]),      # TSDF alignment: the integer sums and the stepped poses must agree with tests/align_model.py bit for bit
     ("posesync.hip", ["-ffp-contract=off"]),       # pose synchronisation: every f64 operation rounds as tests/sync_model.py states it
     ("scnet.hip", []),
 ]

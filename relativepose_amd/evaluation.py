@@ -25,6 +25,9 @@ unchanged" is realised by the build's own eval_pairs-style harness).
   fuse_views(mesh=True) / mesh_stats / mesh_summary
                           no counterpart: the fused volume as an indexed triangle mesh and what kind of surface it is (util.tsdf_mesh_dev,
                           DESIGN.md 4.18)
+  refine_scene / leave_one_out_state, evaluate_scenes(refine=...)
+                          no counterpart: the views' poses refined against the volume the other views fuse into, frame to model
+                          (util.tsdf_align_dev)
   synchronize_scene / absolute_pose_errors / evaluate_scenes / scenes_summary
                           no counterpart: a scene's relative poses synchronised into one pose per view, which pair estimates that
                           distrusts, and the scene fused under the result (util.pose_graph / pose_sync_dev)
@@ -305,6 +308,42 @@ def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, m
     points, normals, colors, valid, n = util.tsdf_surface_dev(state, min_weight, max_points)
     return {"points": points, "normals": normals, "colors": colors, "valid": valid, "n_points": n, "origin": origin, "dims": dims,
             "voxel": float(voxel), "state": state}
+
+
+def leave_one_out_state(state_all, state_solo):
+    """tsdf_fuse_dev's state of all V views in one scene, and of every view alone (V scenes of one view, the same box) -> the state of V
+    scenes, scene v = every view but v.  The sums are integers: the difference is exactly what fusing the others gives."""
+    out = dict(state_solo)
+    for k in ("tsdf_sum", "weight", "color_sum"):
+        out[k] = None if state_solo.get(k) is None else state_all[k] - state_solo[k]
+    return out
+
+
+def refine_scene(depth, R, dataset, voxel, rounds=1, leave_one_out=True, iters=12, eig_min=None, stride=1, trunc=None, pad=3, min_weight=1):
+    """Refine the poses of one scene's views against the volume they fuse into: depth [V,h,4h] f32 CUDA tensor, R [V,4,4]
+    host float64 world -> camera.  Per round: the box (util.tsdf_bounds_dev) and one fusion of all views under the current poses; with
+    leave_one_out, every view fused alone in one batched call and subtracted, so that view v is aligned to the volume of the others (a view
+    aligned to a volume that holds itself is pulled to where it already is); then every view is aligned in ONE util.tsdf_align_dev call.
+    -> {"pose" [V,4,4] host float64, "held" [V], "eig" [V,6], "rms" [V,2] (before the first round's first step, after the last round's last),
+    "used" [V] (points used at the last evaluation)}.  rounds=0 returns the poses as given, scored."""
+    import torch
+    from . import util
+    V = int(depth.shape[0])
+    R = np.ascontiguousarray(R, dtype=np.float64).reshape(V, 4, 4).copy()
+    first = None
+    for rnd in range(max(int(rounds), 1)):
+        origin, dims = util.tsdf_bounds_dev(depth, R, dataset, voxel, pad)
+        state = util.tsdf_fuse_dev(depth, None, R, np.array([0, V], np.int32), origin, dims, voxel, dataset, trunc)
+        sov = np.zeros(V, np.int32)
+        if leave_one_out and V > 1:
+            solo = util.tsdf_fuse_dev(depth, None, R, np.arange(V + 1, dtype=np.int32), np.repeat(origin, V, 0), dims, voxel, dataset, trunc)
+            state = leave_one_out_state(state, solo)
+            sov = np.arange(V, dtype=np.int32)
+        out = util.tsdf_align_dev(state, depth, R, sov, iters if rounds > 0 else 0, eig_min, stride, min_weight=min_weight)
+        first = out["rms"][:, 0].cpu().numpy() if first is None else first
+        R = out["pose"].cpu().numpy()
+    return {"pose": R, "held": out["held"].cpu().numpy(), "eig": out["eig"].cpu().numpy(),
+            "rms": np.stack([first, out["rms"][:, 1].cpu().numpy()], 1), "used": out["sums"][:, 31].cpu().numpy()}
 
 
 def mesh_stats(mesh):
@@ -770,7 +809,8 @@ def absolute_pose_errors(pose_hat, R, component=None):
 SCENE_BAD_ROT, SCENE_BAD_TRANS = 10.0, 0.3       # a pair estimate is wrong beyond 10 degrees or 0.3 m
 
 
-def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, dataset=None, keypoints=200, seed=0, exp=None, mesh=False, **sync):
+def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, dataset=None, keypoints=200, seed=0, exp=None, mesh=False, refine=0,
+                    **sync):
     """Scenes of posed views -> estimated pairs -> synchronised absolute poses -> what they do to the reconstruction.
     scenes: synth.render_scene dicts; pipe_or_method: a RelativePosePipeline, or "fgs" / "gs" / "cgs" (then `dataset` names the scenes').
     Per scene: mine_pairs, the pair method on the mined pairs through evaluate_pairs / evaluate_fgs / _gs / _cgs as they are (verify and
@@ -782,7 +822,11 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
     'good_downweighted' (the share of each kind that is down-weighted; NaN for an empty kind), 'cost', 'last_step'.
     fuse=voxel: 'fuse_accuracy' / 'fuse_completeness' (reconstruction_scores of fuse_views of the largest component's views under the
     synchronised poses against the same fusion under R_k inv(R_gauge)), 'fuse_points', 'fuse_views'; exp: the surface is written to
-    <exp>.scene<k>.ply.  mesh=True (with fuse): 'mesh' = mesh_stats of the estimate's fusion, and <exp>.scene<k>.mesh.ply next to the cloud."""
+    <exp>.scene<k>.ply.  mesh=True (with fuse): 'mesh' = mesh_stats of the estimate's fusion, and <exp>.scene<k>.mesh.ply next to the cloud.
+    refine=rounds (with fuse): the largest component's synchronised poses are refined against the fused volume (refine_scene,
+    re-gauged to the component's first view) before the final fusion, which then uses them; the record gains 'refine_rounds',
+    'refine_err_rot' / 'refine_err_t' [2, views] (absolute_pose_errors before and after), 'refine_wall_median' [2] (the surface's median
+    distance to the room's walls in voxels, for scenes that carry "half"), 'refine_held_views'.  refine=0: nothing changes."""
     import torch
     from . import synth, util
     method = pipe_or_method if isinstance(pipe_or_method, str) else None
@@ -842,7 +886,23 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
             depth = up(sc["depth"][views])
             rgb = up(sc["rgb"][views]) if exp is not None else None
             inv_g = np.linalg.inv(sc["R"][g])
-            est = fuse_views(depth, rgb, sy["pose"][views], ds, fuse, mesh=mesh)
+            pose_est = sy["pose"][views]
+            if refine:
+                ref_out = refine_scene(depth, pose_est, ds, fuse, rounds=int(refine))
+                gauge = np.linalg.inv(ref_out["pose"][int(np.nonzero(views == g)[0][0])])
+                pose_ref = np.stack([np.matmul(P, gauge) for P in ref_out["pose"]])
+                errs = [absolute_pose_errors(P, sc["R"][views], np.full(len(views), int(np.nonzero(views == g)[0][0]))) for P in (pose_est, pose_ref)]
+                rec.update(refine_rounds=int(refine), refine_err_rot=np.stack([e[0] for e in errs]), refine_err_t=np.stack([e[1] for e in errs]),
+                           refine_held_views=int((ref_out["held"] > 0).sum()))
+                if "half" in sc:
+                    walls = []
+                    for P in (pose_est, pose_ref):
+                        sf = fuse_views(depth, None, P, ds, fuse)
+                        pts = sf["points"][0, :int(sf["n_points"][0].item())].cpu().numpy()
+                        walls.append(float(np.median(wall_error(pts @ inv_g[:3, :3].T + inv_g[:3, 3], sc["half"], fuse))) if len(pts) else float("nan"))
+                    rec['refine_wall_median'] = walls
+                pose_est = pose_ref
+            est = fuse_views(depth, rgb, pose_est, ds, fuse, mesh=mesh)
             ref = fuse_views(depth, None, np.stack([np.matmul(sc["R"][v], inv_g) for v in views]), ds, fuse)
             acc, cmp_ = reconstruction_scores(est, ref)
             n = int(est["n_points"][0].item())
@@ -873,6 +933,13 @@ def scenes_summary(recs):
     if recs and 'fuse_accuracy' in recs[0]:
         out.update(fuse_accuracy_median=med([r['fuse_accuracy'] for r in recs]), fuse_completeness_median=med([r['fuse_completeness'] for r in recs]),
                    fuse_points=int(sum(r['fuse_points'] for r in recs)), fuse_ply=[r['fuse_ply'] for r in recs if 'fuse_ply' in r])
+    if recs and any('refine_rounds' in r for r in recs):
+        rr = [r for r in recs if 'refine_rounds' in r]
+        out.update(refine_rounds=rr[0]['refine_rounds'],
+                   refine_abs_err_rot_median=[med([float(np.median(r['refine_err_rot'][k])) for r in rr]) for k in (0, 1)],
+                   refine_abs_err_t_median=[med([float(np.median(r['refine_err_t'][k])) for r in rr]) for k in (0, 1)],
+                   refine_wall_median=[med([r['refine_wall_median'][k] for r in rr if 'refine_wall_median' in r]) for k in (0, 1)],
+                   refine_held_views=int(sum(r['refine_held_views'] for r in rr)))
     if recs and any('mesh' in r for r in recs):
         out.update(mesh_summary([r['mesh'] for r in recs if 'mesh' in r]), mesh_ply=[r['mesh_ply'] for r in recs if 'mesh_ply' in r])
     return out
@@ -1199,6 +1266,11 @@ def _cli_parser_completion():
                          "(util.pose_sync_dev, DESIGN.md 4.17) and print one JSON line with the absolute pose errors, the share of wrong pair "
                          "estimates that were down-weighted and, with --fuse, the reconstruction scores of the scenes fused under the "
                          "synchronised poses; --verify observed weights the edges by vis_agreement; --exp writes <exp>.scene<k>.ply")
+    ap.add_argument("--refine", type=int, default=0, metavar="ROUNDS",
+                    help="--reconstruct --fuse VOXEL: after the synchronisation, refine every view's pose against the volume the other views fuse "
+                         "into (util.tsdf_align_dev, DESIGN.md 4.19), ROUNDS times, before the final fusion.  The JSON line gains, before and "
+                         "after: refine_abs_err_rot_median / _t_median (absolute pose errors), refine_wall_median (the surface's median distance "
+                         "to the room's walls, voxels), and refine_held_views (views with a direction the volume does not constrain)")
     ap.add_argument("--mesh", action="store_true",
                     help="--mine-pairs --fuse VOXEL / --reconstruct --fuse VOXEL: also extract each fused scene's triangle mesh (marching cubes, "
                          "DESIGN.md 4.18); the JSON line gains the medians of mesh_stats (triangles, area, border edges) and the number of "
@@ -1241,6 +1313,9 @@ def main(argv=None):
     if args.mesh and (args.fuse is None or not (args.mine_pairs or args.reconstruct)):
         raise SystemExit("--mesh applies to --mine-pairs --fuse VOXEL and to --reconstruct --fuse VOXEL")
 
+    if args.refine and (args.refine < 0 or args.fuse is None or not args.reconstruct):
+        raise SystemExit("--refine takes a number of rounds >= 0 and applies to --reconstruct --fuse VOXEL")
+
     if args.reconstruct:
         if args.mine_pairs or args.descriptor_eval or args.completion_eval or args.from_frames or args.pair_source != "pairs":
             raise SystemExit("--reconstruct is a mode of its own: it mines, estimates and synchronises the pairs of its scenes")
@@ -1268,10 +1343,12 @@ def main(argv=None):
         t0 = time.perf_counter()
         scenes = [synth.render_scene(args.seed + s, args.scene_views, ds) for s in range(args.scenes)]
         recs = evaluate_scenes(who, scenes, dev, verify=args.verify, fuse=args.fuse, dataset=ds, keypoints=args.keypoints, seed=args.seed,
-                               exp=args.exp, mesh=args.mesh)
+                               exp=args.exp, mesh=args.mesh, refine=args.refine)
         torch.cuda.synchronize()
         line = {"reconstruct": True, "method": args.method, "dataset": ds, "scenes": args.scenes, "views": args.scene_views,
                 "seconds": time.perf_counter() - t0, "verify": args.verify, "fuse": args.fuse}
+        if args.refine:
+            line["refine"] = args.refine
         line.update(scenes_summary(recs))
         print(json.dumps(line), flush=True)
         return

@@ -42,6 +42,7 @@ Operator                    replaces (reference file:line)
   frames_to_pano            the depth/ and rgb/ panoramas the ScanNet loader reads next to its frames, datasets/ScanNet.py:211-230 (built from the frames)
   overlap                   the two KDTree queries of util.point_cloud_overlap, util.py:21-40 (batched over directed cloud pairs, one grid per cloud)
   visibility                no counterpart: the free-space check of a relative pose against the partner's depth panorama
+  tsdf_align                no counterpart: view poses refined against the fused TSDF volume, frame-to-model Gauss-Newton
   tsdf_mesh                 no counterpart: tsdf_surface's cloud plus the triangles of a marching-cubes mesh over the same volume
   tsdf_fuse, tsdf_surface   no counterpart: posed depth panoramas merged into a TSDF volume and its surface cloud
   pose_sync                 no counterpart: the relative poses of a scene's pairs synchronised into one pose per view
@@ -123,6 +124,11 @@ _lib.define("tsdf_surface(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Ten
 # the state of tsdf_fuse -> tsdf_surface's five outputs, triangles i32 [S,max_triangles,3] (indices into the scene's vertex list), n_triangles i32 [S]
 _lib.define("tsdf_mesh(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Tensor origin, float voxel, int min_weight=1, "
             "int max_points=65536, int max_triangles=131072) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+# the state of tsdf_fuse, depth f32 [V,h,4h], pose f64 [V,4,4] world -> camera, scene_of_view integer [V] (read on the host) -> pose f64 [V,4,4],
+# eig f64 [V,6], held i32 [V], sums i64 [V,32], rms f64 [V,2], trace_pose f64 [V,iters+1,4,4] and trace_sums i64 [V,iters+1,32] (empty without trace)
+_lib.define("tsdf_align(Tensor tsdf_sum, Tensor weight, Tensor origin, float voxel, Tensor depth, Tensor pose, Tensor scene_of_view, int dataset, "
+            "int iters=12, float eig_min=0.0043, int stride=1, int min_weight=1, bool trace=False) "
+            "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 # T f64 [E,4,4], src / dst integer [E] (local to the scene), w0 f64 [E], view_begin / edge_begin integer [S+1] (read on the host), n_views =
 # view_begin[-1] (an argument so that the Meta function knows the shapes) -> pose f64 [V,4,4],
 # component i32 [V], tree, edge_state i32 [E], confidence, res_rot, res_trans f64 [E], n_components i32 [S], cost, last_step f64 [S]
@@ -307,6 +313,15 @@ def _tsdf_mesh(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_poi
             m["triangles"], m["n_triangles"])
 
 
+def _tsdf_align(tsdf_sum, weight, origin, voxel, depth, pose, scene_of_view, dataset, iters=12, eig_min=0.0043, stride=1, min_weight=1, trace=False):
+    S, nz, ny, nx = tsdf_sum.shape
+    st = {"tsdf_sum": tsdf_sum, "weight": weight, "origin": origin.cpu().numpy(), "dims": (nx, ny, nz), "voxel": float(voxel),
+          "dataset": _INV_DATASET[int(dataset)]}
+    o = _util.tsdf_align_dev(st, depth, pose, scene_of_view, int(iters), float(eig_min), int(stride), bool(trace), int(min_weight))
+    return (o["pose"], o["eig"], o["held"], o["sums"], o["rms"], o["trace_pose"] if trace else depth.new_empty(0, dtype=torch.float64),
+            o["trace_sums"] if trace else depth.new_empty(0, dtype=torch.int64))
+
+
 POSE_SYNC_OUTPUTS = ("pose", "component", "tree", "edge_state", "confidence", "res_rot", "res_trans", "n_components", "cost", "last_step")
 
 
@@ -341,7 +356,7 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank),
                    ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals),
                    ("frames_to_pano", _frames_to_pano), ("overlap", _overlap), ("visibility", _visibility),
-                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("tsdf_mesh", _tsdf_mesh), ("pose_sync", _pose_sync)):
+                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("tsdf_mesh", _tsdf_mesh), ("tsdf_align", _tsdf_align), ("pose_sync", _pose_sync)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -495,6 +510,13 @@ def _m_tsdf_mesh(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_p
         tsdf_sum.new_empty(S, int(max_triangles), 3, dtype=torch.int32), tsdf_sum.new_empty(S, dtype=torch.int32))
 
 
+def _m_tsdf_align(tsdf_sum, weight, origin, voxel, depth, pose, scene_of_view, dataset, iters=12, eig_min=0.0043, stride=1, min_weight=1, trace=False):
+    V, E = depth.shape[0], int(iters) + 1
+    n = lambda dt, *s: depth.new_empty(*s, dtype=dt)
+    return (n(torch.float64, V, 4, 4), n(torch.float64, V, 6), n(torch.int32, V), n(torch.int64, V, 32), n(torch.float64, V, 2),
+            n(torch.float64, V, E, 4, 4) if trace else n(torch.float64, 0), n(torch.int64, V, E, 32) if trace else n(torch.int64, 0))
+
+
 def _m_pose_sync(T, src, dst, w0, view_begin, edge_begin, n_views, sigma_r=0.1, sigma_t=0.1, mu0=64.0, div=1.4, n_final=10, robust=True):
     E, S, V = T.shape[0], view_begin.shape[0] - 1, int(n_views)
     f64, i32 = (lambda *s: T.new_empty(*s, dtype=torch.float64)), (lambda *s: T.new_empty(*s, dtype=torch.int32))
@@ -521,10 +543,10 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank),
                    ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals),
                    ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap), ("visibility", _m_visibility),
-                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("tsdf_mesh", _m_tsdf_mesh), ("pose_sync", _m_pose_sync)):
+                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("tsdf_mesh", _m_tsdf_mesh), ("tsdf_align", _m_tsdf_align), ("pose_sync", _m_pose_sync)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
        "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals",
-       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "tsdf_mesh", "pose_sync")
+       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "tsdf_mesh", "tsdf_align", "pose_sync")

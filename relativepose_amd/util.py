@@ -777,6 +777,65 @@ def tsdf_mesh_dev(state, min_weight=1, max_points=None, max_triangles=None):
     return out
 
 
+def tsdf_align_dev(state, depth, R, scene_of_view=None, iters=12, eig_min=None, stride=1, trace=False, min_weight=1):
+    """relpose_tsdf_align (include/relpose.h): refine the world -> camera poses R [V,4,4] (float64 host array or CUDA tensor)
+    of the depth panoramas depth [V,h,4h] f32 against tsdf_fuse_dev's state, so that each view's measured points lie on the zero level of the
+    volume scene_of_view[v] names (None: every view against scene 0; read on the host).  iters Gauss-Newton steps (0 scores the poses as
+    given); directions whose eigenvalue of JtJ / n_used is not above eig_min (None: _lib.TSDF_ALIGN_EIG_MIN) are held still; stride samples
+    every stride-th pixel.
+    -> {"pose" [V,4,4] f64, "eig" [V,6] f64 ascending, "held" [V] i32, "sums" [V,32] i64 (the last 4: outside, unknown, saturated, used),
+    "rms" [V,2] f64 (first and last evaluation, in units of trunc)} CUDA tensors, and with trace=True "trace_pose" [V,iters+1,4,4] and
+    "trace_sums" [V,iters+1,32].  The integer sums make the result bitwise independent of the batch.  The call waits for the stream once."""
+    import torch
+    _lib.require_gpu()
+    if depth.dim() != 3 or depth.shape[2] != 4 * depth.shape[1] or depth.dtype != torch.float32:
+        raise ValueError("tsdf_align_dev takes depth [V,h,4h] float32")
+    V, h = int(depth.shape[0]), int(depth.shape[1])
+    dev = depth.device
+    ts, wt = state["tsdf_sum"], state["weight"]
+    if ts.dim() != 4 or ts.shape != wt.shape or ts.dtype != torch.int32 or wt.dtype != torch.int32 or ts.device != dev or wt.device != dev:
+        raise ValueError("tsdf_align_dev takes tsdf_fuse_dev's state on depth's device")
+    S, nz, ny, nx = (int(v) for v in ts.shape)
+    origin = np.ascontiguousarray(state["origin"], dtype=np.float64).reshape(S, 3)
+    sov = np.zeros(V, np.int32) if scene_of_view is None else np.ascontiguousarray(
+        scene_of_view.cpu().numpy() if hasattr(scene_of_view, "cpu") else scene_of_view, dtype=np.int32).reshape(-1)
+    pose = R if hasattr(R, "data_ptr") else torch.from_numpy(np.ascontiguousarray(R, dtype=np.float64).reshape(-1, 4, 4)).to(dev)
+    if tuple(pose.shape) != (V, 4, 4) or pose.dtype != torch.float64 or pose.device != dev or len(sov) != V:
+        raise ValueError("tsdf_align_dev takes one float64 4x4 pose and one scene index per view")
+    iters, stride = int(iters), int(stride)
+    eig_min = _lib.TSDF_ALIGN_EIG_MIN if eig_min is None else float(eig_min)
+    L = _lib.lib()
+    nbytes = L.relpose_tsdf_align_workspace_bytes(S, V, h, nx, ny, nz, stride)
+    if nbytes == 0 or not 0 <= iters <= 64:
+        raise ValueError("tsdf_align_dev: sizes outside relpose_tsdf_align's limits (a dimension above 2048, more than 2^22 sampled pixels, "
+                         "stride < 1, or iters outside 0..64)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = {"pose": torch.empty(V, 4, 4, dtype=torch.float64, device=dev), "eig": torch.empty(V, 6, dtype=torch.float64, device=dev),
+           "held": torch.empty(V, dtype=torch.int32, device=dev), "sums": torch.empty(V, _lib.TSDF_ALIGN_SUMS, dtype=torch.int64, device=dev),
+           "rms": torch.empty(V, 2, dtype=torch.float64, device=dev)}
+    if trace:
+        out["trace_pose"] = torch.empty(V, iters + 1, 4, 4, dtype=torch.float64, device=dev)
+        out["trace_sums"] = torch.empty(V, iters + 1, _lib.TSDF_ALIGN_SUMS, dtype=torch.int64, device=dev)
+    tsc, wtc, dc, pc_ = ts.contiguous(), wt.contiguous(), depth.contiguous(), pose.contiguous()
+    a = _lib.TsdfAlignArgs()
+    a.struct_size = _lib.C.sizeof(_lib.TsdfAlignArgs)
+    a.n_scenes, a.n_views, a.h, a.dataset = S, V, h, dataset_id(state["dataset"])
+    a.nx, a.ny, a.nz, a.min_weight, a.iters, a.stride = nx, ny, nz, int(min_weight), iters, stride
+    a.tsdf_sum, a.weight, a.depth, a.pose = tsc.data_ptr(), wtc.data_ptr(), dc.data_ptr(), pc_.data_ptr()
+    a.origin_host, a.scene_of_view_host = origin.ctypes.data, sov.ctypes.data
+    a.voxel, a.eig_min = float(state["voxel"]), eig_min
+    a.pose_out, a.eig, a.held, a.sums, a.rms = (out[k].data_ptr() for k in ("pose", "eig", "held", "sums", "rms"))
+    a.trace_pose, a.trace_sums = (out["trace_pose"].data_ptr(), out["trace_sums"].data_ptr()) if trace else (0, 0)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.stream = _lib.stream_ptr()
+    rc_ = L.relpose_tsdf_align(_lib.C.byref(a))
+    if rc_ == -1:
+        raise ValueError("relpose_tsdf_align: invalid arguments (a scene index outside 0..S-1, min_weight < 1, eig_min negative or not finite, "
+                         "a non-finite origin, voxel not > 0, or sizes outside the limits)")
+    _lib.check(rc_, "relpose_tsdf_align")
+    return out
+
+
 def tsdf_bounds_dev(depth, R, dataset, voxel, pad=3, view_begin=None):
     """The box tsdf_fuse_dev should be given: per scene, around every pixel with data of its views unprojected (pano2pc_dev) and moved into the
     world frame by the inverse of its pose R [V,4,4] (host float64, world -> camera), widened by `pad` voxels on every side.
