@@ -1211,6 +1211,88 @@ typedef struct RelposeTsdfAlignArgs {
 size_t relpose_tsdf_align_workspace_bytes(int32_t n_scenes, int32_t n_views, int32_t h, int32_t nx, int32_t ny, int32_t nz, int32_t stride);
 int relpose_tsdf_align(const RelposeTsdfAlignArgs* args);
 
+/* What the fused model looks like from a pose: depth, normal and colour panoramas of n_views views, each marched through the volume of
+ * relpose_tsdf_fuse's state it names.  The contract is the project's own (tests/render_model.py restates it in numpy, on
+ * whole arrays and as a plain loop per ray).  One plain march defines every output bit; the one optimisation, skipping empty space, cannot
+ * change a bit (the proof is in DESIGN.md 4.20).  The geometry is float64, every operation rounded on its own, + - * / sqrt floor only.
+ * A pixel depends on its own ray and the volume alone: no atomics, bitwise repeatable, independent of the batch around a view and of skip.
+ *
+ *   tsdf_sum, weight [n_scenes, nz, ny, nx] i32, color_sum [n_scenes, 3, nz, ny, nx] u32 or NULL, origin_host [n_scenes, 3] f64 (HOST), voxel,
+ *                    min_weight (>= 1): relpose_tsdf_fuse's state
+ *   pose             [n_views, 4, 4] f64 row-major on the DEVICE, world -> camera (the last row is not read)
+ *   scene_of_view_host [n_views] i32 in HOST memory, each in 0 .. n_scenes-1: several views may name one volume, a volume may have none
+ *   ray              pixel (row, col) of the [h, 4h] panorama: slot = col / h, px = col - slot h, xn = (2.0 * px) / h - 1.0,
+ *                    yn = 1.0 - (2.0 * row) / h, dir = Rs[face(dataset, slot)] (xn, yn, -1) (a signed permutation: exact): the ray
+ *                    relpose_tsdf_align unprojects.  Column 0 of a slot and row 0 lie on the face's open edge (xn = -1, yn = 1); they are
+ *                    rendered like any other pixel, as alignment uses them.  W = the rigid inverse of the pose as relpose_tsdf_align
+ *                    writes it out.  Sample k (0 <= k < n_steps) lies at face depth d_k = d_min + (double)k * step: the camera point
+ *                    (x, y, z) = (d_k dir_0, d_k dir_1, d_k dir_2), the world point q_a = ((W_a0 x + W_a1 y) + W_a2 z) + W_a3.
+ *   sample           u_a = (q_a - origin_a) / voxel - 0.5, i0_a = floor(u_a), f_a = u_a - i0_a.  The sample is IN RANGE iff q is finite and
+ *                    0 <= i0_a <= n_a - 2 on every axis; it is VALID iff it is in range, it is evaluated (below) and each of the 8 corners
+ *                    i0 + (c & 1, c >> 1 & 1, c >> 2 & 1) has weight >= min_weight.  Its value t is the trilinear interpolation of
+ *                    t_c = (double)tsdf_sum / (32768.0 * (double)weight) and its gradient g = (gx, gy, gz), in relpose_tsdf_align's order:
+ *                      d00 = t1 - t0, d10 = t3 - t2, d01 = t5 - t4, d11 = t7 - t6;  a00 = t0 + fx d00, a10 = t2 + fx d10, a01 = t4 + fx d01,
+ *                      a11 = t6 + fx d11;  c0 = a10 - a00, c1 = a11 - a01;  b0 = a00 + fy c0, b1 = a01 + fy c1;
+ *                      gz = b1 - b0;  t = b0 + fz gz;  gy = c0 + fz (c1 - c0);  e0 = d00 + fy (d10 - d00), e1 = d01 + fy (d11 - d01);
+ *                      gx = e0 + fz (e1 - e0).      A corner with |t_c| >= 1 (saturated) is an ordinary value here.
+ *                    The colour of a sample is the same rule for t on c_c = (double)color_sum / (255.0 * (double)weight), per channel.
+ *   march            for k = 1, 2, .. n_steps-1 the FIRST pair (k-1, k) of valid samples with t_{k-1} >= 0 && t_k < 0 or
+ *                    t_{k-1} < 0 && t_k >= 0 ends the ray.  The first: a HIT, cls = 1, s = t_{k-1} / (t_{k-1} - t_k),
+ *                    depth = (float)(d_{k-1} + s * step); the normal is n = g_{k-1} + s * (g_k - g_{k-1}) per component, divided by
+ *                    sqrt((nx nx + ny ny) + nz nz) unless that is 0, then rotated into the camera frame by the pose's rotation
+ *                    R_ij = W_ji, (float)((R_i0 nx + R_i1 ny) + R_i2 nz): the frame relpose_depth_normals writes; it points where t grows,
+ *                    towards the space the sensors saw through.  colour = (float)(c_{k-1} + s * (c_k - c_{k-1})) per channel.
+ *                    The second: a BACK FACE, cls = 2: the ray left a solid, no data.  No such pair: a MISS, cls = 0.  A pair with a
+ *                    sample that is not valid never ends a ray: no surface is invented across unknown space.  Without a hit depth,
+ *                    normal and colour are 0: depth 0 is "no data", the rule of every consumer of a depth panorama.
+ *   skip             0: every in-range sample is evaluated (its sixteen loads are made).  1: a first launch sets one flag byte per brick
+ *                    of 8 x 8 x 8 cells (cell i0 lies in brick i0 / 8 per axis) iff one of the brick's cells has a corner voxel with
+ *                    weight >= min_weight and tsdf_sum < 0; an in-range sample k is evaluated iff the cell of sample k-1, k or k+1 (those
+ *                    of them that exist, 0 .. n_steps-1, and are in range) lies in a flagged brick.  Every output but n_evaluated is bit for
+ *                    bit what skip = 0 gives.
+ *   outputs          depth [n_views, h, 4h] f32; cls [n_views, h, 4h] u8; optional (NULL: not written) normal [n_views, 3, h, 4h] f32,
+ *                    color [n_views, 3, h, 4h] f32 (needs color_sum), n_evaluated [n_views, h, 4h] i32: the number of samples evaluated
+ *                    up to and including the one that ended the ray, under the mode in force.
+ *   limits           relpose_tsdf_fuse's for h, n_views and the volume; 3 nx ny nz < 2^31; d_min >= 0 and step > 0, both finite;
+ *                    1 <= n_steps <= 65536; skip 0 or 1; min_weight >= 1; voxel finite > 0; origin finite.  A volume with a dimension of 1
+ *                    has no cells: every pixel is a miss.  A pose with a NaN or an inf makes every world point non-finite: all misses.
+ *   workspace        relpose_tsdf_render_workspace_bytes(n_scenes, n_views, h, nx, ny, nz) bytes (0 for sizes outside the limits), 256-byte
+ *                    aligned: the device copies of origin and scene_of_view, and the brick flags
+ * The kernels restrict each march to a conservative clip of the ray against the box; samples outside it are out of range, so the plain
+ * loop above stays the definition.  Invalid arguments return RELPOSE_EINVAL before anything is enqueued or any output is touched.  One
+ * launch, two with skip, whatever n_views is.  The call waits for `stream` once, at its end. */
+typedef struct RelposeTsdfRenderArgs {
+    uint32_t struct_size;       /* sizeof(RelposeTsdfRenderArgs) as the caller compiled it */
+    int32_t n_scenes;
+    int32_t n_views;
+    int32_t h;
+    int32_t dataset;
+    int32_t nx, ny, nz;
+    int32_t min_weight;
+    int32_t n_steps;
+    int32_t skip;
+    int32_t reserved0;
+    const int32_t* tsdf_sum;
+    const int32_t* weight;
+    const uint32_t* color_sum;
+    const double* pose;
+    const double* origin_host;
+    const int32_t* scene_of_view_host;
+    double voxel;
+    double d_min;
+    double step;
+    float* depth;
+    uint8_t* cls;
+    float* normal;
+    float* color;
+    int32_t* n_evaluated;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeTsdfRenderArgs;
+size_t relpose_tsdf_render_workspace_bytes(int32_t n_scenes, int32_t n_views, int32_t h, int32_t nx, int32_t ny, int32_t nz);
+int relpose_tsdf_render(const RelposeTsdfRenderArgs* args);
+
 /* -------------------------------------------------------------------- robust synchronisation of pose graphs
  * The pair drivers give a relative pose per pair of views; some are grossly wrong.  relpose_pose_sync turns the relative poses of n_scenes
  * scenes into one absolute pose per view and one confidence per relative pose: graduated Geman-McClure re-weighting around a linearised

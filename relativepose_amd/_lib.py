@@ -232,6 +232,16 @@ class TsdfAlignArgs(C.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
 
 
+class TsdfRenderArgs(C.Structure):
+    """RelposeTsdfRenderArgs (include/relpose.h): the argument block of relpose_tsdf_render."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("n_views", c_int), ("h", c_int), ("dataset", c_int), ("nx", c_int),
+                ("ny", c_int), ("nz", c_int), ("min_weight", c_int), ("n_steps", c_int), ("skip", c_int), ("reserved0", c_int),
+                ("tsdf_sum", c_void_p), ("weight", c_void_p), ("color_sum", c_void_p), ("pose", c_void_p), ("origin_host", c_void_p),
+                ("scene_of_view_host", c_void_p), ("voxel", c_double), ("d_min", c_double), ("step", c_double), ("depth", c_void_p),
+                ("cls", c_void_p), ("normal", c_void_p), ("color", c_void_p), ("n_evaluated", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
 class PoseSyncArgs(C.Structure):
     """RelposePoseSyncArgs (include/relpose.h): the argument block of relpose_pose_sync."""
     _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("n_views", c_int), ("n_edges", c_int), ("n_final", c_int), ("robust", c_int),
@@ -247,6 +257,7 @@ SYNC_MAX_EDGES = 4096               # RELPOSE_SYNC_MAX_EDGES, per scene
 TSDF_MAX_VIEWS = 4096               # per scene per relpose_tsdf_fuse call
 TSDF_MAX_WEIGHT = 65535             # the caller's bound on a voxel's weight across accumulating calls
 TSDF_ALIGN_EIG_MIN = 0.0043         # relpose_tsdf_align's eigenvalue floor: between the two ranges measured in DESIGN.md 4.19
+TSDF_RENDER_MAX_STEPS = 65536        # relpose_tsdf_render's bound on n_steps
 TSDF_ALIGN_SUMS = 32                # 21 JtJ + 6 Jtr + r^2 + the counts of outside, unknown, saturated and used points
 
 
@@ -314,6 +325,8 @@ SIGNATURES = {
     "relpose_tsdf_mesh": (c_int, [C.POINTER(TsdfMeshArgs)]),
     "relpose_tsdf_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "relpose_tsdf_align": (c_int, [C.POINTER(TsdfAlignArgs)]),
+    "relpose_tsdf_render_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "relpose_tsdf_render": (c_int, [C.POINTER(TsdfRenderArgs)]),
     "relpose_pose_sync_workspace": (c_size_t, [c_int, c_int, c_int]),
     "relpose_pose_sync": (c_int, [C.POINTER(PoseSyncArgs)]),
     "relpose_scnet_create": (c_void_p, [c_int, c_int]),

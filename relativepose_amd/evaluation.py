@@ -28,6 +28,9 @@ unchanged" is realised by the build's own eval_pairs-style harness).
   refine_scene / leave_one_out_state, evaluate_scenes(refine=...)
                           no counterpart: the views' poses refined against the volume the other views fuse into, frame to model
                           (util.tsdf_align_dev)
+  render_views / render_scores / render_summary, evaluate_scenes(render=...)
+                          no counterpart: the fused volume rendered back into depth, normal and colour panoramas from given poses and
+                          compared with the scans pixel by pixel (util.tsdf_render_dev)
   synchronize_scene / absolute_pose_errors / evaluate_scenes / scenes_summary
                           no counterpart: a scene's relative poses synchronised into one pose per view, which pair estimates that
                           distrusts, and the scene fused under the result (util.pose_graph / pose_sync_dev)
@@ -308,6 +311,48 @@ def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, m
     points, normals, colors, valid, n = util.tsdf_surface_dev(state, min_weight, max_points)
     return {"points": points, "normals": normals, "colors": colors, "valid": valid, "n_points": n, "origin": origin, "dims": dims,
             "voxel": float(voxel), "state": state}
+
+
+def render_views(state, R, dataset=None, h=160, scene_of_view=None, **kw):
+    """What the fused model looks like from the world -> camera poses R [V,4,4]: `state` is util.tsdf_fuse_dev's (or
+    fuse_views(...)["state"]); dataset defaults to the state's; kw goes to util.tsdf_render_dev (d_min, d_max, step, min_weight, skip).
+    -> {"depth" [V,h,4h] f32 (0 = no data), "normal" [V,3,h,4h] f32 (camera frame), "color" [V,3,h,4h] f32 or None, "cls" [V,h,4h] u8}: the
+    triple RelativePosePipeline.prepare, util.depth_normals_dev, util.visibility_dev and util.tsdf_fuse_dev take."""
+    from . import util
+    depth, normal, color, cls = util.tsdf_render_dev(state, R, state["dataset"] if dataset is None else dataset, h, scene_of_view, **kw)
+    return {"depth": depth, "normal": normal, "color": color, "cls": cls}
+
+
+def render_scores(rendered_depth, cls, measured_depth, voxel):
+    """A rendered model view against the scan it stands for, pixel by pixel: -> ((median, p90) of |rendered - measured| in voxels over the
+    pixels where both have data (the render a hit, the scan finite and > 0; NaN without such a pixel), coverage = hits / measured pixels: above 1
+    where the model fills more holes of the scan than it leaves)."""
+    import torch
+    rd = torch.as_tensor(rendered_depth)
+    md, hit = torch.as_tensor(measured_depth).to(rd.device), torch.as_tensor(cls).to(rd.device) == 1
+    have = torch.isfinite(md) & (md > 0)
+    both = hit & have
+    err = ((rd[both].double() - md[both].double()).abs() / float(voxel)).cpu().numpy()
+    n = int(have.sum().item())
+    med, p90 = (float(np.median(err)), float(np.percentile(err, 90))) if err.size else (float("nan"), float("nan"))
+    return (med, p90), (int(hit.sum().item()) / n if n else float("nan"))
+
+
+def render_summary(parts, voxel):
+    """[(rendered depth, cls, measured depth)] of several scenes -> the CLI's three fields over all their pixels"""
+    import torch
+    if not parts:
+        return {"render_depth_err_median": float("nan"), "render_depth_err_p90": float("nan"), "render_coverage": float("nan")}
+    (med, p90), cov = render_scores(torch.cat([p[0].reshape(-1) for p in parts]), torch.cat([p[1].reshape(-1) for p in parts]),
+                                    torch.cat([p[2].reshape(-1) for p in parts]), voxel)
+    return {"render_depth_err_median": med, "render_depth_err_p90": p90, "render_coverage": cov}
+
+
+def save_render(path, rv):
+    """<exp>.scene<k>.render.npz: depth, normal, colour and cls of render_views"""
+    np.savez(path, depth=rv["depth"].cpu().numpy(), normal=rv["normal"].cpu().numpy(), cls=rv["cls"].cpu().numpy(),
+             color=np.zeros(0, np.float32) if rv["color"] is None else rv["color"].cpu().numpy())
+    return path
 
 
 def leave_one_out_state(state_all, state_solo):
@@ -810,7 +855,7 @@ SCENE_BAD_ROT, SCENE_BAD_TRANS = 10.0, 0.3       # a pair estimate is wrong beyo
 
 
 def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, dataset=None, keypoints=200, seed=0, exp=None, mesh=False, refine=0,
-                    **sync):
+                    render=False, **sync):
     """Scenes of posed views -> estimated pairs -> synchronised absolute poses -> what they do to the reconstruction.
     scenes: synth.render_scene dicts; pipe_or_method: a RelativePosePipeline, or "fgs" / "gs" / "cgs" (then `dataset` names the scenes').
     Per scene: mine_pairs, the pair method on the mined pairs through evaluate_pairs / evaluate_fgs / _gs / _cgs as they are (verify and
@@ -826,7 +871,10 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
     refine=rounds (with fuse): the largest component's synchronised poses are refined against the fused volume (refine_scene,
     re-gauged to the component's first view) before the final fusion, which then uses them; the record gains 'refine_rounds',
     'refine_err_rot' / 'refine_err_t' [2, views] (absolute_pose_errors before and after), 'refine_wall_median' [2] (the surface's median
-    distance to the room's walls in voxels, for scenes that carry "half"), 'refine_held_views'.  refine=0: nothing changes."""
+    distance to the room's walls in voxels, for scenes that carry "half"), 'refine_held_views'.  refine=0: nothing changes.
+    render=True (with fuse): every fused view is rendered from its final pose against the final volume (render_views); the
+    record gains 'render' = (rendered depth, cls, the view's own depth) on the device for render_summary, and with exp
+    <exp>.scene<k>.render.npz is written.  render=False: nothing changes."""
     import torch
     from . import synth, util
     method = pipe_or_method if isinstance(pipe_or_method, str) else None
@@ -910,6 +958,11 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
             if exp is not None:
                 rec['fuse_ply'] = f"{exp}.scene{k}.ply"
                 util.save_ply(rec['fuse_ply'], est["points"][0, :n], est["normals"][0, :n], est["colors"][0, :n])
+            if render:
+                rv = render_views(est["state"], pose_est, ds, int(depth.shape[1]))
+                rec['render'] = (rv["depth"], rv["cls"], depth)
+                if exp is not None:
+                    rec['render_npz'] = save_render(f"{exp}.scene{k}.render.npz", rv)
             if mesh:
                 rec['mesh'] = mesh_stats(est)[0]
                 if exp is not None:
@@ -1275,6 +1328,12 @@ def _cli_parser_completion():
                     help="--mine-pairs --fuse VOXEL / --reconstruct --fuse VOXEL: also extract each fused scene's triangle mesh (marching cubes, "
                          "DESIGN.md 4.18); the JSON line gains the medians of mesh_stats (triangles, area, border edges) and the number of "
                          "non-manifold edges, and <exp>.scene<k>.mesh.ply is written next to the cloud when --exp is given")
+    ap.add_argument("--render", action="store_true",
+                    help="--mine-pairs --fuse VOXEL / --reconstruct --fuse VOXEL: render every view of a scene from its pose (ground truth for "
+                         "--mine-pairs, the final poses for --reconstruct) against the final volume (util.tsdf_render_dev, DESIGN.md 4.20) and "
+                         "compare the depth panoramas with the scans pixel by pixel; the JSON line gains render_depth_err_median / _p90 "
+                         "(voxels, where both have data) and render_coverage (hits / measured pixels), and <exp>.scene<k>.render.npz (depth, "
+                         "normal, color, cls) is written when --exp is given")
     return ap
 
 
@@ -1313,6 +1372,9 @@ def main(argv=None):
     if args.mesh and (args.fuse is None or not (args.mine_pairs or args.reconstruct)):
         raise SystemExit("--mesh applies to --mine-pairs --fuse VOXEL and to --reconstruct --fuse VOXEL")
 
+    if args.render and (args.fuse is None or not (args.mine_pairs or args.reconstruct)):
+        raise SystemExit("--render applies to --mine-pairs --fuse VOXEL and to --reconstruct --fuse VOXEL")
+
     if args.refine and (args.refine < 0 or args.fuse is None or not args.reconstruct):
         raise SystemExit("--refine takes a number of rounds >= 0 and applies to --reconstruct --fuse VOXEL")
 
@@ -1343,13 +1405,16 @@ def main(argv=None):
         t0 = time.perf_counter()
         scenes = [synth.render_scene(args.seed + s, args.scene_views, ds) for s in range(args.scenes)]
         recs = evaluate_scenes(who, scenes, dev, verify=args.verify, fuse=args.fuse, dataset=ds, keypoints=args.keypoints, seed=args.seed,
-                               exp=args.exp, mesh=args.mesh, refine=args.refine)
+                               exp=args.exp, mesh=args.mesh, refine=args.refine, render=args.render)
         torch.cuda.synchronize()
         line = {"reconstruct": True, "method": args.method, "dataset": ds, "scenes": args.scenes, "views": args.scene_views,
                 "seconds": time.perf_counter() - t0, "verify": args.verify, "fuse": args.fuse}
         if args.refine:
             line["refine"] = args.refine
         line.update(scenes_summary(recs))
+        if args.render:
+            line.update(render_summary([r['render'] for r in recs if 'render' in r], args.fuse),
+                        render_npz=[r['render_npz'] for r in recs if 'render_npz' in r])
         print(json.dumps(line), flush=True)
         return
 
@@ -1364,6 +1429,7 @@ def main(argv=None):
         entries = []
         wall, fuse_points, plys = [], 0, []
         meshes, mesh_plys = [], []
+        renders, render_npz = [], []
         t0 = time.perf_counter()
         for s in range(args.scenes):
             sc = synth.render_scene(args.seed + s, args.scene_views, args.dataset)
@@ -1380,6 +1446,12 @@ def main(argv=None):
                 if args.exp is not None:
                     plys.append(f"{args.exp}.scene{s}.ply")
                     util.save_ply(plys[-1], pts, surf["normals"][0, :n], surf["colors"][0, :n])
+                if args.render:
+                    dm = up(sc["depth"])
+                    rv = render_views(surf["state"], sc["R"], args.dataset, int(dm.shape[1]))
+                    renders.append((rv["depth"], rv["cls"], dm))
+                    if args.exp is not None:
+                        render_npz.append(save_render(f"{args.exp}.scene{s}.render.npz", rv))
                 if args.mesh:
                     meshes.append(mesh_stats(surf)[0])
                     if args.exp is not None:
@@ -1401,6 +1473,8 @@ def main(argv=None):
                         fuse_wall_err_p90=float(np.percentile(e, 90)) if e.size else float("nan"), fuse_points=fuse_points, fuse_ply=plys)
         if args.mesh:
             line.update(mesh_summary(meshes), mesh_ply=mesh_plys)
+        if args.render:
+            line.update(render_summary(renders, args.fuse), render_npz=render_npz)
         print(json.dumps(line), flush=True)
         return
 

@@ -43,6 +43,7 @@ Operator                    replaces (reference file:line)
   overlap                   the two KDTree queries of util.point_cloud_overlap, util.py:21-40 (batched over directed cloud pairs, one grid per cloud)
   visibility                no counterpart: the free-space check of a relative pose against the partner's depth panorama
   tsdf_align                no counterpart: view poses refined against the fused TSDF volume, frame-to-model Gauss-Newton
+  tsdf_render               no counterpart: depth, normal and colour panoramas marched out of the fused TSDF volume
   tsdf_mesh                 no counterpart: tsdf_surface's cloud plus the triangles of a marching-cubes mesh over the same volume
   tsdf_fuse, tsdf_surface   no counterpart: posed depth panoramas merged into a TSDF volume and its surface cloud
   pose_sync                 no counterpart: the relative poses of a scene's pairs synchronised into one pose per view
@@ -129,6 +130,12 @@ _lib.define("tsdf_mesh(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Tensor
 _lib.define("tsdf_align(Tensor tsdf_sum, Tensor weight, Tensor origin, float voxel, Tensor depth, Tensor pose, Tensor scene_of_view, int dataset, "
             "int iters=12, float eig_min=0.0043, int stride=1, int min_weight=1, bool trace=False) "
             "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+# the state of tsdf_fuse (color_sum optional), pose f64 [V,4,4] world -> camera, scene_of_view integer [V] (read on the host) -> depth f32 [V,h,4h],
+# normal f32 [V,3,h,4h], color f32 [V,3,h,4h] (empty without color_sum), cls u8 [V,h,4h], n_evaluated i32 [V,h,4h] (empty without stages).
+# d_max = 0 and step = 0 stand for the defaults: the box diagonal and half a voxel
+_lib.define("tsdf_render(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Tensor origin, float voxel, Tensor pose, Tensor scene_of_view, "
+            "int dataset, int h, float d_min=0.0, float d_max=0.0, float step=0.0, int min_weight=1, bool skip=True, bool stages=False) "
+            "-> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 # T f64 [E,4,4], src / dst integer [E] (local to the scene), w0 f64 [E], view_begin / edge_begin integer [S+1] (read on the host), n_views =
 # view_begin[-1] (an argument so that the Meta function knows the shapes) -> pose f64 [V,4,4],
 # component i32 [V], tree, edge_state i32 [E], confidence, res_rot, res_trans f64 [E], n_components i32 [S], cost, last_step f64 [S]
@@ -322,6 +329,16 @@ def _tsdf_align(tsdf_sum, weight, origin, voxel, depth, pose, scene_of_view, dat
             o["trace_sums"] if trace else depth.new_empty(0, dtype=torch.int64))
 
 
+def _tsdf_render(tsdf_sum, weight, color_sum, origin, voxel, pose, scene_of_view, dataset, h, d_min=0.0, d_max=0.0, step=0.0, min_weight=1, skip=True,
+                 stages=False):
+    S, nz, ny, nx = tsdf_sum.shape
+    st = {"tsdf_sum": tsdf_sum, "weight": weight, "color_sum": color_sum, "origin": origin.cpu().numpy(), "dims": (nx, ny, nz), "voxel": float(voxel)}
+    o = _util.tsdf_render_dev(st, pose, _INV_DATASET[int(dataset)], int(h), scene_of_view, float(d_min), None if float(d_max) == 0.0 else float(d_max),
+                              None if float(step) == 0.0 else float(step), int(min_weight), bool(skip), bool(stages))
+    return (o[0], o[1], tsdf_sum.new_empty(0, dtype=torch.float32) if o[2] is None else o[2], o[3],
+            o[4] if stages else tsdf_sum.new_empty(0, dtype=torch.int32))
+
+
 POSE_SYNC_OUTPUTS = ("pose", "component", "tree", "edge_state", "confidence", "res_rot", "res_trans", "n_components", "cost", "last_step")
 
 
@@ -356,7 +373,8 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank),
                    ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals),
                    ("frames_to_pano", _frames_to_pano), ("overlap", _overlap), ("visibility", _visibility),
-                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("tsdf_mesh", _tsdf_mesh), ("tsdf_align", _tsdf_align), ("pose_sync", _pose_sync)):
+                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("tsdf_mesh", _tsdf_mesh), ("tsdf_align", _tsdf_align), ("tsdf_render", _tsdf_render),
+                   ("pose_sync", _pose_sync)):
     _lib.impl(_name, _fn, "CUDA")
 
 
@@ -517,6 +535,14 @@ def _m_tsdf_align(tsdf_sum, weight, origin, voxel, depth, pose, scene_of_view, d
             n(torch.float64, V, E, 4, 4) if trace else n(torch.float64, 0), n(torch.int64, V, E, 32) if trace else n(torch.int64, 0))
 
 
+def _m_tsdf_render(tsdf_sum, weight, color_sum, origin, voxel, pose, scene_of_view, dataset, h, d_min=0.0, d_max=0.0, step=0.0, min_weight=1, skip=True,
+                   stages=False):
+    V, h = pose.shape[0], int(h)
+    n = lambda dt, *s: tsdf_sum.new_empty(*s, dtype=dt)
+    return (n(torch.float32, V, h, 4 * h), n(torch.float32, V, 3, h, 4 * h), n(torch.float32, 0) if color_sum is None else n(torch.float32, V, 3, h, 4 * h),
+            n(torch.uint8, V, h, 4 * h), n(torch.int32, V, h, 4 * h) if stages else n(torch.int32, 0))
+
+
 def _m_pose_sync(T, src, dst, w0, view_begin, edge_begin, n_views, sigma_r=0.1, sigma_t=0.1, mu0=64.0, div=1.4, n_final=10, robust=True):
     E, S, V = T.shape[0], view_begin.shape[0] - 1, int(n_views)
     f64, i32 = (lambda *s: T.new_empty(*s, dtype=torch.float64)), (lambda *s: T.new_empty(*s, dtype=torch.int32))
@@ -543,10 +569,11 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank),
                    ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals),
                    ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap), ("visibility", _m_visibility),
-                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("tsdf_mesh", _m_tsdf_mesh), ("tsdf_align", _m_tsdf_align), ("pose_sync", _m_pose_sync)):
+                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("tsdf_mesh", _m_tsdf_mesh), ("tsdf_align", _m_tsdf_align), ("tsdf_render", _m_tsdf_render),
+                   ("pose_sync", _m_pose_sync)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
        "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals",
-       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "tsdf_mesh", "tsdf_align", "pose_sync")
+       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "tsdf_mesh", "tsdf_align", "tsdf_render", "pose_sync")

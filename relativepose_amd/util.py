@@ -836,6 +836,75 @@ def tsdf_align_dev(state, depth, R, scene_of_view=None, iters=12, eig_min=None, 
     return out
 
 
+def tsdf_render_steps(dims, voxel, d_min=0.0, d_max=None, step=None):
+    """tsdf_render_dev's host rule -> (step, n_steps): step defaults to half a voxel, d_max to the box diagonal; the samples d_min + k step
+    reach up to d_max, at least one and at most _lib.TSDF_RENDER_MAX_STEPS."""
+    voxel = float(voxel)
+    step = 0.5 * voxel if step is None else float(step)
+    if d_max is None:
+        d_max = float(np.sqrt(sum((float(n) * voxel) ** 2 for n in dims)))
+    if not (np.isfinite(step) and step > 0 and np.isfinite(d_max) and np.isfinite(d_min)):
+        raise ValueError("tsdf_render_dev: d_min, d_max and step must be finite and step > 0")
+    return step, int(min(max(np.floor((float(d_max) - float(d_min)) / step) + 1, 1), _lib.TSDF_RENDER_MAX_STEPS))
+
+
+def tsdf_render_dev(state, R, dataset, h, scene_of_view=None, d_min=0.0, d_max=None, step=None, min_weight=1, skip=True, stages=False,
+                    normal=True, color=True):
+    """relpose_tsdf_render (include/relpose.h): what tsdf_fuse_dev's state looks like from the world -> camera poses R [V,4,4]
+    (float64 host array or CUDA tensor): one [h,4h] panorama per view, marched through the volume scene_of_view[v] names (None: every view
+    against scene 0; read on the host).  The samples lie at face depth d_min + k step, k < n_steps, up to d_max (tsdf_render_steps: step
+    defaults to half a voxel, d_max to the box diagonal).  skip=True skips empty space brick by brick; it changes no output bit.
+    -> (depth [V,h,4h] f32 with 0 = no data, normal [V,3,h,4h] f32 in the camera frame or None, color [V,3,h,4h] f32 or None (a state without
+    colours, or color=False), cls [V,h,4h] u8: 0 miss, 1 hit, 2 back face) CUDA tensors, and with stages=True also n_evaluated [V,h,4h] i32,
+    the samples each ray evaluated.  A view's image does not depend on the batch.  The call waits for the stream once."""
+    import torch
+    _lib.require_gpu()
+    ts, wt, cs = state["tsdf_sum"], state["weight"], state.get("color_sum")
+    dev = ts.device
+    if ts.dim() != 4 or ts.shape != wt.shape or ts.dtype != torch.int32 or wt.dtype != torch.int32 or wt.device != dev:
+        raise ValueError("tsdf_render_dev takes tsdf_fuse_dev's state")
+    S, nz, ny, nx = (int(v) for v in ts.shape)
+    if cs is not None and (tuple(cs.shape) != (S, 3, nz, ny, nx) or cs.dtype != torch.int32 or cs.device != dev):
+        raise ValueError("tsdf_render_dev takes color_sum [S,3,nz,ny,nx] int32 on the state's device")
+    origin = np.ascontiguousarray(state["origin"], dtype=np.float64).reshape(S, 3)
+    pose = R if hasattr(R, "data_ptr") else torch.from_numpy(np.ascontiguousarray(R, dtype=np.float64).reshape(-1, 4, 4)).to(dev)
+    V, h = int(pose.shape[0]), int(h)
+    sov = np.zeros(V, np.int32) if scene_of_view is None else np.ascontiguousarray(
+        scene_of_view.cpu().numpy() if hasattr(scene_of_view, "cpu") else scene_of_view, dtype=np.int32).reshape(-1)
+    if pose.dim() != 3 or tuple(pose.shape[1:]) != (4, 4) or pose.dtype != torch.float64 or pose.device != dev or len(sov) != V:
+        raise ValueError("tsdf_render_dev takes one float64 4x4 pose and one scene index per view")
+    step, n_steps = tsdf_render_steps((nx, ny, nz), state["voxel"], d_min, d_max, step)
+    L = _lib.lib()
+    nbytes = L.relpose_tsdf_render_workspace_bytes(S, V, h, nx, ny, nz)
+    if nbytes == 0:
+        raise ValueError("tsdf_render_dev: sizes outside relpose_tsdf_render's limits (no view, h odd or above 8192, 2^31 pixels or voxels)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    colours = color and cs is not None
+    depth = torch.empty(V, h, 4 * h, dtype=torch.float32, device=dev)
+    cls = torch.empty(V, h, 4 * h, dtype=torch.uint8, device=dev)
+    nrm = torch.empty(V, 3, h, 4 * h, dtype=torch.float32, device=dev) if normal else None
+    col = torch.empty(V, 3, h, 4 * h, dtype=torch.float32, device=dev) if colours else None
+    nev = torch.empty(V, h, 4 * h, dtype=torch.int32, device=dev) if stages else None
+    tsc, wtc, csc, pc_ = ts.contiguous(), wt.contiguous(), (None if cs is None else cs.contiguous()), pose.contiguous()
+    a = _lib.TsdfRenderArgs()
+    a.struct_size = _lib.C.sizeof(_lib.TsdfRenderArgs)
+    a.n_scenes, a.n_views, a.h, a.dataset = S, V, h, dataset_id(dataset)
+    a.nx, a.ny, a.nz, a.min_weight, a.n_steps, a.skip = nx, ny, nz, int(min_weight), n_steps, int(bool(skip))
+    a.tsdf_sum, a.weight, a.color_sum, a.pose = tsc.data_ptr(), wtc.data_ptr(), (0 if csc is None else csc.data_ptr()), pc_.data_ptr()
+    a.origin_host, a.scene_of_view_host = origin.ctypes.data, sov.ctypes.data
+    a.voxel, a.d_min, a.step = float(state["voxel"]), float(d_min), step
+    a.depth, a.cls = depth.data_ptr(), cls.data_ptr()
+    a.normal, a.color, a.n_evaluated = (0 if t is None else t.data_ptr() for t in (nrm, col, nev))
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.stream = _lib.stream_ptr()
+    rc_ = L.relpose_tsdf_render(_lib.C.byref(a))
+    if rc_ == -1:
+        raise ValueError("relpose_tsdf_render: invalid arguments (a scene index outside 0..S-1, min_weight < 1, d_min negative, a non-finite "
+                         "origin, voxel not > 0, or sizes outside the limits)")
+    _lib.check(rc_, "relpose_tsdf_render")
+    return (depth, nrm, col, cls, nev) if stages else (depth, nrm, col, cls)
+
+
 def tsdf_bounds_dev(depth, R, dataset, voxel, pad=3, view_begin=None):
     """The box tsdf_fuse_dev should be given: per scene, around every pixel with data of its views unprojected (pano2pc_dev) and moved into the
     world frame by the inverse of its pose R [V,4,4] (host float64, world -> camera), widened by `pad` voxels on every side.
