@@ -1472,6 +1472,15 @@ int relpose_scnet_forward(RelposeSCNet* net, const float* x, float* out, int32_t
  *                         Contract: two forwards on one workspace that carry the same non-zero tag have identical channels 0:8 (the caller
  *                         draws a fresh tag whenever it rewrites them); set_param / finalize / set_precision drop the cache.
  *                         RELPOSE_FWD_ZERO_WARP forwards always compute (and cache) the self streams.
+ *                         The flags of the forward that filled the cache do not matter.  Everything head-independent (the self members of
+ *                         conv1-3, their scale / shift, conv4's self slices and row maps) is taken from the workspace whichever outputs the
+ *                         filling forward computed; the skip-connection halves are kept per skip head (rgb, n, d), each in a slot of its own,
+ *                         and the record says which heads the filling forward stored.  A forward WITHOUT RELPOSE_FWD_POSE_OUTPUTS behind a
+ *                         fill WITH it (the last level of a step whose earlier levels asked for the pose outputs only) is therefore cached
+ *                         too: it takes the n and d halves from the workspace and computes the rgb head's halves (deconv3rgb, deconv2rgb, the
+ *                         rgb lines of the 1x1 heads) in the full forward's order, storing nothing.  Cached forwards never change the record,
+ *                         and a pose-outputs forward never writes an rgb slot: full, pose, full under one tag -> the third forward still
+ *                         starts from the first one's rgb halves.  Every such forward is bitwise the tag-less full forward of its input.
  *   workspace_generation  the caller's name for THIS ALLOCATION of `workspace` (e.g. a counter bumped whenever the buffer is re-allocated),
  *                         sent with every call: the self-stream cache is used only when the previous forward on the pointer carried the
  *                         same generation -- a workspace re-created at a recycled address is never mistaken for the old one, whichever call
@@ -1497,7 +1506,9 @@ typedef struct RelposeForwardArgs {
 int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args);
 
 /* Multiply-accumulates one forward of a plan family executes (host-only, no device access): flags as above, self_cached != 0 = the plan
- * a forward takes when it finds its self_tag on the workspace.  The full forward (flags 0, self_cached 0) counts every member of
+ * a forward takes when it finds its self_tag on the workspace: 1 = behind a fill that stored every skip head's halves, 2 = behind a
+ * pose-outputs fill (no rgb halves in the workspace: a forward without RELPOSE_FWD_POSE_OUTPUTS computes them, and they are counted; with
+ * the flag 2 counts what 1 does).  The full forward (flags 0, self_cached 0) counts every member of
  * model/mymodel.py:259-380; the level-0 plan and the self-stream cache count what they really launch.  bench.py divides the two for
  * its plan-aware in-loop roofline ("roofline.in_loop").  It is the STATIC plan that is counted: the patches and rows that the zero-tile lists
  * and conv4's row lists drop depend on the input and stay counted (relpose_scnet_zero_tiles / relpose_scnet_conv4_rows report them). */

@@ -1863,7 +1863,9 @@ struct HeadsDesc {
     // self-stream cache: the skip source of the rgb / n / d heads (the self-view blocks of A1) is level-invariant and is accumulated FIRST
     // in every plan; snap_mode 1 stores the three heads' accumulators after it (12 floats per pixel), snap_mode 2 starts from them and
     // does not read A1 at all (384 of the 1280 bytes a pixel reads)
-    int snap_mode; float* snap;
+    // snap_heads (snap_mode 2): bit m = head m (0 rgb, 1 n, 2 d) starts from its snapshot row; a full forward cached behind a pose-outputs
+    // fill has no rgb row (bits 1, 2 only): the rgb head's skip lines are then computed from A1 as in a plain forward, nothing is stored
+    int snap_mode; float* snap; int snap_heads;
 };
 constexpr int HEADS_W = 4352;
 
@@ -1937,10 +1939,16 @@ __global__ __launch_bounds__(256) void heads_lanepix_kernel(const HeadsDesc hd) 
     if (hd.snap_mode == 2) {
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
-            const float4 v = rp_ldg4(reinterpret_cast<const float*>(snp + m));
+            const float4 v = rp_ldg4(reinterpret_cast<const float*>(snp + m));      // (snap_heads without bit 0: the rgb row is loaded too -- in bounds, possibly never written -- and discarded below)
             a3[2 * m] = (rp_v2f){v.x, v.y}; a3[2 * m + 1] = (rp_v2f){v.z, v.w};
         }
-        if constexpr (POSE) { RP_HEAD_LOAD(xa, pd + 32) } else { RP_HEAD_LOAD(xb, pd) }
+        if constexpr (POSE) { RP_HEAD_LOAD(xa, pd + 32) } else {
+            if (!(hd.snap_heads & 1)) {          // no rgb snapshot (the cache was filled by a pose-outputs forward): the rgb skip line as in a plain forward
+                a3[0] = a3[1] = (rp_v2f){0.f, 0.f};
+                RP_HEAD_LOAD(xa, pa)
+                RP_HEAD_SKIP(xa, RP_HEAD_LOAD(xb, pd), 0)
+            } else RP_HEAD_LOAD(xb, pd)
+        }
     } else {
         if constexpr (POSE) {
             RP_HEAD_LOAD(xa, pa + 64)
@@ -1954,7 +1962,7 @@ __global__ __launch_bounds__(256) void heads_lanepix_kernel(const HeadsDesc hd) 
         }
         if (hd.snap_mode == 1) {
 #pragma unroll
-            for (int m = 0; m < 3; ++m) rp_stg4(reinterpret_cast<float*>(snp + m), make_float4(a3[2 * m].x, a3[2 * m].y, a3[2 * m + 1].x, a3[2 * m + 1].y));
+            for (int m = M0; m < 3; ++m) rp_stg4(reinterpret_cast<float*>(snp + m), make_float4(a3[2 * m].x, a3[2 * m].y, a3[2 * m + 1].x, a3[2 * m + 1].y));   // (POSE: the rgb row stays as a full forward left it -- defensive only: a pose-outputs fill commits no rgb bit, so nobody reads that row before the next full fill rewrites it)
         }
     }
     if constexpr (POSE) {
@@ -2095,8 +2103,14 @@ __global__ __launch_bounds__(256, RP_HEADS_WAVES) void heads_kernel(const HeadsD
     if (hd.snap_mode == 2) {
         float4 sv[3];
 #pragma unroll
+        // (the wave's 192 float4 are one contiguous run, the rgb rows every third of them: with snap_heads lacking bit 0 they are loaded all the
+        // same -- in bounds, possibly never written -- and a3[0..1] is overwritten with zeros below; 1 KB of 14 KB a wave reads there)
         for (int m = 0; m < 3; ++m) sv[m] = rp_ldg4(snw + (m * 64 + lane) * 4);
-        if constexpr (POSE) { RP_HS_FETCH_D2(xa, 32) RP_HS_FETCH_D2(xb, 64) } else { RP_HS_FETCH_D2(xb, 0) RP_HS_FETCH_D2(xa, 32) }
+        // no rgb snapshot (the cache was filled by a pose-outputs forward): the rgb head's skip set is fetched and accumulated as in a plain forward
+        const bool rgb_skip = !POSE && !(hd.snap_heads & 1);
+        if constexpr (POSE) { RP_HS_FETCH_D2(xa, 32) RP_HS_FETCH_D2(xb, 64) } else {
+            if (rgb_skip) { RP_HS_FETCH_A1(xa, 0) RP_HS_FETCH_D2(xb, 0) } else { RP_HS_FETCH_D2(xb, 0) RP_HS_FETCH_D2(xa, 32) }
+        }
 #pragma unroll
         for (int m = 0; m < 3; ++m) xw[m * 64 + lane] = sv[m];
         rp_wave_lds_sync();
@@ -2106,6 +2120,12 @@ __global__ __launch_bounds__(256, RP_HEADS_WAVES) void heads_kernel(const HeadsD
             a3[2 * m] = (rp_v2f){v.x, v.y}; a3[2 * m + 1] = (rp_v2f){v.z, v.w};
         }
         rp_wave_lds_sync();
+        if constexpr (!POSE) {
+            if (rgb_skip) {
+                a3[0] = a3[1] = (rp_v2f){0.f, 0.f};
+                RP_HS_SKIP(xa, RP_HS_FETCH_D2(xa, 32), 0)
+            }
+        }
     } else {
         if constexpr (POSE) { RP_HS_FETCH_A1(xa, 64) RP_HS_FETCH_A1(xb, 128) } else { RP_HS_FETCH_A1(xa, 0) RP_HS_FETCH_A1(xb, 64) }
         if constexpr (POSE) {
@@ -2121,7 +2141,8 @@ __global__ __launch_bounds__(256, RP_HEADS_WAVES) void heads_kernel(const HeadsD
             for (int m = 0; m < 3; ++m) xw[lane * 3 + m] = make_float4(a3[2 * m].x, a3[2 * m].y, a3[2 * m + 1].x, a3[2 * m + 1].y);
             rp_wave_lds_sync();
 #pragma unroll
-            for (int m = 0; m < 3; ++m) rp_stg4(snw + (m * 64 + lane) * 4, xw[m * 64 + lane]);
+            for (int m = 0; m < 3; ++m)
+                if (!POSE || (m * 64 + lane) % 3 != 0) rp_stg4(snw + (m * 64 + lane) * 4, xw[m * 64 + lane]);      // (POSE: the rgb rows stay as a full forward left them; defensive only, as in heads_lanepix_kernel)
             rp_wave_lds_sync();
         }
     }
@@ -2791,8 +2812,8 @@ struct RelposeSCNet {
     float2* d_ident = nullptr;   // 16 x {1,0}: scale/shift of the raw network input
     size_t w1_off = 0;           // conv1_mfma_kernel's weights inside d_w
     size_t wh_off = 0, bh_off = 0;   // fused-heads weight image and bias vector inside d_w
-    std::map<std::pair<void*, int>, void*> plans;   // (workspace, n) -> Plan* (each with its own device descriptor table)
-    struct SelfState { uint64_t tag = 0, gen = 0; int n = 0, H = 0, W = 0; bool pose_only = false; bool c4_rows = false; };   // c4_rows: it left conv4's self-slice maps
+    std::map<std::pair<void*, int64_t>, void*> plans;   // (workspace, n | plan family bits) -> Plan* (each with its own device descriptor table)
+    struct SelfState { uint64_t tag = 0, gen = 0; int n = 0, H = 0, W = 0; int snap_heads = 0; bool c4_rows = false; };   // snap_heads: skip heads (bit 0 rgb, 1 n, 2 d) whose snapshots the filling forward stored; c4_rows: it left conv4's self-slice maps
     std::map<void*, SelfState> self_state;          // workspace -> whose self-view streams it holds (relpose_scnet_forward4)
     std::map<std::string, Layer> layers;
     std::map<std::string, Buf> bufs;
@@ -3080,6 +3101,7 @@ struct Plan {
     size_t snap_floats = 0;      // accumulator snapshots of the skip-connection halves of deconv3 / deconv2 (ConvDesc::snap) and the heads
     size_t heads_snap_off = 0;
     int snap_mode = 0;           // 0 = plain forward, 1 = fills the snapshots (a tagged forward), 2 = self-cached forward
+    int snap_heads = 7;          // (snap_mode 2) skip heads whose snapshots are valid: bit 0 rgb, 1 n, 2 d (RelposeSCNet::SelfState); the others run their whole K chain
     std::vector<ConvDesc> descs;
     std::vector<Op> ops;
     size_t splitk_floats = 0;
@@ -3111,6 +3133,8 @@ struct Builder {
     float* snapbuf = nullptr;   // accumulator snapshots (ConvDesc::snap), `snap_mode` as in Plan
     int skip_slices = 0;        // (conv4, strip kernel) K slices left from the forward that filled the cache
     int snap_mode = 0;
+    int snap_heads = 7;         // (snap_mode 2) heads that start from their snapshot; a head outside the mask runs snap_mode 0
+    std::map<int, int> head_of; // first phase descriptor of a skip head's transposed conv -> head (0 rgb, 1 n, 2 d): its slot of the snapshot region
     int force_ksplit = 0, shared_slices = 0;   // conv4: 6 K slices = the six 128-channel stream blocks of A3 (in EVERY plan: same numerics);
                                                 // zero-warp plans mark the warped streams' slices shared (ConvDesc::shared_slices)
     int nimg = 0;               // images of the members added by conv() (0 = n): RELPOSE_FWD_ZERO_WARP plans run the warped streams on 2
@@ -3392,16 +3416,22 @@ void Builder::end_group() {
         Op o; o.type = OP_DECONV_TILE; o.first = first; o.count = count; o.cfg = dt_cfg; o.split = net->prec;
         o.grid = dim3((unsigned)(plan->descs[first].M / BMt), count / 4, dt_cfg >= 2 ? cp / 32 : 1);
         if (dt_cfg != 1) {
-            // heads with a skip source (the self-view block of A3 / A2): accumulator snapshots for the self-stream cache -- the region
-            // is laid out (and its offsets are the same) in every plan; only tagged forwards write it, only self-cached ones read it
+            // heads with a skip source (the self-view block of A3 / A2): accumulator snapshots for the self-stream cache -- every skip head
+            // (rgb, n, d) has a slot of its own in the region, at the same offset in every plan whichever heads the plan launches (a
+            // pose-outputs plan leaves the rgb slot alone); only tagged forwards write it, only self-cached ones read it, and a self-cached
+            // plan reads it for the heads of `snap_heads` only: any other head runs its whole K chain (snap_mode 0) and stores nothing
+            bool slots = false;
+            const size_t nfl = (size_t)o.grid.x * o.grid.z * 256 * 64;           // (MI * NI = 1 in variants 2 and 4)
             for (int i = first; i < first + count; i += 4) {
                 ConvDesc& d = plan->descs[i];
                 if (d.nsrc != 2) continue;
-                const size_t nfl = (size_t)o.grid.x * o.grid.z * 256 * 64;       // (MI * NI = 1 in variants 2 and 4)
-                d.snap = snapbuf ? snapbuf + plan->snap_floats : nullptr;
-                d.snap_mode = snapbuf ? snap_mode : 0;
-                plan->snap_floats += nfl;
+                const auto h = head_of.find(i);
+                if (h == head_of.end() || h->second < 0 || h->second > 2) { rc = RELPOSE_EINVAL; return; }
+                slots = true;
+                d.snap = snapbuf ? snapbuf + plan->snap_floats + (size_t)h->second * nfl : nullptr;
+                d.snap_mode = !snapbuf ? 0 : ((snap_mode == 2 && !((snap_heads >> h->second) & 1)) ? 0 : snap_mode);
             }
+            if (slots) plan->snap_floats += 3 * nfl;
         }
         plan->ops.push_back(o);
         return;
@@ -3565,13 +3595,13 @@ void build_plan(RelposeSCNet* net, int n, Builder& R) {
     R.begin_group();
     for (int m = 0; m < 5; ++m) {
         if (!wanted(m)) continue;
-        if (m < 3) { sk = R.src("A3", 2 * m * 128, 128); R.conv(std::string("deconv3") + heads[m], R.src("D4", 0, 128), &sk, 56, "D3", m * 64); }
+        if (m < 3) { sk = R.src("A3", 2 * m * 128, 128); R.head_of[(int)R.plan->descs.size()] = m; R.conv(std::string("deconv3") + heads[m], R.src("D4", 0, 128), &sk, 56, "D3", m * 64); }
         else R.conv(std::string("deconv3") + heads[m], R.src("D4", 0, 128), nullptr, 56, "D3", m * 64);
     }
     R.end_group(); R.stats("D3");
     const int d2off[5] = {0, 32, 64, 96, 160};
     R.begin_group();
-    for (int m = 0; m < 3; ++m) if (wanted(m)) { sk = R.src("A2", 2 * m * 64, 64); R.conv(std::string("deconv2") + heads[m], R.src("D3", m * 64, 64), &sk, 112, "D2", d2off[m]); }
+    for (int m = 0; m < 3; ++m) if (wanted(m)) { sk = R.src("A2", 2 * m * 64, 64); R.head_of[(int)R.plan->descs.size()] = m; R.conv(std::string("deconv2") + heads[m], R.src("D3", m * 64, 64), &sk, 112, "D2", d2off[m]); }
     R.end_group();
     R.begin_group();
     for (int m = 3; m < 5; ++m) if (wanted(m)) R.conv(std::string("deconv2") + heads[m], R.src("D3", m * 64, 64), nullptr, 112, "D2", d2off[m]);
@@ -3848,7 +3878,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     const bool zt_on = g_rp_tune[RELPOSE_TUNE_ZERO_TILES] != 1;
     const bool c4_on = zt_on && g_rp_tune[RELPOSE_TUNE_CONV4_ROWS] != 1;
     commit.c4_rows = c4_on;
-    commit.tag = self_tag; commit.n = n; commit.H = H; commit.W = W; commit.pose_only = pose_only; commit.gen = ws_gen;
+    commit.tag = self_tag; commit.n = n; commit.H = H; commit.W = W; commit.gen = ws_gen;
     if (flags & RELPOSE_FWD_NEW_WORKSPACE) net->self_state.erase(workspace);      // the memory behind this pointer is not what the last forward left
     // Self-stream cache: the previous forward on this workspace carried the same non-zero tag (and shape, and -- when the caller names its
     // allocations -- the same workspace generation) -> the self-view encoder streams it left in the workspace are what this forward would
@@ -3856,23 +3886,30 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     // have been enqueued: a forward that returns an error leaves no claim on the workspace's content.
     RelposeSCNet::SelfState prev = net->self_state[workspace];
     net->self_state[workspace] = RelposeSCNet::SelfState();
-    // (the accumulator snapshots are laid out per plan family: a pose-outputs forward has fewer decoder heads)
-    bool self_cached = self_tag != 0 && prev.tag == self_tag && prev.n == n && prev.H == H && prev.W == W && prev.pose_only == pose_only && !zero_warp &&
+    // (everything head-independent -- the self members of conv1-3, their scale / shift, conv4's self slices and row maps -- is the same whichever
+    // outputs the filling forward computed; the accumulator snapshots are per skip head, each in its own slot: prev.snap_heads says which the
+    // filling forward stored.  A pose-outputs fill leaves no rgb snapshot: a full forward cached behind it runs the rgb head's whole K chain.)
+    bool self_cached = self_tag != 0 && prev.tag == self_tag && prev.n == n && prev.H == H && prev.W == W && (prev.snap_heads & 6) == 6 && !zero_warp &&
                        prev.gen == ws_gen && prev.c4_rows == c4_on;     // (a forward without conv4's row lists computes every row of the self slices, one with them leaves their maps)
-    int snap_mode = 0;
+    int snap_mode = 0, snap_heads = 7;
     const int ds_key = ((g_rp_tune[RELPOSE_TUNE_DECONV_STRIP] == 1 ? 1 : 0) << 28) | ((zt_on ? 0 : 1) << 29) | ((c4_on ? 0 : 1) << 30);       // the builder reads the knobs: one plan per value
+    auto key_of = [&]() {
+        // (a cached pose-outputs plan launches no rgb head: one plan whatever the rgb bit)
+        return (int64_t)((int)n | (zero_warp ? 1 << 24 : 0) | (pose_only ? 1 << 25 : 0) | (self_cached ? 1 << 26 : 0) | (snap_mode == 1 ? 1 << 27 : 0) | ds_key) |
+               ((int64_t)(self_cached ? snap_heads : 7) << 32);
+    };
     for (int attempt = 0; attempt < 2 && !plan; ++attempt) {
         // a tagged forward that computes the self streams also leaves the accumulator snapshots of the skip-connection halves
         snap_mode = self_cached ? 2 : (self_tag != 0 ? 1 : 0);
-        const int plan_key = (int)n | (zero_warp ? 1 << 24 : 0) | (pose_only ? 1 << 25 : 0) | (self_cached ? 1 << 26 : 0) | (snap_mode == 1 ? 1 << 27 : 0) | ds_key;
-        auto it = net->plans.find(std::make_pair(workspace, plan_key));
+        snap_heads = self_cached ? (prev.snap_heads | (pose_only ? 1 : 0)) & 7 : 7;
+        auto it = net->plans.find(std::make_pair(workspace, key_of()));
         if (it != net->plans.end()) { plan = (Plan*)it->second; break; }
         const WsOffsets o = ws_offsets(net, n);
         if (workspace_bytes < o.total) return RELPOSE_ENOMEM;
         if (net->plans.size() >= 32) {       // callers keep a few long-lived workspaces; bound the cache
             free_plan(net);
             self_cached = false;             // (free_plan drops every workspace's self-stream record with the plans)
-            snap_mode = self_tag != 0 ? 1 : 0;
+            snap_mode = self_tag != 0 ? 1 : 0; snap_heads = 7;
         }
         Plan* p = new Plan();
         p->n = n; p->ws = workspace; p->zero_warp = zero_warp; p->pose_only = pose_only; p->self_cached = self_cached;
@@ -3881,6 +3918,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         B.act = (float*)(ws + o.act); B.ss = (float2*)(ws + o.ss); B.splitk = (float*)(ws + o.splitk); B.statp = (double*)(ws + o.statp);
         B.persist = (float*)(ws + o.persist);
         B.snapbuf = (float*)(ws + o.snap); B.snap_mode = snap_mode; p->snap_mode = snap_mode;
+        B.snap_heads = snap_heads; p->snap_heads = snap_heads;
         B.zt = zt_on ? (int*)(ws + o.zt) + zt_occ_ints(n) : nullptr;
         B.c4r = c4_on ? (int*)(ws + o.c4r) : nullptr;
         build_plan(net, n, B);
@@ -3893,11 +3931,13 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
         }
         RP_HIP(hipMalloc((void**)&p->d_descs, MAX_DESCS * sizeof(ConvDesc)));
         RP_HIP(hipMemcpy(p->d_descs, p->descs.data(), p->descs.size() * sizeof(ConvDesc), hipMemcpyHostToDevice));
-        const int key2 = (int)n | (zero_warp ? 1 << 24 : 0) | (pose_only ? 1 << 25 : 0) | (self_cached ? 1 << 26 : 0) | (snap_mode == 1 ? 1 << 27 : 0) | ds_key;
-        net->plans[std::make_pair(workspace, key2)] = p;
+        net->plans[std::make_pair(workspace, key_of())] = p;
         plan = p;
     }
     if (!plan) return RELPOSE_EINVAL;
+    // the snapshots the workspace holds after this forward: a cached forward stores none and carries the record on, a tagged forward that
+    // computes the self streams stores those of the skip heads it launches
+    commit.snap_heads = plan->self_cached ? prev.snap_heads : (self_tag != 0 ? (pose_only ? 6 : 7) : 0);
     net->last_n = n;
     // two-stream mode: the HBM-bound head (resize_in, conv1) and tail (heads, resize_out) run on tail_stream, the MFMA-bound middle on `stream`
     const bool two = tail_stream != stream;
@@ -4122,7 +4162,7 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
             hd.ss_d2 = ssp + net->bufs["D2"].ss_off * G; hd.ss_a1 = ssp + net->bufs["A1"].ss_off * G;
             hd.w = net->d_w + net->wh_off; hd.bias = net->d_w + net->bh_off; hd.out = act + net->bufs["OUT"].off * n;
             hd.n = n; hd.S = net->S; hd.cf = net->cf; hd.use_tanh = net->use_tanh;
-            hd.snap_mode = plan->snap_mode; hd.snap = (float*)(ws + o.snap) + plan->heads_snap_off;
+            hd.snap_mode = plan->snap_mode; hd.snap = (float*)(ws + o.snap) + plan->heads_snap_off; hd.snap_heads = plan->snap_heads;
             mark(1);
             const dim3 hg((unsigned)((size_t)n * RS * RS / 256));
             // RELPOSE_TUNE_HEADS_KERNEL: 0 = the streamed kernel, 1 = the lane-per-pixel kernel (the same bits; tests/test_gpu_heads_stream.py)
@@ -4206,6 +4246,9 @@ int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n, int32_t flags, int32_t
     B.zero_warp = zero_warp; B.pose_only = pose_only; B.self_cached = self_cached != 0;
     B.snapbuf = (float*)(uintptr_t)4096;       // (never dereferenced: makes the builder record ConvDesc::snap_mode in the dry run)
     B.snap_mode = self_cached ? 2 : 1; dry.snap_mode = B.snap_mode;
+    // self_cached 2 = cached behind a pose-outputs fill: no rgb snapshots, the rgb head's skip halves are computed (deconv3rgb, deconv2rgb, heads)
+    const int snap_heads = self_cached == 2 ? 6 : 7;
+    B.snap_heads = snap_heads; dry.snap_heads = snap_heads;
     build_plan(net, n, B);
     if (B.rc) return B.rc;
     double macs = 0;
@@ -4239,7 +4282,7 @@ int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n, int32_t flags, int32_t
             const int hc[5] = {3, 3, 1, net->S, 32};
             for (int m = 0; m < 5; ++m) {
                 if (pose_only && (m == 0 || m == 3)) continue;
-                const int cin = (m < 3 && self_cached) ? 32 : 64;
+                const int cin = (m < 3 && self_cached && ((snap_heads >> m) & 1)) ? 32 : 64;
                 macs += px * cin * hc[m];
             }
         }

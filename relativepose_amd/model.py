@@ -174,7 +174,7 @@ class SCNet(torch.nn.Module):
         cls._tag_counter += 1
         return cls._tag_counter
 
-    FLAG_ZERO_WARP, FLAG_POSE_OUTPUTS = 1, 2       # RELPOSE_FWD_* (include/relpose.h)
+    FLAG_ZERO_WARP, FLAG_POSE_OUTPUTS, FLAG_NEW_WORKSPACE = 1, 2, 4       # RELPOSE_FWD_* (include/relpose.h)
 
     def forward(self, x, out=None, tail_stream=None, ws_key=None, zero_warp=False, outputs="all", self_tag=0):
         """tail_stream (a torch stream; not part of the reference interface): run the HBM-bound tail of the forward (heads + final
@@ -188,7 +188,9 @@ class SCNet(torch.nn.Module):
         those of the full forward).
         self_tag: non-zero = the caller's name for the content of x[:, 0:8] (the masked own views, constant across the levels of a scan
         pair's recurrence, evaluation.py:217-242): a forward that finds the previous forward of its workspace carried the same tag reuses
-        that forward's self-view encoder streams (RelposeForwardArgs::self_tag; bitwise the same output).  0 = always recompute."""
+        that forward's self-view encoder streams (RelposeForwardArgs::self_tag; bitwise the same output).  0 = always recompute.
+        The outputs of the forward that filled the cache do not matter: an "all" forward behind "pose" forwards of its tag is cached too
+        (it computes the rgb head's skip halves itself, the only part no "pose" forward leaves behind)."""
         flags = (self.FLAG_ZERO_WARP if zero_warp else 0) | {"all": 0, "pose": self.FLAG_POSE_OUTPUTS}[outputs]
         return self.forward_flags(x, out, flags, self_tag, tail_stream, ws_key)
 
@@ -221,7 +223,7 @@ class SCNet(torch.nn.Module):
             assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, self.out_channels, H, W)
         a = _lib.ForwardArgs()
         a.struct_size = C.sizeof(_lib.ForwardArgs)
-        a.flags = int(flags) & 3
+        a.flags = int(flags) & 7
         a.x, a.out = x.data_ptr(), out.data_ptr()
         a.n_images, a.H, a.W = n, H, W
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
@@ -239,9 +241,12 @@ class SCNet(torch.nn.Module):
         return out
 
     def plan_macs(self, n, flags=0, self_cached=False):
-        """Multiply-accumulates one forward of n images executes under a plan family (relpose_scnet_plan_macs; host-only)."""
+        """Multiply-accumulates one forward of n images executes under a plan family (relpose_scnet_plan_macs; host-only).
+        self_cached: False / 0 = computes the self streams, True / 1 = cached behind a forward that computed every output, 2 = cached behind
+        a pose-outputs forward (the rgb head's skip halves are computed: the last level of RelativePosePipeline(level_outputs="last"))."""
         v = C.c_double()
-        _lib.check(_lib.lib().relpose_scnet_plan_macs(self._h, int(n), int(flags), 1 if self_cached else 0, C.byref(v)), "relpose_scnet_plan_macs")
+        _lib.check(_lib.lib().relpose_scnet_plan_macs(self._h, int(n), int(flags), 2 if self_cached == 2 else (1 if self_cached else 0), C.byref(v)),
+                   "relpose_scnet_plan_macs")
         return v.value
 
     def layer_kernel(self, layer, n):

@@ -24,7 +24,7 @@ class RelativePosePipeline:
     _net_streams = None
 
     def __init__(self, net, dataset="suncg", mask_method="second", sigmas=None, alter_steps=3, completion=1, max_edges=0, compose=0, outputs="all",
-                 self_stream_cache=True, tail_overlap=True, net_priority=None, loop_fit_cluster=1, keypoints="given"):
+                 self_stream_cache=True, tail_overlap=True, net_priority=None, loop_fit_cluster=1, keypoints="given", level_outputs="last"):
         self.net = net
         # "given": prepare(pts, ptw) fixes the keypoints of every view for all levels.  "reference": prepare(sift=...) takes the views' SIFT
         # detections (panorama coordinates, rputil.map_detections) and every level derives its keypoints from its own feature maps, as
@@ -39,6 +39,14 @@ class RelativePosePipeline:
         # "all": SCNet computes every output like the reference; "pose": only the heads this loop reads (normal, depth, features:
         # RELPOSE_FWD_POSE_OUTPUTS) -- the same poses bit for bit, the completed rgb / semantic maps are not produced (opt-in)
         self.outputs = outputs
+        # Nobody reads the completed rgb / semantic maps between the levels: the pose loop samples normal, depth and features
+        # (util.sample_primitives_dev), every level writes the same st["f"], and the caller gets what the LAST level left there.  "last"
+        # (with outputs="all"): the levels before the last run the pose-outputs forward and the last one computes every output -- the same
+        # poses, status and final st["f"] bit for bit.  "every": each level computes every output, like the reference.  run(keep=...) hands
+        # out every level's maps and therefore always computes them; outputs="pose" and variant nets are not affected.
+        if level_outputs not in ("last", "every"):
+            raise ValueError("level_outputs must be 'last' or 'every'")
+        self.level_outputs = level_outputs
         self.dataset = dataset
         self.mask_method = mask_method
         self.alter_steps = alter_steps
@@ -379,6 +387,12 @@ class RelativePosePipeline:
         self._chain_nets = False
         return results
 
+    def _outputs_at(self, step, keep=None):
+        """forward(outputs=...) of level `step`: level_outputs="last" asks the levels before the last for the pose outputs only."""
+        if self.outputs == "all" and self.level_outputs == "last" and keep is None and step < self.alter_steps - 1 and not self.net.is_variant:
+            return "pose"
+        return self.outputs
+
     def _net_input(self, st):
         """The network input [2B,16,h,4h] of a prepared batch (kept across calls): channels 0:8 = the masked own
         view of every image (util.apply_mask layout), channels 8:16 are rewritten by every level's warp."""
@@ -421,17 +435,17 @@ class RelativePosePipeline:
                     # forwards need separate workspaces: one per stream (= per in-flight slot).
                     f = st["f"]
                     with torch.cuda.stream(ns):
-                        self.net.forward(x, out=f, tail_stream=ms, ws_key=ms.cuda_stream, zero_warp=(step == 0), outputs=self.outputs,
+                        self.net.forward(x, out=f, tail_stream=ms, ws_key=ms.cuda_stream, zero_warp=(step == 0), outputs=self._outputs_at(step),
                                          self_tag=st["self_tag"])
                 else:
                     with torch.cuda.stream(ns):
-                        f = self.net.forward(x, out=st["f"], zero_warp=(step == 0), outputs=self.outputs, self_tag=st["self_tag"])
+                        f = self.net.forward(x, out=st["f"], zero_warp=(step == 0), outputs=self._outputs_at(step), self_tag=st["self_tag"])
                         done = torch.cuda.Event()
                         done.record()
                     ms.wait_event(done)
                 yield                                            # one yield per level: the other batches enqueue theirs
             else:
-                f = self.net.forward(x, out=st["f"], zero_warp=(step == 0), outputs=self.outputs, self_tag=st["self_tag"])
+                f = self.net.forward(x, out=st["f"], zero_warp=(step == 0), outputs=self._outputs_at(step), self_tag=st["self_tag"])
             kpts, knpts, w_s, w_t, ns, nt = self._level_keypoints(st, f, step)
             pc, nn, ft = util.sample_primitives_dev(f, self.feat_off, st["norm"], st["depth"], kpts, knpts,
                                                     self.mask_method, self.dataset, self.compose)
@@ -463,8 +477,8 @@ class RelativePosePipeline:
             util.warp_pairs_dev(x, poses, self.dataset)       # x[:, 8:] = partner view warped by the pose estimate
             # level 0 starts from the identity: util.warping returns zeros (util.py:95-96) for every image, which SCNet can exploit
             # (the batch's preallocated output buffer, unless the caller keeps every level's output: `keep` entries must not alias)
-            f = self.net.forward(x, out=st["f"] if keep is None else None, zero_warp=(step == 0 and R_forced is None), outputs=self.outputs,
-                                 self_tag=st["self_tag"])
+            f = self.net.forward(x, out=st["f"] if keep is None else None, zero_warp=(step == 0 and R_forced is None),
+                                 outputs=self._outputs_at(step, keep), self_tag=st["self_tag"])
             kpts, knpts, w_s, w_t, ns, nt = self._level_keypoints(st, f, step)
             pc, nn, ft = util.sample_primitives_dev(f, self.feat_off, st["norm"], st["depth"], kpts, knpts,
                                                     self.mask_method, self.dataset, self.compose)
