@@ -38,6 +38,7 @@ extern "C" {
 
 #define RELPOSE_EINVAL (-1)
 #define RELPOSE_ENOMEM (-2)
+#define RELPOSE_EROUNDS (-3) /* relpose_mesh_components: labels still moved in round max_rounds; the outputs hold nothing to rely on */
 
 /* status[b] of relpose_match_pairs */
 enum {
@@ -1121,6 +1122,111 @@ typedef struct RelposeTsdfMeshArgs {
 } RelposeTsdfMeshArgs;
 size_t relpose_tsdf_mesh_workspace_bytes(int32_t n_scenes, int32_t nx, int32_t ny, int32_t nz);
 int relpose_tsdf_mesh(const RelposeTsdfMeshArgs* args);
+
+/* -------------------------------------------------------------------- connected components of triangle meshes, and their removal
+ * relpose_mesh_components labels the connected components of n_scenes indexed triangle meshes in relpose_tsdf_mesh's layout and sums a few
+ * integers per component; relpose_mesh_filter keeps the components a caller selects and compacts the mesh.  The contract is the project's own
+ * (tests/components_model.py restates it in numpy).  Every input and output is device memory unless it says host.
+ *   scene            nv = min(max(n_points, 0), cap) vertices and nt = min(max(n_triangles, 0), cap_tri) triangle rows (relpose_tsdf_mesh's
+ *                    counts may exceed its caps; only what was written is read).
+ *   bad rows         a row < nt with an index outside [0, nv) is bad: it joins nothing, gets label -1 and is counted in bad_triangles [S].
+ *   rule             VERTEX connectivity: two vertices are connected iff a chain of good triangles links them through shared vertex
+ *                    indices.  Two triangles that meet in ONE vertex are one component -- unlike Open3D's cluster_connected_triangles, which
+ *                    joins triangles across shared edges only.  It is what union-find over vertices gives, and it keeps the zero-area
+ *                    triangles marching cubes leaves where t == 0 with the surface they belong to.  Vertices are joined by index, never by
+ *                    position.  A vertex no good triangle names belongs to no component.
+ *   numbering        components are numbered 0, 1, ... in ascending order of their smallest vertex index: the result is unique.
+ *   vertex_label     [S, cap] i32: the component, -1 for unused vertices and rows >= nv.      tri_label [S, cap_tri] i32: -1 for bad rows and
+ *                    rows >= nt.      n_components [S] i32: the true count, which may exceed cap_comp.      bad_triangles [S] i32.
+ *   statistics       for components c < cap_comp, each [S, cap_comp]: comp_root i32 (the smallest vertex index), comp_vertices i32,
+ *                    comp_triangles i32, comp_area i64; entries at and beyond n_components hold -1, 0, 0, 0.  The four pointers may be NULL
+ *                    with cap_comp = 0 (the counting call).  comp_area = the sum over the component's triangles of
+ *                    llrint(min(A area_scale, 2147483648.0)) with A = sqrt((cx cx + cy cy) + cz cz) 0.5 and c = (p1 - p0) x (p2 - p0), every
+ *                    operation its own f64 rounding; a product A area_scale that is not finite counts 0.  points NULL: comp_area is 0.
+ *   method           monotone lowering: L[v] starts at v; a round lowers, with device-scope atomic minima only, every good triangle's three
+ *                    entries and the entries they point to to the triangle's smallest label, then shortcuts L[v] <- L[L[v]].  Every write is
+ *                    the minimum with a label of the same component, so a stale read costs a round and never an answer; the fixpoint is the
+ *                    component's smallest index.  The host reads one flag word per group of 4 rounds and stops at the first round that
+ *                    lowered nothing; *rounds_host (host, may be NULL) receives the number of rounds counted, that last one included.  If
+ *                    round max_rounds still lowered a label the call returns RELPOSE_EROUNDS and promises nothing about the outputs:
+ *                    max_rounds is a guard, not a tuning knob.
+ *   limits           n_scenes >= 1; 1 <= cap, 1 <= cap_tri; n_scenes * cap, n_scenes * cap_tri and n_scenes * cap_comp < 2^29; cap_comp >= 0;
+ *                    area_scale finite and > 0; max_rounds >= 1.
+ *   workspace        relpose_mesh_components_workspace_bytes(n_scenes, cap, cap_tri) bytes (0 outside the limits), 256-byte aligned.
+ * The sums are integer atomic adds: every output is bitwise repeatable and a scene does not depend on its batch.  Invalid arguments return
+ * RELPOSE_EINVAL before anything is enqueued or any output is touched.  The call waits for `stream` once per group of rounds; the ranking
+ * and statistics launches behind the last wait are only enqueued. */
+typedef struct RelposeMeshComponentsArgs {
+    uint32_t struct_size;       /* sizeof(RelposeMeshComponentsArgs) as the caller compiled it */
+    int32_t n_scenes;
+    int32_t cap;
+    int32_t cap_tri;
+    int32_t cap_comp;
+    int32_t max_rounds;
+    const int32_t* triangles;   /* [n_scenes, cap_tri, 3] */
+    const int32_t* n_triangles; /* [n_scenes] */
+    const int32_t* n_points;    /* [n_scenes] */
+    const double* points;       /* [n_scenes, cap, 3], or NULL for no areas */
+    double area_scale;
+    int32_t* vertex_label;
+    int32_t* tri_label;
+    int32_t* n_components;
+    int32_t* bad_triangles;
+    int32_t* comp_root;
+    int32_t* comp_vertices;
+    int32_t* comp_triangles;
+    int64_t* comp_area;
+    int32_t* rounds_host;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeMeshComponentsArgs;
+size_t relpose_mesh_components_workspace_bytes(int32_t n_scenes, int32_t cap, int32_t cap_tri);
+int relpose_mesh_components(const RelposeMeshComponentsArgs* args);
+
+/* Keep the selected components of relpose_mesh_components' meshes and compact them.
+ *   survivors        a triangle row < nt survives iff its tri_label is in [0, cap_comp) and keep [S, cap_comp] u8 is not 0 for it.  A vertex
+ *                    < nv survives iff its vertex_label is kept in the same sense; a vertex with label < 0 survives iff drop_unused is 0.
+ *   order            survivors keep their order: a vertex's new index is the number of surviving vertices below it, and the triangles' indices
+ *                    are renumbered (an index whose vertex did not survive, which labels of relpose_mesh_components never produce, becomes -1).
+ *   outputs          out_points, out_normals f64 [S, cap, 3], out_colors f32 [S, cap, 3] (NULL iff colors is), out_triangles i32 [S, cap_tri, 3]:
+ *                    only rows below the new counts out_n_points, out_n_triangles [S] i32 are written, each a bitwise copy of its source
+ *                    row; out_valid u8 [S, cap] is written whole, 1 below the new count.  vertex_map [S, cap] i32 (may be NULL): old index
+ *                    -> new index, -1 for dropped vertices and rows >= nv.  Every output is a buffer of its own, none an input.
+ *   limits           relpose_mesh_components'; drop_unused 0 or 1; keep may be NULL only with cap_comp = 0 (nothing labelled survives).
+ *   workspace        relpose_mesh_filter_workspace_bytes(n_scenes, cap, cap_tri) bytes (0 outside the limits), 256-byte aligned.
+ * Flag, scan per scene, scatter: four launches, no atomics, only enqueued on `stream`.  Invalid arguments return RELPOSE_EINVAL before
+ * anything is enqueued or any output is touched. */
+typedef struct RelposeMeshFilterArgs {
+    uint32_t struct_size;       /* sizeof(RelposeMeshFilterArgs) as the caller compiled it */
+    int32_t n_scenes;
+    int32_t cap;
+    int32_t cap_tri;
+    int32_t cap_comp;
+    int32_t drop_unused;
+    const double* points;
+    const double* normals;
+    const float* colors;
+    const int32_t* n_points;
+    const int32_t* triangles;
+    const int32_t* n_triangles;
+    const int32_t* vertex_label;
+    const int32_t* tri_label;
+    const uint8_t* keep;
+    double* out_points;
+    double* out_normals;
+    float* out_colors;
+    uint8_t* out_valid;
+    int32_t* out_n_points;
+    int32_t* out_triangles;
+    int32_t* out_n_triangles;
+    int32_t* vertex_map;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeMeshFilterArgs;
+size_t relpose_mesh_filter_workspace_bytes(int32_t n_scenes, int32_t cap, int32_t cap_tri);
+int relpose_mesh_filter(const RelposeMeshFilterArgs* args);
 
 /* Frame-to-model alignment: refine the poses of n_views depth panoramas against relpose_tsdf_fuse's volumes, so that each view's measured
  * points come to lie on the zero level of the volume it names (the KinectFusion tracking step, sampled at the measured points: no ray is

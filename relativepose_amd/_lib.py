@@ -222,6 +222,25 @@ class TsdfMeshArgs(C.Structure):
                 ("workspace_bytes", c_size_t), ("stream", c_void_p)]
 
 
+class MeshComponentsArgs(C.Structure):
+    """RelposeMeshComponentsArgs (include/relpose.h): the argument block of relpose_mesh_components."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("cap", c_int), ("cap_tri", c_int), ("cap_comp", c_int), ("max_rounds", c_int),
+                ("triangles", c_void_p), ("n_triangles", c_void_p), ("n_points", c_void_p), ("points", c_void_p), ("area_scale", c_double),
+                ("vertex_label", c_void_p), ("tri_label", c_void_p), ("n_components", c_void_p), ("bad_triangles", c_void_p),
+                ("comp_root", c_void_p), ("comp_vertices", c_void_p), ("comp_triangles", c_void_p), ("comp_area", c_void_p),
+                ("rounds_host", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
+class MeshFilterArgs(C.Structure):
+    """RelposeMeshFilterArgs (include/relpose.h): the argument block of relpose_mesh_filter."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("cap", c_int), ("cap_tri", c_int), ("cap_comp", c_int), ("drop_unused", c_int),
+                ("points", c_void_p), ("normals", c_void_p), ("colors", c_void_p), ("n_points", c_void_p), ("triangles", c_void_p),
+                ("n_triangles", c_void_p), ("vertex_label", c_void_p), ("tri_label", c_void_p), ("keep", c_void_p), ("out_points", c_void_p),
+                ("out_normals", c_void_p), ("out_colors", c_void_p), ("out_valid", c_void_p), ("out_n_points", c_void_p),
+                ("out_triangles", c_void_p), ("out_n_triangles", c_void_p), ("vertex_map", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
 class TsdfAlignArgs(C.Structure):
     """RelposeTsdfAlignArgs (include/relpose.h): the argument block of relpose_tsdf_align."""
     _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("n_views", c_int), ("h", c_int), ("dataset", c_int), ("nx", c_int),
@@ -258,6 +277,7 @@ TSDF_MAX_VIEWS = 4096               # per scene per relpose_tsdf_fuse call
 TSDF_MAX_WEIGHT = 65535             # the caller's bound on a voxel's weight across accumulating calls
 TSDF_ALIGN_EIG_MIN = 0.0043         # relpose_tsdf_align's eigenvalue floor: between the two ranges measured in DESIGN.md 4.19
 TSDF_RENDER_MAX_STEPS = 65536        # relpose_tsdf_render's bound on n_steps
+MESH_EROUNDS = -3                   # RELPOSE_EROUNDS: relpose_mesh_components ran out of max_rounds
 TSDF_ALIGN_SUMS = 32                # 21 JtJ + 6 Jtr + r^2 + the counts of outside, unknown, saturated and used points
 
 
@@ -323,6 +343,10 @@ SIGNATURES = {
     "relpose_tsdf_surface": (c_int, [C.POINTER(TsdfSurfaceArgs)]),
     "relpose_tsdf_mesh_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "relpose_tsdf_mesh": (c_int, [C.POINTER(TsdfMeshArgs)]),
+    "relpose_mesh_components_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "relpose_mesh_components": (c_int, [C.POINTER(MeshComponentsArgs)]),
+    "relpose_mesh_filter_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "relpose_mesh_filter": (c_int, [C.POINTER(MeshFilterArgs)]),
     "relpose_tsdf_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "relpose_tsdf_align": (c_int, [C.POINTER(TsdfAlignArgs)]),
     "relpose_tsdf_render_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

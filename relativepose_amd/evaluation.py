@@ -25,6 +25,9 @@ unchanged" is realised by the build's own eval_pairs-style harness).
   fuse_views(mesh=True) / mesh_stats / mesh_summary
                           no counterpart: the fused volume as an indexed triangle mesh and what kind of surface it is (util.tsdf_mesh_dev,
                           DESIGN.md 4.18)
+  fuse_views(mesh=True, min_component=N) / mesh_component_stats / clean_mesh / mesh_clean_summary
+                          no counterpart: the mesh's connected components and the mesh without the small ones (util.mesh_components_dev /
+                          mesh_filter_dev / mesh_clean_dev)
   refine_scene / leave_one_out_state, evaluate_scenes(refine=...)
                           no counterpart: the views' poses refined against the volume the other views fuse into, frame to model
                           (util.tsdf_align_dev)
@@ -294,12 +297,14 @@ def verify_summary(stats):
     return out
 
 
-def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, max_points=None, view_begin=None, mesh=False):
+def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, max_points=None, view_begin=None, mesh=False, min_component=None):
     """Merge posed depth panoramas into one surface cloud per scene: depth [V,h,4h] f32 and rgb [V,3,h,4h] f32 (or None)
     CUDA tensors, R [V,4,4] host float64 world -> camera poses (the loaders' R), view_begin as util.tsdf_fuse_dev's (None: one scene).  The box
     is util.tsdf_bounds_dev's, the volume util.tsdf_fuse_dev's, the cloud util.tsdf_surface_dev's.
     -> {"points" [S,cap,3] f64, "normals", "colors" (or None), "valid" [S,cap] u8, "n_points" [S] i32, "origin", "dims", "voxel", "state"}.
-    mesh=True: the same five tensors from util.tsdf_mesh_dev, and "triangles" [S,cap_tri,3] i32, "n_triangles" [S] i32."""
+    mesh=True: the same five tensors from util.tsdf_mesh_dev, and "triangles" [S,cap_tri,3] i32, "n_triangles" [S] i32.
+    min_component=N (with mesh=True): the mesh without its connected components of fewer than N triangles and without unused vertices
+    (util.mesh_clean_dev), "vertex_map", and "components": mesh_clean_dev's description of the mesh before the cleaning."""
     from . import util
     vb = np.array([0, int(depth.shape[0])], np.int32) if view_begin is None else view_begin
     origin, dims = util.tsdf_bounds_dev(depth, R, dataset, voxel, pad, vb)
@@ -307,7 +312,12 @@ def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, m
     if mesh:
         out = util.tsdf_mesh_dev(state, min_weight, max_points)
         out.update(origin=origin, dims=dims, voxel=float(voxel), state=state)
+        if min_component is not None:
+            clean, comps = util.mesh_clean_dev(out, min_triangles=int(min_component))
+            out.update(clean, components=comps)
         return out
+    if min_component is not None:
+        raise ValueError("fuse_views: min_component applies to mesh=True")
     points, normals, colors, valid, n = util.tsdf_surface_dev(state, min_weight, max_points)
     return {"points": points, "normals": normals, "colors": colors, "valid": valid, "n_points": n, "origin": origin, "dims": dims,
             "voxel": float(voxel), "state": state}
@@ -409,6 +419,38 @@ def mesh_stats(mesh):
         manifold = (cnt == 1) | ((cnt == 2) & (fwd == 1))
         out.append({"triangles": int(len(t)), "area": area, "border_edges": int((cnt == 1).sum()), "nonmanifold_edges": int((~manifold).sum())})
     return out
+
+
+def mesh_component_stats(comps):
+    """What util.mesh_components_dev / mesh_clean_dev's `comps` (or the model's dict) says per scene, on the host: -> a list of {"components",
+    "largest_share": the largest component's share of the labelled triangles (nan without any), "small_triangles": the triangles outside the
+    largest component}.  Needs every component's count: cap_comp >= n_components."""
+    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+    n, ct = host(comps["n_components"]), host(comps["comp_triangles"]).astype(np.int64)
+    if len(n) and int(n.max()) > ct.shape[1]:
+        raise ValueError("mesh_component_stats: the statistics are truncated (cap_comp < n_components)")
+    out = []
+    for s in range(len(n)):
+        c = ct[s, :int(n[s])]
+        total, top = int(c.sum()), int(c.max()) if len(c) else 0
+        out.append({"components": int(n[s]), "largest_share": top / total if total else float("nan"), "small_triangles": total - top})
+    return out
+
+
+def mesh_clean_summary(stats, removed):
+    """the CLI's medians of mesh_component_stats and of the triangles --mesh-min-component removed, over scenes"""
+    med = lambda v: float(np.nanmedian(v)) if len(v) and not np.all(np.isnan(v)) else float("nan")
+    return {"mesh_components_median": med([m["components"] for m in stats]), "mesh_largest_share_median": med([m["largest_share"] for m in stats]),
+            "mesh_removed_triangles_median": med(removed)}
+
+
+def clean_mesh(mesh, min_component):
+    """--mesh-min-component: -> (the mesh dict without its components of fewer than min_component triangles, mesh_component_stats of the mesh as
+    it came, the number of triangles removed); scene 0 of a one-scene mesh"""
+    from . import util
+    clean, comps = util.mesh_clean_dev(mesh, min_triangles=int(min_component))
+    removed = int(mesh["n_triangles"][0].item()) - int(clean["n_triangles"][0].item())
+    return dict(mesh, **clean), mesh_component_stats(comps)[0], removed
 
 
 def mesh_summary(stats):
@@ -855,7 +897,7 @@ SCENE_BAD_ROT, SCENE_BAD_TRANS = 10.0, 0.3       # a pair estimate is wrong beyo
 
 
 def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, dataset=None, keypoints=200, seed=0, exp=None, mesh=False, refine=0,
-                    render=False, **sync):
+                    render=False, mesh_min_component=None, **sync):
     """Scenes of posed views -> estimated pairs -> synchronised absolute poses -> what they do to the reconstruction.
     scenes: synth.render_scene dicts; pipe_or_method: a RelativePosePipeline, or "fgs" / "gs" / "cgs" (then `dataset` names the scenes').
     Per scene: mine_pairs, the pair method on the mined pairs through evaluate_pairs / evaluate_fgs / _gs / _cgs as they are (verify and
@@ -867,7 +909,9 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
     'good_downweighted' (the share of each kind that is down-weighted; NaN for an empty kind), 'cost', 'last_step'.
     fuse=voxel: 'fuse_accuracy' / 'fuse_completeness' (reconstruction_scores of fuse_views of the largest component's views under the
     synchronised poses against the same fusion under R_k inv(R_gauge)), 'fuse_points', 'fuse_views'; exp: the surface is written to
-    <exp>.scene<k>.ply.  mesh=True (with fuse): 'mesh' = mesh_stats of the estimate's fusion, and <exp>.scene<k>.mesh.ply next to the cloud.
+    <exp>.scene<k>.ply.  mesh=True (with fuse): 'mesh' = mesh_stats of the estimate's fusion, and <exp>.scene<k>.mesh.ply next to the cloud;
+    mesh_min_component=N: of that mesh without its components of fewer than N triangles (the cloud stays), with 'mesh_components' and
+    'mesh_removed_triangles'.
     refine=rounds (with fuse): the largest component's synchronised poses are refined against the fused volume (refine_scene,
     re-gauged to the component's first view) before the final fusion, which then uses them; the record gains 'refine_rounds',
     'refine_err_rot' / 'refine_err_t' [2, views] (absolute_pose_errors before and after), 'refine_wall_median' [2] (the surface's median
@@ -964,6 +1008,9 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
                 if exp is not None:
                     rec['render_npz'] = save_render(f"{exp}.scene{k}.render.npz", rv)
             if mesh:
+                if mesh_min_component is not None:
+                    est, rec['mesh_components'], rec['mesh_removed_triangles'] = clean_mesh(est, mesh_min_component)
+                    n = int(est["n_points"][0].item())
                 rec['mesh'] = mesh_stats(est)[0]
                 if exp is not None:
                     rec['mesh_ply'] = f"{exp}.scene{k}.mesh.ply"
@@ -995,6 +1042,9 @@ def scenes_summary(recs):
                    refine_held_views=int(sum(r['refine_held_views'] for r in rr)))
     if recs and any('mesh' in r for r in recs):
         out.update(mesh_summary([r['mesh'] for r in recs if 'mesh' in r]), mesh_ply=[r['mesh_ply'] for r in recs if 'mesh_ply' in r])
+    if recs and any('mesh_components' in r for r in recs):
+        rr = [r for r in recs if 'mesh_components' in r]
+        out.update(mesh_clean_summary([r['mesh_components'] for r in rr], [r['mesh_removed_triangles'] for r in rr]))
     return out
 
 
@@ -1324,6 +1374,10 @@ def _cli_parser_completion():
                          "into (util.tsdf_align_dev, DESIGN.md 4.19), ROUNDS times, before the final fusion.  The JSON line gains, before and "
                          "after: refine_abs_err_rot_median / _t_median (absolute pose errors), refine_wall_median (the surface's median distance "
                          "to the room's walls, voxels), and refine_held_views (views with a direction the volume does not constrain)")
+    ap.add_argument("--mesh-min-component", type=int, default=None, metavar="N",
+                    help="--mesh: drop the mesh's connected components of fewer than N triangles (vertex connectivity, DESIGN.md 4.21) and its "
+                         "unused vertices before the mesh statistics and <exp>.scene<k>.mesh.ply; the JSON line gains mesh_components_median, "
+                         "mesh_largest_share_median (both of the mesh as extracted) and mesh_removed_triangles_median.  The cloud is not touched")
     ap.add_argument("--mesh", action="store_true",
                     help="--mine-pairs --fuse VOXEL / --reconstruct --fuse VOXEL: also extract each fused scene's triangle mesh (marching cubes, "
                          "DESIGN.md 4.18); the JSON line gains the medians of mesh_stats (triangles, area, border edges) and the number of "
@@ -1371,6 +1425,8 @@ def main(argv=None):
 
     if args.mesh and (args.fuse is None or not (args.mine_pairs or args.reconstruct)):
         raise SystemExit("--mesh applies to --mine-pairs --fuse VOXEL and to --reconstruct --fuse VOXEL")
+    if args.mesh_min_component is not None and (not args.mesh or args.mesh_min_component < 1):
+        raise SystemExit("--mesh-min-component N >= 1 applies to --mesh")
 
     if args.render and (args.fuse is None or not (args.mine_pairs or args.reconstruct)):
         raise SystemExit("--render applies to --mine-pairs --fuse VOXEL and to --reconstruct --fuse VOXEL")
@@ -1405,7 +1461,8 @@ def main(argv=None):
         t0 = time.perf_counter()
         scenes = [synth.render_scene(args.seed + s, args.scene_views, ds) for s in range(args.scenes)]
         recs = evaluate_scenes(who, scenes, dev, verify=args.verify, fuse=args.fuse, dataset=ds, keypoints=args.keypoints, seed=args.seed,
-                               exp=args.exp, mesh=args.mesh, refine=args.refine, render=args.render)
+                               exp=args.exp, mesh=args.mesh, refine=args.refine, render=args.render,
+                               mesh_min_component=args.mesh_min_component)
         torch.cuda.synchronize()
         line = {"reconstruct": True, "method": args.method, "dataset": ds, "scenes": args.scenes, "views": args.scene_views,
                 "seconds": time.perf_counter() - t0, "verify": args.verify, "fuse": args.fuse}
@@ -1429,6 +1486,7 @@ def main(argv=None):
         entries = []
         wall, fuse_points, plys = [], 0, []
         meshes, mesh_plys = [], []
+        mesh_comps, mesh_removed = [], []
         renders, render_npz = [], []
         t0 = time.perf_counter()
         for s in range(args.scenes):
@@ -1453,6 +1511,12 @@ def main(argv=None):
                     if args.exp is not None:
                         render_npz.append(save_render(f"{args.exp}.scene{s}.render.npz", rv))
                 if args.mesh:
+                    if args.mesh_min_component is not None:                 # the cloud above stays; the mesh loses its small components
+                        surf, cs, removed = clean_mesh(surf, args.mesh_min_component)
+                        mesh_comps.append(cs)
+                        mesh_removed.append(removed)
+                        n = int(surf["n_points"][0].item())
+                        pts = surf["points"][0, :n].cpu().numpy()
                     meshes.append(mesh_stats(surf)[0])
                     if args.exp is not None:
                         mesh_plys.append(f"{args.exp}.scene{s}.mesh.ply")
@@ -1473,6 +1537,8 @@ def main(argv=None):
                         fuse_wall_err_p90=float(np.percentile(e, 90)) if e.size else float("nan"), fuse_points=fuse_points, fuse_ply=plys)
         if args.mesh:
             line.update(mesh_summary(meshes), mesh_ply=mesh_plys)
+        if args.mesh_min_component is not None:
+            line.update(mesh_clean_summary(mesh_comps, mesh_removed))
         if args.render:
             line.update(render_summary(renders, args.fuse), render_npz=render_npz)
         print(json.dumps(line), flush=True)

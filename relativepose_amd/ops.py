@@ -45,6 +45,8 @@ Operator                    replaces (reference file:line)
   tsdf_align                no counterpart: view poses refined against the fused TSDF volume, frame-to-model Gauss-Newton
   tsdf_render               no counterpart: depth, normal and colour panoramas marched out of the fused TSDF volume
   tsdf_mesh                 no counterpart: tsdf_surface's cloud plus the triangles of a marching-cubes mesh over the same volume
+  mesh_components, mesh_filter
+                            no counterpart: the connected components of tsdf_mesh's meshes, and the mesh without the ones not kept
   tsdf_fuse, tsdf_surface   no counterpart: posed depth panoramas merged into a TSDF volume and its surface cloud
   pose_sync                 no counterpart: the relative poses of a scene's pairs synchronised into one pose per view
   affinity_topk             rpmodule.py:342-379
@@ -125,6 +127,16 @@ _lib.define("tsdf_surface(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Ten
 # the state of tsdf_fuse -> tsdf_surface's five outputs, triangles i32 [S,max_triangles,3] (indices into the scene's vertex list), n_triangles i32 [S]
 _lib.define("tsdf_mesh(Tensor tsdf_sum, Tensor weight, Tensor? color_sum, Tensor origin, float voxel, int min_weight=1, "
             "int max_points=65536, int max_triangles=131072) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+# tsdf_mesh's points f64 [S,cap,3], n_points i32 [S], triangles i32 [S,cap_tri,3], n_triangles i32 [S] -> vertex_label i32 [S,cap], tri_label i32
+# [S,cap_tri], n_components, bad_triangles i32 [S], comp_root, comp_vertices, comp_triangles i32 [S,max_components], comp_area i64
+# [S,max_components], rounds i32 [1]
+_lib.define("mesh_components(Tensor points, Tensor n_points, Tensor triangles, Tensor n_triangles, float area_scale, int max_components, "
+            "int max_rounds=1024, bool truncated=False) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+# a mesh, mesh_components' two label arrays and keep u8 / bool [S,cap_comp] -> tsdf_mesh's seven outputs compacted (colors empty without
+# colors), vertex_map i32 [S,cap]
+_lib.define("mesh_filter(Tensor points, Tensor normals, Tensor? colors, Tensor n_points, Tensor triangles, Tensor n_triangles, Tensor vertex_label, "
+            "Tensor tri_label, Tensor keep, bool drop_unused=True, bool truncated=False) "
+            "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 # the state of tsdf_fuse, depth f32 [V,h,4h], pose f64 [V,4,4] world -> camera, scene_of_view integer [V] (read on the host) -> pose f64 [V,4,4],
 # eig f64 [V,6], held i32 [V], sums i64 [V,32], rms f64 [V,2], trace_pose f64 [V,iters+1,4,4] and trace_sums i64 [V,iters+1,32] (empty without trace)
 _lib.define("tsdf_align(Tensor tsdf_sum, Tensor weight, Tensor origin, float voxel, Tensor depth, Tensor pose, Tensor scene_of_view, int dataset, "
@@ -320,6 +332,19 @@ def _tsdf_mesh(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_poi
             m["triangles"], m["n_triangles"])
 
 
+def _mesh_components(points, n_points, triangles, n_triangles, area_scale, max_components, max_rounds=1024, truncated=False):
+    c = _util.mesh_components_dev({"points": points, "n_points": n_points, "triangles": triangles, "n_triangles": n_triangles}, float(area_scale),
+                                  int(max_components), int(max_rounds), bool(truncated))
+    return tuple(c[k] for k in _util.COMPONENT_KEYS) + (torch.tensor([c["rounds"]], dtype=torch.int32, device=points.device),)
+
+
+def _mesh_filter(points, normals, colors, n_points, triangles, n_triangles, vertex_label, tri_label, keep, drop_unused=True, truncated=False):
+    mesh = {"points": points, "normals": normals, "colors": colors, "n_points": n_points, "triangles": triangles, "n_triangles": n_triangles}
+    m = _util.mesh_filter_dev(mesh, {"vertex_label": vertex_label, "tri_label": tri_label}, keep, bool(drop_unused), bool(truncated))
+    return (m["points"], m["normals"], (points.new_empty(0, dtype=torch.float32) if m["colors"] is None else m["colors"]), m["valid"], m["n_points"],
+            m["triangles"], m["n_triangles"], m["vertex_map"])
+
+
 def _tsdf_align(tsdf_sum, weight, origin, voxel, depth, pose, scene_of_view, dataset, iters=12, eig_min=0.0043, stride=1, min_weight=1, trace=False):
     S, nz, ny, nx = tsdf_sum.shape
     st = {"tsdf_sum": tsdf_sum, "weight": weight, "origin": origin.cpu().numpy(), "dims": (nx, ny, nz), "voxel": float(voxel),
@@ -373,7 +398,8 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("dense_nn", _dense_nn), ("descriptor_rank", _descriptor_rank), ("sift_describe", _sift_describe), ("sift_rank", _sift_rank),
                    ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals),
                    ("frames_to_pano", _frames_to_pano), ("overlap", _overlap), ("visibility", _visibility),
-                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("tsdf_mesh", _tsdf_mesh), ("tsdf_align", _tsdf_align), ("tsdf_render", _tsdf_render),
+                   ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("tsdf_mesh", _tsdf_mesh), ("mesh_components", _mesh_components),
+                   ("mesh_filter", _mesh_filter), ("tsdf_align", _tsdf_align), ("tsdf_render", _tsdf_render),
                    ("pose_sync", _pose_sync)):
     _lib.impl(_name, _fn, "CUDA")
 
@@ -528,6 +554,20 @@ def _m_tsdf_mesh(tsdf_sum, weight, color_sum, origin, voxel, min_weight=1, max_p
         tsdf_sum.new_empty(S, int(max_triangles), 3, dtype=torch.int32), tsdf_sum.new_empty(S, dtype=torch.int32))
 
 
+def _m_mesh_components(points, n_points, triangles, n_triangles, area_scale, max_components, max_rounds=1024, truncated=False):
+    S, cap, cap_tri, cc = points.shape[0], points.shape[1], triangles.shape[1], int(max_components)
+    n = lambda dt, *s: points.new_empty(*s, dtype=dt)
+    return (n(torch.int32, S, cap), n(torch.int32, S, cap_tri), n(torch.int32, S), n(torch.int32, S), n(torch.int32, S, cc), n(torch.int32, S, cc),
+            n(torch.int32, S, cc), n(torch.int64, S, cc), n(torch.int32, 1))
+
+
+def _m_mesh_filter(points, normals, colors, n_points, triangles, n_triangles, vertex_label, tri_label, keep, drop_unused=True, truncated=False):
+    S, cap, cap_tri = points.shape[0], points.shape[1], triangles.shape[1]
+    n = lambda dt, *s: points.new_empty(*s, dtype=dt)
+    return (n(torch.float64, S, cap, 3), n(torch.float64, S, cap, 3), n(torch.float32, 0) if colors is None else n(torch.float32, S, cap, 3),
+            n(torch.uint8, S, cap), n(torch.int32, S), n(torch.int32, S, cap_tri, 3), n(torch.int32, S), n(torch.int32, S, cap))
+
+
 def _m_tsdf_align(tsdf_sum, weight, origin, voxel, depth, pose, scene_of_view, dataset, iters=12, eig_min=0.0043, stride=1, min_weight=1, trace=False):
     V, E = depth.shape[0], int(iters) + 1
     n = lambda dt, *s: depth.new_empty(*s, dtype=dt)
@@ -569,11 +609,12 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("dense_nn", _m_dense_nn), ("descriptor_rank", _m_descriptor_rank), ("sift_describe", _m_sift_describe), ("sift_rank", _m_sift_rank),
                    ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals),
                    ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap), ("visibility", _m_visibility),
-                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("tsdf_mesh", _m_tsdf_mesh), ("tsdf_align", _m_tsdf_align), ("tsdf_render", _m_tsdf_render),
+                   ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("tsdf_mesh", _m_tsdf_mesh), ("mesh_components", _m_mesh_components),
+                   ("mesh_filter", _m_mesh_filter), ("tsdf_align", _m_tsdf_align), ("tsdf_render", _m_tsdf_render),
                    ("pose_sync", _m_pose_sync)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
        "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals",
-       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "tsdf_mesh", "tsdf_align", "tsdf_render", "pose_sync")
+       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "tsdf_mesh", "mesh_components", "mesh_filter", "tsdf_align", "tsdf_render", "pose_sync")

@@ -777,6 +777,152 @@ def tsdf_mesh_dev(state, min_weight=1, max_points=None, max_triangles=None):
     return out
 
 
+def _mesh_caps(mesh, what, truncated):
+    """(S, cap, cap_tri) of a mesh dict; ValueError where a count exceeds its cap unless truncated"""
+    import torch
+    pts, tri = mesh["points"], mesh["triangles"]
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.dtype != torch.float64 or tri.dim() != 3 or tri.shape[2] != 3 or tri.dtype != torch.int32 or \
+            tri.shape[0] != pts.shape[0]:
+        raise ValueError(f"{what} takes points [S,cap,3] float64 and triangles [S,cap_tri,3] int32")
+    S, cap, cap_tri = int(pts.shape[0]), int(pts.shape[1]), int(tri.shape[1])
+    if not truncated and S and (int(mesh["n_points"].max().item()) > cap or int(mesh["n_triangles"].max().item()) > cap_tri):
+        raise ValueError(f"{what}: a scene's n_points or n_triangles exceeds its capacity (a truncated mesh): pass truncated=True to label what was written")
+    return S, cap, cap_tri
+
+
+COMPONENT_KEYS = ("vertex_label", "tri_label", "n_components", "bad_triangles", "comp_root", "comp_vertices", "comp_triangles", "comp_area")
+
+
+def mesh_components_dev(mesh, area_scale=None, max_components=None, max_rounds=1024, truncated=False):
+    """relpose_mesh_components (include/relpose.h): the connected components of tsdf_mesh_dev's meshes (any dict with "points"
+    [S,cap,3] f64, "n_points" [S] i32, "triangles" [S,cap_tri,3] i32, "n_triangles" [S] i32 on the GPU).  VERTEX connectivity: triangles that
+    share a vertex index are one component; a component's id is its rank by smallest vertex index.
+    -> {"vertex_label" [S,cap] i32 (-1: unused), "tri_label" [S,cap_tri] i32 (-1: bad or beyond the count), "n_components" [S] i32 (the true
+    count), "bad_triangles" [S] i32, "comp_root", "comp_vertices", "comp_triangles" [S,cap_comp] i32, "comp_area" [S,cap_comp] i64, "rounds" int,
+    "area_scale" float}.  cap_comp = max_components; None sizes it to the largest scene by a counting call first (at least 1).  comp_area is in
+    units of 1 / area_scale; None = 2^20 / voxel^2 with the mesh's "voxel" (1.0 if it has none).  More than max_rounds propagation rounds
+    raises RuntimeError.  A count above its capacity raises ValueError unless truncated=True."""
+    import torch
+    _lib.require_gpu()
+    S, cap, cap_tri = _mesh_caps(mesh, "mesh_components_dev", truncated)
+    if area_scale is None:
+        area_scale = float(2 ** 20) / float(mesh.get("voxel", 1.0)) ** 2
+    L = _lib.lib()
+    nbytes = L.relpose_mesh_components_workspace_bytes(S, cap, cap_tri)
+    if nbytes == 0:
+        raise ValueError("mesh_components_dev: sizes outside relpose_mesh_components' limits")
+    dev = mesh["points"].device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    pts, tri = mesh["points"].contiguous(), mesh["triangles"].contiguous()
+    npts, ntri = mesh["n_points"].contiguous(), mesh["n_triangles"].contiguous()
+
+    def call(cap_comp):
+        z = lambda n, dt: torch.zeros(S, n, dtype=dt, device=dev)
+        out = {"vertex_label": z(cap, torch.int32), "tri_label": z(cap_tri, torch.int32),
+               "n_components": torch.zeros(S, dtype=torch.int32, device=dev), "bad_triangles": torch.zeros(S, dtype=torch.int32, device=dev),
+               "comp_root": z(cap_comp, torch.int32), "comp_vertices": z(cap_comp, torch.int32), "comp_triangles": z(cap_comp, torch.int32),
+               "comp_area": z(cap_comp, torch.int64)}
+        rounds = _lib.C.c_int(0)
+        a = _lib.MeshComponentsArgs()
+        a.struct_size = _lib.C.sizeof(_lib.MeshComponentsArgs)
+        a.n_scenes, a.cap, a.cap_tri, a.cap_comp, a.max_rounds = S, cap, cap_tri, cap_comp, int(max_rounds)
+        a.triangles, a.n_triangles, a.n_points, a.points = tri.data_ptr(), ntri.data_ptr(), npts.data_ptr(), pts.data_ptr()
+        a.area_scale = float(area_scale)
+        for k in COMPONENT_KEYS:
+            setattr(a, k, out[k].data_ptr() if out[k].numel() else 0)
+        a.rounds_host = _lib.C.addressof(rounds)
+        a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), nbytes, _lib.stream_ptr()
+        rc_ = L.relpose_mesh_components(_lib.C.byref(a))
+        if rc_ == -1:
+            raise ValueError("relpose_mesh_components: invalid arguments (sizes outside the limits, area_scale not finite and > 0, or max_rounds < 1)")
+        if rc_ == _lib.MESH_EROUNDS:
+            raise RuntimeError(f"relpose_mesh_components: labels still moved after max_rounds = {int(max_rounds)} rounds")
+        _lib.check(rc_, "relpose_mesh_components")
+        out["rounds"] = int(rounds.value)
+        out["area_scale"] = float(area_scale)
+        return out
+
+    if max_components is None:
+        max_components = max(1, int(call(0)["n_components"].max().item()))
+    return call(int(max_components))
+
+
+def mesh_filter_dev(mesh, comps, keep, drop_unused=True, truncated=False):
+    """relpose_mesh_filter (include/relpose.h): the mesh without the components whose keep [S,cap_comp] (bool or uint8, on the
+    GPU) is 0, compacted in order; comps is mesh_components_dev's dict.  Unused vertices go too unless drop_unused=False.
+    -> a mesh dict of tsdf_mesh_dev's keys with the same capacities (rows beyond the new counts are zero) plus "vertex_map" [S,cap] i32, old
+    index -> new index or -1."""
+    import torch
+    _lib.require_gpu()
+    S, cap, cap_tri = _mesh_caps(mesh, "mesh_filter_dev", truncated)
+    dev = mesh["points"].device
+    keep = keep.to(device=dev, dtype=torch.uint8).contiguous()
+    if keep.dim() != 2 or keep.shape[0] != S:
+        raise ValueError("mesh_filter_dev takes keep [S,cap_comp]")
+    cap_comp = int(keep.shape[1])
+    vl, tl = comps["vertex_label"].contiguous(), comps["tri_label"].contiguous()
+    if tuple(vl.shape) != (S, cap) or tuple(tl.shape) != (S, cap_tri) or vl.dtype != torch.int32 or tl.dtype != torch.int32:
+        raise ValueError("mesh_filter_dev: the labels are not this mesh's")
+    L = _lib.lib()
+    nbytes = L.relpose_mesh_filter_workspace_bytes(S, cap, cap_tri)
+    if nbytes == 0:
+        raise ValueError("mesh_filter_dev: sizes outside relpose_mesh_filter's limits")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    col = mesh.get("colors")
+    src = {k: (None if mesh.get(k) is None else mesh[k].contiguous()) for k in ("points", "normals", "colors", "n_points", "triangles", "n_triangles")}
+    out = {"points": torch.zeros(S, cap, 3, dtype=torch.float64, device=dev), "normals": torch.zeros(S, cap, 3, dtype=torch.float64, device=dev),
+           "colors": None if col is None else torch.zeros(S, cap, 3, dtype=torch.float32, device=dev),
+           "valid": torch.empty(S, cap, dtype=torch.uint8, device=dev), "n_points": torch.empty(S, dtype=torch.int32, device=dev),
+           "triangles": torch.zeros(S, cap_tri, 3, dtype=torch.int32, device=dev), "n_triangles": torch.empty(S, dtype=torch.int32, device=dev),
+           "vertex_map": torch.empty(S, cap, dtype=torch.int32, device=dev)}
+    a = _lib.MeshFilterArgs()
+    a.struct_size = _lib.C.sizeof(_lib.MeshFilterArgs)
+    a.n_scenes, a.cap, a.cap_tri, a.cap_comp, a.drop_unused = S, cap, cap_tri, cap_comp, int(bool(drop_unused))
+    for k, v in src.items():
+        setattr(a, k, 0 if v is None else v.data_ptr())
+    a.vertex_label, a.tri_label, a.keep = vl.data_ptr(), tl.data_ptr(), (keep.data_ptr() if cap_comp else 0)
+    a.out_points, a.out_normals, a.out_colors = out["points"].data_ptr(), out["normals"].data_ptr(), (0 if col is None else out["colors"].data_ptr())
+    a.out_valid, a.out_n_points = out["valid"].data_ptr(), out["n_points"].data_ptr()
+    a.out_triangles, a.out_n_triangles, a.vertex_map = out["triangles"].data_ptr(), out["n_triangles"].data_ptr(), out["vertex_map"].data_ptr()
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), nbytes, _lib.stream_ptr()
+    rc_ = L.relpose_mesh_filter(_lib.C.byref(a))
+    if rc_ == -1:
+        raise ValueError("relpose_mesh_filter: invalid arguments (sizes outside the limits)")
+    _lib.check(rc_, "relpose_mesh_filter")
+    return out                                                 # (the workspace is freed in stream order: the launches are only enqueued)
+
+
+def mesh_keep_mask(comps, min_triangles=None, min_area=None, largest=None):
+    """mesh_clean_dev's selection with torch operators on the device: keep [S,cap_comp] bool, the criteria ANDed over the components that
+    exist.  min_triangles: comp_triangles >= it; min_area (in the mesh's length unit squared): comp_area >= min_area area_scale; largest = k:
+    the k components with the most triangles, ties to the lower id."""
+    import torch
+    ct = comps["comp_triangles"]
+    S, cap_comp = int(ct.shape[0]), int(ct.shape[1])
+    ids = torch.arange(cap_comp, device=ct.device)[None]
+    keep = ids < comps["n_components"][:, None]
+    if min_triangles is not None:
+        keep &= ct >= int(min_triangles)
+    if min_area is not None:
+        keep &= comps["comp_area"].to(torch.float64) >= float(min_area) * comps["area_scale"]
+    if largest is not None:
+        key = torch.where(keep, ct.to(torch.int64), torch.full_like(ct, -1, dtype=torch.int64))
+        order = torch.argsort(key, dim=1, descending=True, stable=True)          # stable: ties stay in ascending id
+        top = torch.zeros_like(keep)
+        k = max(0, min(int(largest), cap_comp))
+        top.scatter_(1, order[:, :k], True)
+        keep &= top
+    return keep
+
+
+def mesh_clean_dev(mesh, min_triangles=None, min_area=None, largest=None, drop_unused=True, truncated=False, area_scale=None):
+    """Drop a mesh's small connected components: mesh_components_dev, mesh_keep_mask, mesh_filter_dev.
+    -> (clean_mesh, comps); comps describes the mesh as it came in and has "keep" [S,cap_comp] bool."""
+    comps = mesh_components_dev(mesh, area_scale, truncated=truncated)
+    comps["keep"] = mesh_keep_mask(comps, min_triangles, min_area, largest)
+    return mesh_filter_dev(mesh, comps, comps["keep"], drop_unused, truncated), comps
+
+
 def tsdf_align_dev(state, depth, R, scene_of_view=None, iters=12, eig_min=None, stride=1, trace=False, min_weight=1):
     """relpose_tsdf_align (include/relpose.h): refine the world -> camera poses R [V,4,4] (float64 host array or CUDA tensor)
     of the depth panoramas depth [V,h,4h] f32 against tsdf_fuse_dev's state, so that each view's measured points lie on the zero level of the
