@@ -1593,8 +1593,23 @@ int relpose_scnet_forward(RelposeSCNet* net, const float* x, float* out, int32_t
  *                         touches it first (RELPOSE_FWD_NEW_WORKSPACE needs the first call to carry the flag).  0 = not tracked.
  *   reserved1             must be NULL (a non-NULL value, like an unknown flag bit, returns RELPOSE_EINVAL before anything is enqueued).
  * Error behaviour: a call that returns != 0 leaves no self-stream record on the workspace (the next forward recomputes everything); a
- * self-cached plan that cannot be built falls back to the full forward (same output) instead of failing. */
-enum { RELPOSE_FWD_ZERO_WARP = 1, RELPOSE_FWD_POSE_OUTPUTS = 2, RELPOSE_FWD_NEW_WORKSPACE = 4 };
+ * self-cached plan that cannot be built falls back to the full forward (same output) instead of failing.
+ *
+ * RELPOSE_FWD_SAMPLED_OUTPUTS (with sample_pts, sample_npts, sample_npts_max): the pose-outputs forward for a caller that only SAMPLES its
+ * output at keypoints (relpose_sample_primitives with the same pts / npts / npts_max; W must be 4 H).  The plan is the pose-outputs plan up
+ * to and including deconv2 and its BatchNorm statistics (dense); in place of the dense 1x1 heads and the output resize one kernel writes,
+ * for every image and every keypoint k < sample_npts[img], exactly the elements of `out` that relpose_sample_primitives loads:
+ *   channels 3:7 at (ty .. ty + 1, tx .. tx + 1) and channels 7+S : 7+S+32 at (yi .. yi + 1, xi .. xi + 1)
+ * (tx, ty, xi, yi as csrc/sample_pixels.h derives them from the keypoint), each bit for bit the value of the RELPOSE_FWD_POSE_OUTPUTS
+ * forward -- also where the keypoint lies inside the observed box (the sampler multiplies the network value by 0 there, which keeps a NaN).
+ * EVERY OTHER ELEMENT OF `out` IS UNSPECIFIED after such a forward (it keeps whatever it held).  sample_pts (double [n, npts_max, 2], pixel
+ * coordinates) and sample_npts (int32 [n]) are device arrays read by that kernel on every call, on tail_stream when there is one; entries
+ * k >= sample_npts[img] are never read; a block pixel outside the map is not written.  A constructor variant ignores the flag like
+ * RELPOSE_FWD_POSE_OUTPUTS (the plain dense forward).  Self-stream cache: a sampled forward stores no accumulator snapshot of the 1x1
+ * heads and, when it fills the cache, records none -- a snapshot an earlier tag left in the workspace is never picked up: a later forward
+ * of its tag that runs the dense heads computes the skip lines of rgb, n and d from A1 (whose self blocks stay in the workspace), bitwise the
+ * same output; the deconv3 / deconv2 snapshots are stored and used as by a pose-outputs forward.  relpose_scnet_last_tail tells which tail ran. */
+enum { RELPOSE_FWD_ZERO_WARP = 1, RELPOSE_FWD_POSE_OUTPUTS = 2, RELPOSE_FWD_NEW_WORKSPACE = 4, RELPOSE_FWD_SAMPLED_OUTPUTS = 32 };   /* (8 and 16 named a removed form and stay invalid) */
 typedef struct RelposeForwardArgs {
     uint32_t struct_size;
     int32_t flags;
@@ -1608,13 +1623,22 @@ typedef struct RelposeForwardArgs {
     uint64_t self_tag;
     uint64_t workspace_generation;
     void* reserved1;
+    const double* sample_pts;        /* RELPOSE_FWD_SAMPLED_OUTPUTS: device, [n_images, sample_npts_max, 2] */
+    const int32_t* sample_npts;      /* device, [n_images] */
+    int32_t sample_npts_max, reserved2;
 } RelposeForwardArgs;
 int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args);
+
+/* Which tail the last forward of `net` ran: 0 = the dense 1x1 heads and output resize, 1 = the sampled tail (RELPOSE_FWD_SAMPLED_OUTPUTS),
+ * -1 = no forward yet.  Host-only.  For tests and profiles. */
+int relpose_scnet_last_tail(RelposeSCNet* net);
 
 /* Multiply-accumulates one forward of a plan family executes (host-only, no device access): flags as above, self_cached != 0 = the plan
  * a forward takes when it finds its self_tag on the workspace: 1 = behind a fill that stored every skip head's halves, 2 = behind a
  * pose-outputs fill (no rgb halves in the workspace: a forward without RELPOSE_FWD_POSE_OUTPUTS computes them, and they are counted; with
- * the flag 2 counts what 1 does).  The full forward (flags 0, self_cached 0) counts every member of
+ * the flag 2 counts what 1 does), 3 = behind a sampled-outputs fill (no snapshot of the 1x1 heads either: their skip lines are counted).
+ * RELPOSE_FWD_SAMPLED_OUTPUTS counts the pose-outputs plan without the 1x1 heads (the sampled tail's few multiply-adds depend on the
+ * keypoint count and are left out).  The full forward (flags 0, self_cached 0) counts every member of
  * model/mymodel.py:259-380; the level-0 plan and the self-stream cache count what they really launch.  bench.py divides the two for
  * its plan-aware in-loop roofline ("roofline.in_loop").  It is the STATIC plan that is counted: the patches and rows that the zero-tile lists
  * and conv4's row lists drop depend on the input and stay counted (relpose_scnet_zero_tiles / relpose_scnet_conv4_rows report them). */

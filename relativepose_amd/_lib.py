@@ -35,7 +35,8 @@ class ForwardArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", c_int), ("x", c_void_p), ("out", c_void_p),
                 ("n_images", c_int), ("H", c_int), ("W", c_int), ("reserved0", c_int),
                 ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p), ("tail_stream", c_void_p),
-                ("self_tag", C.c_uint64), ("workspace_generation", C.c_uint64), ("reserved1", c_void_p)]
+                ("self_tag", C.c_uint64), ("workspace_generation", C.c_uint64), ("reserved1", c_void_p),
+                ("sample_pts", c_void_p), ("sample_npts", c_void_p), ("sample_npts_max", c_int), ("reserved2", c_int)]
 
 
 class SCNetConfig(C.Structure):
@@ -366,6 +367,7 @@ SIGNATURES = {
     "relpose_scnet_plan_macs": (c_int, [c_void_p, c_int, c_int, c_int, C.POINTER(c_double)]),
     "relpose_scnet_layer_kernel": (c_int, [c_void_p, c_char_p, c_int]),
     "relpose_scnet_zero_tiles": (c_int, [c_void_p, c_void_p, c_void_p, C.POINTER(c_int64)]),
+    "relpose_scnet_last_tail": (c_int, [c_void_p]),
     "relpose_scnet_conv1_zero": (c_int, [c_void_p, c_void_p, c_void_p, C.POINTER(c_int64), c_void_p]),
     "relpose_scnet_conv4_rows": (c_int, [c_void_p, c_void_p, c_void_p, C.POINTER(c_int64)]),
     "relpose_scnet_read_tap": (c_int64, [c_void_p, c_char_p, c_void_p, c_void_p, c_void_p]),

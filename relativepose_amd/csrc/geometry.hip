@@ -12,6 +12,7 @@
 // descriptor gather must round like numpy / torch (no FMA fusion).
 #include "common.h"
 #include "rp_math.h"
+#include "sample_pixels.h"
 #include "skybox.h"
 #include <limits.h>
 
@@ -245,8 +246,10 @@ __global__ void sample_primitives_kernel(const float* __restrict__ f, int cf, in
     const float* on = obs_norm + (size_t)img * 3 * hw;
     const float* od = obs_depth + (size_t)img * hw;
     const double px = pts[((size_t)img * npts_max + k) * 2 + 0], py = pts[((size_t)img * npts_max + k) * 2 + 1];
-    // rputil.getPixel :88-119 (float64 bilinear of the float32 composed maps)
-    const int tx = (int)floor(px), ty = (int)floor(py);
+    // rputil.getPixel :88-119 (float64 bilinear of the float32 composed maps); the pixel indices come from sample_pixels.h, which the sampled
+    // tail of the SCNet forward shares (it writes exactly the elements of f this kernel loads)
+    const RpSamplePix sp = rp_sample_pixels(px, py, h);
+    const int tx = sp.tx, ty = sp.ty;
     const double fx1 = px - tx, fx0 = tx + 1 - px, fy1 = py - ty, fy0 = ty + 1 - py;
     float n00[3], n01[3], n10[3], n11[3], d00, d01, d10, d11;
     composed_pixel(fi, cf, on, od, hw, h, bx, compose, ty, tx, n00, d00);
@@ -269,10 +272,8 @@ __global__ void sample_primitives_kernel(const float* __restrict__ f, int cf, in
     double* po = pc + ((size_t)img * npts_max + k) * 3;
     po[0] = ox; po[1] = oy; po[2] = oz;
     // rputil.interpolate :43-58 in float32: pt = (x/W, y/H) cast to float32, x = pt*(W-1)
-    const float ptx = (float)(px / W), pty = (float)(py / h);
-    const float x = ptx * (float)(W - 1), y = pty * (float)(h - 1);
-    const float x0 = floorf(x), y0 = floorf(y);
-    const int xi = (int)x0, yi = (int)y0;
+    const float x = sp.x, y = sp.y, x0 = sp.x0, y0 = sp.y0;
+    const int xi = sp.xi, yi = sp.yi;
     const float wx0 = x0 + 1.0f - x, wy0 = y0 + 1.0f - y, wx1 = x - x0, wy1 = y - y0;
     const float* ff = fi + (size_t)feat_off * hw;
     float* fo = feat + ((size_t)img * npts_max + k) * 32;

@@ -25,6 +25,7 @@
 #include "common.h"
 #include "matcher_internal.h"      // g_rp_tune
 #include "conv1_zero_geom.h"        // c1z_range: conv1's zero-unit test
+#include "sample_pixels.h"          // rp_sample_pixels: the pixels relpose_sample_primitives reads (heads_sampled_kernel writes them)
 #include <map>
 #include <string>
 #include <vector>
@@ -2769,6 +2770,120 @@ __global__ __launch_bounds__(256) void resize_out_kernel(const float* __restrict
     }
 }
 
+// ---- the sampled tail (RELPOSE_FWD_SAMPLED_OUTPUTS): heads + output resize at the keypoints only ------------------------------
+// In place of heads_kernel<S, true> and resize_out_kernel: for every keypoint k < npts[img] exactly the elements of `out` (NCHW) that
+// sample_primitives_kernel (csrc/geometry.hip) loads -- channels 3:7 at (ty .. ty + 1, tx .. tx + 1) and the 32 feature channels at
+// (yi .. yi + 1, xi .. xi + 1), indices from rp_sample_pixels -- each bit for bit what the dense pair would have stored there:
+//  * per source pixel of the 224 x 224 maps the fused-multiply-add chains of heads_lanepix_kernel in its order (n, d: the A1 skip line, then
+//    the D2 line, then the bias; f: the two D2 lines, bias, tanhf); every chain is always computed from A1 / D2 (a snapshot holds the same bits),
+//  * lin_coef's taps and resize_out_kernel's blend as the compiler contracts it there (default fp-contract; read in its ISA):
+//    fma(ly0, fma(lx0, a, lx1 * b), ly1 * fma(lx0, c, lx1 * d)).
+// One wave per keypoint, no workgroup barrier.  A work item = (output pixel of the 2 x 2 block, tap of its 2 x 2 stencil): 16 per block, no
+// de-duplication of source pixels shared between taps (about 0.4 M head-pixel evaluations per forward at 64 x 200 keypoints: not worth a
+// list).  Lanes 0:16 evaluate the n and d heads of the (ty, tx) block's items, lanes 16:48 the f head of the (yi, xi) block's items (two
+// lanes per item, 16 outputs each: every output is a chain of its own); the results meet in the wave's LDS rows and the lanes then blend
+// and store the 16 + 128 output elements.  Keypoints that share pixels store the same bits.  A pixel outside the map is neither
+// evaluated nor stored (the sampler has no such keypoint: rputil.getPixel's precondition); entries k >= npts[img] are never read.
+struct SampledDesc {
+    const float* d2; const float* a1; const float2* ss_d2; const float2* ss_a1;
+    const float* w; const float* bias; float* out;
+    const double* pts; const int* npts;
+    int npts_max, cf, use_tanh, H, W;
+};
+
+__global__ __launch_bounds__(256) void heads_sampled_kernel(const SampledDesc sd) {
+    __shared__ float ndl[4][16][4];                    // per wave: item -> n0, n1, n2, d
+    __shared__ float fl[4][16][32];                    // per wave: item -> the 32 features
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int img = blockIdx.y, k = blockIdx.x * 4 + wave;
+    if (k >= sd.npts_max || k >= sd.npts[img]) return;                 // (wave-uniform)
+    const int H = sd.H, W = sd.W, cf = sd.cf, feat_off = cf - 32;
+    const double px = sd.pts[((size_t)img * sd.npts_max + k) * 2 + 0], py = sd.pts[((size_t)img * sd.npts_max + k) * 2 + 1];
+    const RpSamplePix sp = rp_sample_pixels(px, py, H);
+    const float shh = (float)RS / H, sww = (float)RS / W;          // as resize_out_kernel
+    const int g = img >> 1;                                         // BatchNorm group
+    const float2* ssd = sd.ss_d2 + (size_t)g * 224;
+    const float2* ssa = sd.ss_a1 + (size_t)g * 192;
+    // the item's output pixel, whether it lies in the map, and its source pixel
+    auto item_src = [&](int item, int by, int bx, int& oy, int& ox, size_t& spix) {
+        oy = by + (item >> 3); ox = bx + ((item >> 2) & 1);
+        if (oy < 0 || oy >= H || ox < 0 || ox >= W) return false;
+        int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
+        lin_coef(oy, shh, RS, y0, y1, ly0, ly1);
+        lin_coef(ox, sww, RS, x0, x1, lx0, lx1);
+        spix = ((size_t)img * RS + ((item & 2) ? y1 : y0)) * RS + ((item & 1) ? x1 : x0);
+        return true;
+    };
+    if (lane < 16) {
+        int oy, ox; size_t spix;
+        if (item_src(lane, sp.ty, sp.tx, oy, ox, spix)) {
+            const float* pa = sd.a1 + spix * 192;
+            const float* pd = sd.d2 + spix * 224;
+            float an[3] = {0.f, 0.f, 0.f}, ad = 0.f;
+            // weight image rows (HeadsDesc): 4 floats per input channel; D2[0:96] = rows 0:96, the A1 skip blocks of rgb / n / d = rows 96:192
+            for (int c = 0; c < 32; ++c) {                          // n: A1 skip line (self block 64:96)
+                const float2 sc = ssa[64 + c];
+                const float v = lrelu(pa[64 + c] * sc.x + sc.y, LRELU);
+                for (int j = 0; j < 3; ++j) an[j] = __builtin_fmaf(v, sd.w[(128 + c) * 4 + j], an[j]);
+            }
+            for (int c = 0; c < 32; ++c) {                          // d: A1 skip line (self block 128:160)
+                const float2 sc = ssa[128 + c];
+                const float v = lrelu(pa[128 + c] * sc.x + sc.y, LRELU);
+                ad = __builtin_fmaf(v, sd.w[(160 + c) * 4], ad);
+            }
+            for (int c = 0; c < 32; ++c) {                          // n: D2 line 32:64
+                const float2 sc = ssd[32 + c];
+                const float v = lrelu(pd[32 + c] * sc.x + sc.y, LRELU);
+                for (int j = 0; j < 3; ++j) an[j] = __builtin_fmaf(v, sd.w[(32 + c) * 4 + j], an[j]);
+            }
+            for (int c = 0; c < 32; ++c) {                          // d: D2 line 64:96
+                const float2 sc = ssd[64 + c];
+                const float v = lrelu(pd[64 + c] * sc.x + sc.y, LRELU);
+                ad = __builtin_fmaf(v, sd.w[(64 + c) * 4], ad);
+            }
+            for (int j = 0; j < 3; ++j) ndl[wave][lane][j] = an[j] + sd.bias[3 + j];
+            ndl[wave][lane][3] = ad + sd.bias[6];
+        }
+    } else if (lane < 48) {
+        const int item = (lane - 16) & 15, o0 = ((lane - 16) >> 4) * 16;
+        int oy, ox; size_t spix;
+        if (item_src(item, sp.yi, sp.xi, oy, ox, spix)) {
+            const float* pd = sd.d2 + spix * 224 + 160;
+            const float* wf = sd.w + 2304 + o0;                     // f rows: 32 floats per input channel of D2[160:224]
+            float af[16];
+#pragma unroll
+            for (int o = 0; o < 16; ++o) af[o] = 0.f;
+            for (int c = 0; c < 64; ++c) {
+                const float2 sc = ssd[160 + c];
+                const float v = lrelu(pd[c] * sc.x + sc.y, LRELU);
+#pragma unroll
+                for (int o = 0; o < 16; ++o) af[o] = __builtin_fmaf(v, wf[c * 32 + o], af[o]);
+            }
+#pragma unroll
+            for (int o = 0; o < 16; ++o) {
+                const float v = af[o] + sd.bias[feat_off + o0 + o];
+                fl[wave][item][o0 + o] = sd.use_tanh ? tanhf(v) : v;
+            }
+        }
+    }
+    rp_wave_lds_sync();
+    const size_t hw = (size_t)H * W;
+    float* const oi = sd.out + (size_t)img * cf * hw;
+    for (int e = lane; e < 16 + 128; e += 64) {
+        const bool nd = e < 16;
+        const int p = nd ? (e >> 2) : ((e - 16) >> 5), c = nd ? (e & 3) : ((e - 16) & 31);
+        const int oy = (nd ? sp.ty : sp.yi) + (p >> 1), ox = (nd ? sp.tx : sp.xi) + (p & 1);
+        if (oy < 0 || oy >= H || ox < 0 || ox >= W) continue;
+        int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
+        lin_coef(oy, shh, RS, y0, y1, ly0, ly1);
+        lin_coef(ox, sww, RS, x0, x1, lx0, lx1);
+        const float a = nd ? ndl[wave][p * 4 + 0][c] : fl[wave][p * 4 + 0][c], b = nd ? ndl[wave][p * 4 + 1][c] : fl[wave][p * 4 + 1][c];
+        const float cc = nd ? ndl[wave][p * 4 + 2][c] : fl[wave][p * 4 + 2][c], dd = nd ? ndl[wave][p * 4 + 3][c] : fl[wave][p * 4 + 3][c];
+        const float r = __fmaf_rn(ly0, __fmaf_rn(lx0, a, __fmul_rn(lx1, b)), __fmul_rn(ly1, __fmaf_rn(lx0, cc, __fmul_rn(lx1, dd))));
+        oi[(size_t)(nd ? 3 + c : feat_off + c) * hw + (size_t)oy * W + ox] = r;
+    }
+}
+
 // ---- host-side model ---------------------------------------------------------------------------------
 struct Phase {                       // one launch of the implicit GEMM
     int ntaps; signed char offy[16], offx[16];
@@ -2813,7 +2928,7 @@ struct RelposeSCNet {
     size_t w1_off = 0;           // conv1_mfma_kernel's weights inside d_w
     size_t wh_off = 0, bh_off = 0;   // fused-heads weight image and bias vector inside d_w
     std::map<std::pair<void*, int64_t>, void*> plans;   // (workspace, n | plan family bits) -> Plan* (each with its own device descriptor table)
-    struct SelfState { uint64_t tag = 0, gen = 0; int n = 0, H = 0, W = 0; int snap_heads = 0; bool c4_rows = false; };   // snap_heads: skip heads (bit 0 rgb, 1 n, 2 d) whose snapshots the filling forward stored; c4_rows: it left conv4's self-slice maps
+    struct SelfState { uint64_t tag = 0, gen = 0; int n = 0, H = 0, W = 0; int snap_heads = 0; int heads_snap = 0; bool c4_rows = false; };   // snap_heads: skip heads (bit 0 rgb, 1 n, 2 d) whose deconv3 / deconv2 snapshots the filling forward stored; heads_snap: those whose 1x1-head snapshot rows (HeadsDesc::snap) it stored -- none behind a sampled fill; c4_rows: it left conv4's self-slice maps
     std::map<void*, SelfState> self_state;          // workspace -> whose self-view streams it holds (relpose_scnet_forward4)
     std::map<std::string, Layer> layers;
     std::map<std::string, Buf> bufs;
@@ -2821,6 +2936,7 @@ struct RelposeSCNet {
     size_t gb_floats = 0;
     // timing
     int last_n = 0;
+    int last_tail = -1;          // relpose_scnet_last_tail: 0 = dense heads + resize, 1 = heads_sampled_kernel
     // relpose_scnet_zero_tiles: the last forward's list counts (device, null = it ran without lists) and the workgroups its conv2 / conv3 launches cover
     const int* last_zt_counts = nullptr;
     // relpose_scnet_conv4_rows: the last forward's {rows listed, list path} per K slice (device, null = no lists) and the rows of each slice
@@ -3866,13 +3982,20 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     const uint64_t self_tag = (!variant && args->struct_size >= offsetof(RelposeForwardArgs, self_tag) + sizeof(uint64_t)) ? args->self_tag : 0;
     const uint64_t ws_gen = args->struct_size >= offsetof(RelposeForwardArgs, workspace_generation) + sizeof(uint64_t) ? args->workspace_generation : 0;
     if (!net->finalized || !x || !out || !workspace || n <= 0 || (n & 1) || H <= 0 || W <= 0 || n >= (1 << 24)) return RELPOSE_EINVAL;
-    if (flags & ~(RELPOSE_FWD_ZERO_WARP | RELPOSE_FWD_POSE_OUTPUTS | RELPOSE_FWD_NEW_WORKSPACE)) return RELPOSE_EINVAL;
+    if (flags & ~(RELPOSE_FWD_ZERO_WARP | RELPOSE_FWD_POSE_OUTPUTS | RELPOSE_FWD_NEW_WORKSPACE | RELPOSE_FWD_SAMPLED_OUTPUTS)) return RELPOSE_EINVAL;
+    // the sampled tail: the pose-outputs plan with heads_sampled_kernel in place of the dense heads and the output resize
+    const bool sampled = (flags & RELPOSE_FWD_SAMPLED_OUTPUTS) != 0 && !variant;
+    if (flags & RELPOSE_FWD_SAMPLED_OUTPUTS) {
+        if (args->struct_size < offsetof(RelposeForwardArgs, sample_npts_max) + sizeof(int32_t)) return RELPOSE_EINVAL;
+        if (!args->sample_pts || !args->sample_npts || args->sample_npts_max <= 0 || W != 4 * H) return RELPOSE_EINVAL;
+        if (!variant && net->S != 15 && net->S != 21) return RELPOSE_EINVAL;         // (like the pose-outputs plan: the fused heads' weight image)
+    }
     // one call = one forward, the bottleneck chain stays on `stream` (the two-part / third-stream forms lost their A/Bs, round 5, and were removed)
     if (args->struct_size >= offsetof(RelposeForwardArgs, reserved1) + sizeof(void*) && args->reserved1) return RELPOSE_EINVAL;
     const int G = n / 2;
     // (nothing to share with one BatchNorm group; the tile kernels' patch pairing wants the 2-image members' patch count even as well)
     const bool zero_warp = (flags & RELPOSE_FWD_ZERO_WARP) && n > 2 && !variant;
-    const bool pose_only = (flags & RELPOSE_FWD_POSE_OUTPUTS) != 0 && !variant;
+    const bool pose_only = ((flags & RELPOSE_FWD_POSE_OUTPUTS) != 0 && !variant) || sampled;
     Plan* plan = nullptr;
     RelposeSCNet::SelfState commit;          // what the workspace holds once this forward is through
     const bool zt_on = g_rp_tune[RELPOSE_TUNE_ZERO_TILES] != 1;
@@ -3938,7 +4061,10 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
     // the snapshots the workspace holds after this forward: a cached forward stores none and carries the record on, a tagged forward that
     // computes the self streams stores those of the skip heads it launches
     commit.snap_heads = plan->self_cached ? prev.snap_heads : (self_tag != 0 ? (pose_only ? 6 : 7) : 0);
+    // ... and the snapshot rows of the 1x1 heads: the sampled tail stores none (whatever rows an earlier tag left are not this tag's)
+    commit.heads_snap = plan->self_cached ? prev.heads_snap : (sampled ? 0 : commit.snap_heads);
     net->last_n = n;
+    net->last_tail = sampled ? 1 : 0;
     // two-stream mode: the HBM-bound head (resize_in, conv1) and tail (heads, resize_out) run on tail_stream, the MFMA-bound middle on `stream`
     const bool two = tail_stream != stream;
     hipStream_t s = (two && plan->head_count > 0) ? (hipStream_t)tail_stream : (hipStream_t)stream;
@@ -4156,6 +4282,16 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
             mark(2);
             hipLaunchKernelGGL(bcast_warped_kernel, dim3(2048), dim3(256), 0, s, act + B.off * n, n, B.H * B.H, B.C, B.C / 6, ssp + B.ss_off * G, G);
             mark(-2);
+        } else if (op.type == OP_HEADS && sampled) {
+            SampledDesc sd;
+            sd.d2 = act + net->bufs["D2"].off * n; sd.a1 = act + net->bufs["A1"].off * n;
+            sd.ss_d2 = ssp + net->bufs["D2"].ss_off * G; sd.ss_a1 = ssp + net->bufs["A1"].ss_off * G;
+            sd.w = net->d_w + net->wh_off; sd.bias = net->d_w + net->bh_off; sd.out = out;
+            sd.pts = args->sample_pts; sd.npts = args->sample_npts; sd.npts_max = args->sample_npts_max;
+            sd.cf = net->cf; sd.use_tanh = net->use_tanh; sd.H = H; sd.W = W;
+            mark(1);
+            hipLaunchKernelGGL(heads_sampled_kernel, dim3((unsigned)((args->sample_npts_max + 3) / 4), (unsigned)n), dim3(256), 0, s, sd);
+            mark(-1);
         } else if (op.type == OP_HEADS) {
             HeadsDesc hd;
             hd.d2 = act + net->bufs["D2"].off * n; hd.a1 = act + net->bufs["A1"].off * n;
@@ -4163,6 +4299,14 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
             hd.w = net->d_w + net->wh_off; hd.bias = net->d_w + net->bh_off; hd.out = act + net->bufs["OUT"].off * n;
             hd.n = n; hd.S = net->S; hd.cf = net->cf; hd.use_tanh = net->use_tanh;
             hd.snap_mode = plan->snap_mode; hd.snap = (float*)(ws + o.snap) + plan->heads_snap_off; hd.snap_heads = plan->snap_heads;
+            if (hd.snap_mode == 2) {
+                // the rows the filling forward really stored: a pose-outputs fill left no rgb row (the kernel computes that head's skip line),
+                // a sampled fill none at all -- the kernel then runs as in a plain forward: the skip lines of rgb, n and d from A1 (the self
+                // blocks of A1 and their scale / shift stay in the workspace across self-cached levels: conv1 writes the warped blocks only and
+                // the A1 finalize keeps the even 32-channel blocks, skip_blk), nothing stored; the same bits either way
+                hd.snap_heads &= prev.heads_snap | (plan->pose_only ? 1 : 0);
+                if ((hd.snap_heads & 6) != 6) { hd.snap_mode = 0; hd.snap_heads = 7; }
+            }
             mark(1);
             const dim3 hg((unsigned)((size_t)n * RS * RS / 256));
             // RELPOSE_TUNE_HEADS_KERNEL: 0 = the streamed kernel, 1 = the lane-per-pixel kernel (the same bits; tests/test_gpu_heads_stream.py)
@@ -4216,10 +4360,12 @@ int relpose_scnet_forward_ex(RelposeSCNet* net, const RelposeForwardArgs* args) 
             mark(-2);
         }
     }
-    mark(3);
-    hipLaunchKernelGGL(resize_out_kernel, dim3(4096), dim3(256), net->cf <= RO_MAXC ? (size_t)4 * 2 * RO_MAXW * net->cf * sizeof(float) : 0, s,
-                       act + net->bufs["OUT"].off * n, out, n, net->cf, H, W);
-    mark(-3);
+    if (!sampled) {                  // (the sampled tail has written its elements of `out` itself)
+        mark(3);
+        hipLaunchKernelGGL(resize_out_kernel, dim3(4096), dim3(256), net->cf <= RO_MAXC ? (size_t)4 * 2 * RO_MAXW * net->cf * sizeof(float) : 0, s,
+                           act + net->bufs["OUT"].off * n, out, n, net->cf, H, W);
+        mark(-3);
+    }
     RP_CHECK_LAUNCH();
     {   // everything is enqueued: the workspace now holds (stream-ordered) the self-view streams of `self_tag`
         net->self_state[workspace] = commit;
@@ -4240,14 +4386,17 @@ int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n, int32_t flags, int32_t
     if (!net || !net->finalized || !macs_out || n <= 0 || (n & 1)) return RELPOSE_EINVAL;
     if (net->variant()) { flags = 0; self_cached = 0; }          // (constructor variants run the plain plan whatever the flags)
     const bool zero_warp = (flags & RELPOSE_FWD_ZERO_WARP) && n > 2 && !self_cached;
-    const bool pose_only = (flags & RELPOSE_FWD_POSE_OUTPUTS) != 0;
+    const bool sampled = (flags & RELPOSE_FWD_SAMPLED_OUTPUTS) != 0;
+    const bool pose_only = (flags & RELPOSE_FWD_POSE_OUTPUTS) != 0 || sampled;
     Plan dry;
     Builder B; B.net = net; B.n = n; B.G = n / 2; B.act = nullptr; B.ss = nullptr; B.splitk = nullptr; B.statp = nullptr; B.plan = &dry;
     B.zero_warp = zero_warp; B.pose_only = pose_only; B.self_cached = self_cached != 0;
     B.snapbuf = (float*)(uintptr_t)4096;       // (never dereferenced: makes the builder record ConvDesc::snap_mode in the dry run)
     B.snap_mode = self_cached ? 2 : 1; dry.snap_mode = B.snap_mode;
     // self_cached 2 = cached behind a pose-outputs fill: no rgb snapshots, the rgb head's skip halves are computed (deconv3rgb, deconv2rgb, heads)
-    const int snap_heads = self_cached == 2 ? 6 : 7;
+    // self_cached 3 = cached behind a sampled-outputs fill: as 2, and no snapshot rows of the 1x1 heads either (their skip lines are computed)
+    const int snap_heads = (self_cached == 2 || self_cached == 3) ? 6 : 7;
+    const int heads_snap = self_cached == 3 ? 0 : snap_heads;
     B.snap_heads = snap_heads; dry.snap_heads = snap_heads;
     build_plan(net, n, B);
     if (B.rc) return B.rc;
@@ -4275,14 +4424,14 @@ int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n, int32_t flags, int32_t
             const double blk = 224.0 * 224 * 32 * (36 + 36 + 18);
             const double self_imgs = self_cached ? 0 : n, warp_imgs = zero_warp ? 2 : n;
             macs += blk * (self_imgs + warp_imgs);
-        } else if (op.type == OP_HEADS) {
+        } else if (op.type == OP_HEADS && !sampled) {
             // 1x1 heads: rgb / n / d read cat(D2 32, A1 skip 32), s / f read 64 channels of D2; a self-cached forward takes the skip halves' sums
             // from the snapshot; the pose-outputs plan skips the rgb and semantic heads
             const double px = (double)n * 224 * 224;
             const int hc[5] = {3, 3, 1, net->S, 32};
             for (int m = 0; m < 5; ++m) {
                 if (pose_only && (m == 0 || m == 3)) continue;
-                const int cin = (m < 3 && self_cached && ((snap_heads >> m) & 1)) ? 32 : 64;
+                const int cin = (m < 3 && self_cached && ((heads_snap >> m) & 1)) ? 32 : 64;
                 macs += px * cin * hc[m];
             }
         }
@@ -4290,6 +4439,8 @@ int relpose_scnet_plan_macs(RelposeSCNet* net, int32_t n, int32_t flags, int32_t
     *macs_out = macs;
     return 0;
 }
+
+int relpose_scnet_last_tail(RelposeSCNet* net) { return net ? net->last_tail : RELPOSE_EINVAL; }
 
 // Which kernel the plain plan of n images runs `layer` on under the current precision and tuning knobs: 1 = deconv_strip_kernel as a
 // split-K launch, 2 = deconv_strip_kernel unsplit (direct stores, fused BatchNorm records), 0 = any other kernel, < 0 = error (unknown

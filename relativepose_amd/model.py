@@ -174,9 +174,9 @@ class SCNet(torch.nn.Module):
         cls._tag_counter += 1
         return cls._tag_counter
 
-    FLAG_ZERO_WARP, FLAG_POSE_OUTPUTS, FLAG_NEW_WORKSPACE = 1, 2, 4       # RELPOSE_FWD_* (include/relpose.h)
+    FLAG_ZERO_WARP, FLAG_POSE_OUTPUTS, FLAG_NEW_WORKSPACE, FLAG_SAMPLED_OUTPUTS = 1, 2, 4, 32       # RELPOSE_FWD_* (include/relpose.h)
 
-    def forward(self, x, out=None, tail_stream=None, ws_key=None, zero_warp=False, outputs="all", self_tag=0):
+    def forward(self, x, out=None, tail_stream=None, ws_key=None, zero_warp=False, outputs="all", self_tag=0, sample_pts=None, sample_npts=None):
         """tail_stream (a torch stream; not part of the reference interface): run the HBM-bound tail of the forward (heads + final
         resize) there, behind the convolutions on the current stream (RelposeForwardArgs::tail_stream) -- `out` is then valid on tail_stream only.
         ws_key: name of the workspace to use (forwards that may overlap need different workspaces; default: one per stream).
@@ -190,11 +190,22 @@ class SCNet(torch.nn.Module):
         pair's recurrence, evaluation.py:217-242): a forward that finds the previous forward of its workspace carried the same tag reuses
         that forward's self-view encoder streams (RelposeForwardArgs::self_tag; bitwise the same output).  0 = always recompute.
         The outputs of the forward that filled the cache do not matter: an "all" forward behind "pose" forwards of its tag is cached too
-        (it computes the rgb head's skip halves itself, the only part no "pose" forward leaves behind)."""
-        flags = (self.FLAG_ZERO_WARP if zero_warp else 0) | {"all": 0, "pose": self.FLAG_POSE_OUTPUTS}[outputs]
-        return self.forward_flags(x, out, flags, self_tag, tail_stream, ws_key)
+        (it computes the rgb head's skip halves itself, the only part no "pose" forward leaves behind).
+        outputs="samples" (RELPOSE_FWD_SAMPLED_OUTPUTS) with sample_pts [n, N, 2] float64 and sample_npts [n] int32 on the device: the "pose"
+        forward for a caller that only samples `out` at those keypoints (util.sample_primitives_dev with the same pts / npts) -- the dense
+        1x1 heads and the output resize are replaced by one kernel that writes exactly the elements the sampler loads, bitwise the "pose"
+        values; every other element of `out` is unspecified (it keeps what it held).  A variant net runs its plain dense forward."""
+        flags = (self.FLAG_ZERO_WARP if zero_warp else 0) | {"all": 0, "pose": self.FLAG_POSE_OUTPUTS, "samples": self.FLAG_SAMPLED_OUTPUTS}[outputs]
+        if outputs == "samples" and (sample_pts is None or sample_npts is None):
+            raise ValueError("outputs='samples' needs sample_pts and sample_npts")
+        return self.forward_flags(x, out, flags, self_tag, tail_stream, ws_key, sample_pts if outputs == "samples" else None, sample_npts)
 
-    def forward_flags(self, x, out=None, flags=0, self_tag=0, tail_stream=None, ws_key=None):
+    def last_tail(self):
+        """Which tail the last forward ran (relpose_scnet_last_tail): "dense" (1x1 heads + output resize) or "sampled"; None before any."""
+        r = int(_lib.lib().relpose_scnet_last_tail(self._h))
+        return {0: "dense", 1: "sampled"}.get(r)
+
+    def forward_flags(self, x, out=None, flags=0, self_tag=0, tail_stream=None, ws_key=None, sample_pts=None, sample_npts=None):
         """The forward as the C ABI sees it (relpose_scnet_forward_ex): `flags` = RELPOSE_FWD_* bits, `tail_stream` a torch stream, a raw
         HIP stream handle (int) or None.  `forward` and torch.ops.relpose.scnet_forward both end here."""
         import torch
@@ -223,7 +234,17 @@ class SCNet(torch.nn.Module):
             assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, self.out_channels, H, W)
         a = _lib.ForwardArgs()
         a.struct_size = C.sizeof(_lib.ForwardArgs)
-        a.flags = int(flags) & 7
+        a.flags = int(flags) & (7 | self.FLAG_SAMPLED_OUTPUTS)
+        if a.flags & self.FLAG_SAMPLED_OUTPUTS:
+            if sample_pts is None or sample_npts is None:
+                raise ValueError("RELPOSE_FWD_SAMPLED_OUTPUTS needs sample_pts and sample_npts")
+            assert sample_pts.is_cuda and sample_pts.dtype == torch.float64 and sample_pts.is_contiguous() and sample_pts.dim() == 3
+            assert tuple(sample_pts.shape) == (n, sample_pts.shape[1], 2) and sample_pts.shape[1] > 0
+            assert sample_npts.is_cuda and sample_npts.dtype == torch.int32 and sample_npts.is_contiguous() and tuple(sample_npts.shape) == (n,)
+            a.sample_pts, a.sample_npts, a.sample_npts_max = sample_pts.data_ptr(), sample_npts.data_ptr(), int(sample_pts.shape[1])
+            if tail_stream is not None:                    # (the sampled tail reads them there)
+                sample_pts.record_stream(tail_stream)
+                sample_npts.record_stream(tail_stream)
         a.x, a.out = x.data_ptr(), out.data_ptr()
         a.n_images, a.H, a.W = n, H, W
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()

@@ -24,7 +24,8 @@ class RelativePosePipeline:
     _net_streams = None
 
     def __init__(self, net, dataset="suncg", mask_method="second", sigmas=None, alter_steps=3, completion=1, max_edges=0, compose=0, outputs="all",
-                 self_stream_cache=True, tail_overlap=True, net_priority=None, loop_fit_cluster=1, keypoints="given", level_outputs="last"):
+                 self_stream_cache=True, tail_overlap=True, net_priority=None, loop_fit_cluster=1, keypoints="given", level_outputs="last",
+                 sampled_levels=True):
         self.net = net
         # "given": prepare(pts, ptw) fixes the keypoints of every view for all levels.  "reference": prepare(sift=...) takes the views' SIFT
         # detections (panorama coordinates, rputil.map_detections) and every level derives its keypoints from its own feature maps, as
@@ -47,6 +48,12 @@ class RelativePosePipeline:
         if level_outputs not in ("last", "every"):
             raise ValueError("level_outputs must be 'last' or 'every'")
         self.level_outputs = level_outputs
+        # With keypoints="given" the only reader of a pose-outputs level's st["f"] is util.sample_primitives_dev at the prepared keypoints: those
+        # levels then ask SCNet for outputs="samples" -- the same plan up to deconv2, and in place of the dense 1x1 heads and the output resize
+        # one kernel that writes just the elements the sampler loads, bit for bit the dense values (poses, status and the final st["f"] are
+        # unchanged).  False: the dense pose-outputs levels (A/B switch).  keypoints="reference" derives its keypoints from the dense
+        # feature maps and is not affected.
+        self.sampled_levels = bool(sampled_levels)
         self.dataset = dataset
         self.mask_method = mask_method
         self.alter_steps = alter_steps
@@ -387,9 +394,12 @@ class RelativePosePipeline:
         self._chain_nets = False
         return results
 
-    def _outputs_at(self, step, keep=None):
-        """forward(outputs=...) of level `step`: level_outputs="last" asks the levels before the last for the pose outputs only."""
+    def _outputs_at(self, step, keep=None, st=None):
+        """forward(outputs=...) of level `step`: level_outputs="last" asks the levels before the last for the pose outputs only -- and, when
+        the prepared keypoints of `st` are all that reads them (keypoints="given", sampled_levels), only at those keypoints."""
         if self.outputs == "all" and self.level_outputs == "last" and keep is None and step < self.alter_steps - 1 and not self.net.is_variant:
+            if self.sampled_levels and self.keypoints == "given" and st is not None and st["N"] > 0 and st["h"] * 4 == st["x"].shape[3]:
+                return "samples"
             return "pose"
         return self.outputs
 
@@ -435,17 +445,19 @@ class RelativePosePipeline:
                     # forwards need separate workspaces: one per stream (= per in-flight slot).
                     f = st["f"]
                     with torch.cuda.stream(ns):
-                        self.net.forward(x, out=f, tail_stream=ms, ws_key=ms.cuda_stream, zero_warp=(step == 0), outputs=self._outputs_at(step),
-                                         self_tag=st["self_tag"])
+                        self.net.forward(x, out=f, tail_stream=ms, ws_key=ms.cuda_stream, zero_warp=(step == 0), outputs=self._outputs_at(step, None, st),
+                                         self_tag=st["self_tag"], sample_pts=st.get("pts"), sample_npts=st.get("npts"))
                 else:
                     with torch.cuda.stream(ns):
-                        f = self.net.forward(x, out=st["f"], zero_warp=(step == 0), outputs=self._outputs_at(step), self_tag=st["self_tag"])
+                        f = self.net.forward(x, out=st["f"], zero_warp=(step == 0), outputs=self._outputs_at(step, None, st), self_tag=st["self_tag"],
+                                             sample_pts=st.get("pts"), sample_npts=st.get("npts"))
                         done = torch.cuda.Event()
                         done.record()
                     ms.wait_event(done)
                 yield                                            # one yield per level: the other batches enqueue theirs
             else:
-                f = self.net.forward(x, out=st["f"], zero_warp=(step == 0), outputs=self._outputs_at(step), self_tag=st["self_tag"])
+                f = self.net.forward(x, out=st["f"], zero_warp=(step == 0), outputs=self._outputs_at(step, None, st), self_tag=st["self_tag"],
+                                             sample_pts=st.get("pts"), sample_npts=st.get("npts"))
             kpts, knpts, w_s, w_t, ns, nt = self._level_keypoints(st, f, step)
             pc, nn, ft = util.sample_primitives_dev(f, self.feat_off, st["norm"], st["depth"], kpts, knpts,
                                                     self.mask_method, self.dataset, self.compose)
@@ -478,7 +490,8 @@ class RelativePosePipeline:
             # level 0 starts from the identity: util.warping returns zeros (util.py:95-96) for every image, which SCNet can exploit
             # (the batch's preallocated output buffer, unless the caller keeps every level's output: `keep` entries must not alias)
             f = self.net.forward(x, out=st["f"] if keep is None else None, zero_warp=(step == 0 and R_forced is None),
-                                 outputs=self._outputs_at(step, keep), self_tag=st["self_tag"])
+                                 outputs=self._outputs_at(step, keep, st), self_tag=st["self_tag"], sample_pts=st.get("pts"),
+                                 sample_npts=st.get("npts"))
             kpts, knpts, w_s, w_t, ns, nt = self._level_keypoints(st, f, step)
             pc, nn, ft = util.sample_primitives_dev(f, self.feat_off, st["norm"], st["depth"], kpts, knpts,
                                                     self.mask_method, self.dataset, self.compose)
