@@ -1228,6 +1228,93 @@ typedef struct RelposeMeshFilterArgs {
 size_t relpose_mesh_filter_workspace_bytes(int32_t n_scenes, int32_t cap, int32_t cap_tri);
 int relpose_mesh_filter(const RelposeMeshFilterArgs* args);
 
+/* -------------------------------------------------------------------- decimation of triangle meshes by vertex clustering
+ * relpose_mesh_decimate merges the vertices of n_scenes indexed triangle meshes in relpose_tsdf_mesh's layout that fall into one cell of a
+ * regular grid, and rewrites the triangles.  The contract is the project's own (tests/decimate_model.py restates it in numpy,
+ * on whole arrays and as plain loops).  Every input and output is device memory unless it says host.
+ *   scene            relpose_mesh_components' rule: nv = min(max(n_points, 0), cap) vertices and nt = min(max(n_triangles, 0), cap_tri) rows.
+ *                    A row < nt with an index outside [0, nv) is bad: it is dropped and counted in bad_triangles.
+ *   cells            origin_host [S, 3] f64 (HOST), cell f64, gx, gy, gz.  For vertex v and axis a: u_a = (p_a - origin_a) / cell, each
+ *                    operation its own f64 rounding.  v is INSIDE iff all three u_a are finite and 0 <= floor(u_a) < g_a; its cell is
+ *                    (floor(u_x), floor(u_y), floor(u_z)).  A vertex that is not inside is dropped (vertex_map = -1), and every good triangle
+ *                    that names a dropped vertex is dropped too and counted in outside_triangles.
+ *   clusters         all inside vertices of one cell form one cluster, whether a triangle uses them or not: the clusters do not depend on
+ *                    the triangle list.  A cluster's representative is its smallest vertex index; clusters are numbered 0, 1, ... in
+ *                    ascending order of their representative.  vertex_map [S, cap] i32: old index -> cluster, -1 for dropped vertices and
+ *                    rows >= nv; written whole.  out_n_points [S] i32: the true cluster count (<= cap).
+ *   attributes       integer sums over the n vertices of a cluster, so the order of the additions does not matter:
+ *                    position  q_a = llrint(u_a * 65536.0) summed as int64; out_p_a = origin_a + ((double)sum_a / (65536.0 * (double)n)) * cell,
+ *                              each operation rounded on its own;
+ *                    normal    llrint(n_a * 32768.0) per component summed as int64; a component that is not finite counts 0 (and so does one
+ *                              of magnitude above 65536.0, which no normal has: the conversion stays defined and the sum inside int64);
+ *                              with s the sums as doubles, len = sqrt((s_x s_x + s_y s_y) + s_z s_z) and the output is s / len, or
+ *                              (0, 0, 0) when len == 0;
+ *                    colour    (colors not NULL) llrint(min(max((double)c, 0.0), 1.0) * 65535.0) summed as int64, NaN counts 0; the output
+ *                              is (float)((double)sum / (65535.0 * (double)n));
+ *                    count     out_count [S, cap] i32 = n.
+ *                    Only rows below out_n_points of out_points, out_normals f64 [S, cap, 3], out_colors f32 [S, cap, 3] (NULL iff colors is)
+ *                    and out_count are written; out_valid [S, cap] u8 is written whole, 1 below out_n_points.
+ *   triangles        a good row (i, j, k) whose vertices are all inside becomes (m(i), m(j), m(k)), m = vertex_map.  It is DEGENERATE iff
+ *                    two of the three are equal: dropped and counted in degenerate_triangles.  With dedupe = 1 two surviving rows are
+ *                    DUPLICATES iff they are equal after rotating each so that its smallest index comes first; the rotation keeps the
+ *                    orientation, so (a, b, c) and (a, c, b) are not duplicates.  Of a set of duplicates the lowest row survives, the
+ *                    others are counted in duplicate_triangles.  Survivors keep their order and are written as remapped, UNROTATED indices
+ *                    to out_triangles [S, cap_tri, 3] i32 (only rows below out_n_triangles [S] i32, the true count, are written).
+ *                    tri_map [S, cap_tri] i32 (may be NULL; written whole): old row -> new row, or -1 bad, -2 outside, -3 degenerate,
+ *                    -4 duplicate, -5 row >= nt.  The four counters are i32 [S]; bad + outside + degenerate + duplicate + survivors = nt.
+ *   limits           n_scenes >= 1; 1 <= cap, 1 <= cap_tri; n_scenes * cap and n_scenes * cap_tri < 2^29; 1 <= gx, gy, gz <= 1024;
+ *                    n_scenes * gx * gy * gz < 2^27; cell finite and > 0; origin finite; dedupe 0 or 1.  Every output is a buffer of its own,
+ *                    none an input.
+ *   workspace        relpose_mesh_decimate_workspace_bytes(n_scenes, cap, cap_tri, gx, gy, gz) bytes (0 outside the limits), 256-byte
+ *                    aligned.
+ *   method           a dense table of gx gy gz entries per scene takes the atomic minimum of the vertex indices of each cell; the
+ *                    representatives are flagged, scanned per scene and numbered; one pass adds each vertex's ten integers to its cluster's
+ *                    row, runs of equal clusters summed inside the wave first, then int64 atomic adds.  Duplicates need no sort: one
+ *                    open-addressing table keyed by the packed pair (a, b) of the rotated row gives the pair a slot, a second keyed by
+ *                    (slot, c) takes the atomic minimum of the row index; every probe loop is bounded by the table size (a power of two
+ *                    >= 2 cap_tri) and nothing waits on another thread.  Slot numbers depend on the order of insertion, the surviving row
+ *                    does not.
+ * Every output is bitwise repeatable and a scene does not depend on its batch.  Invalid arguments return RELPOSE_EINVAL before anything is
+ * enqueued or any output is touched.  The origins travel as kernel arguments: origin_host is the caller's again when the call returns, and
+ * the launches are only enqueued on `stream`. */
+typedef struct RelposeMeshDecimateArgs {
+    uint32_t struct_size;       /* sizeof(RelposeMeshDecimateArgs) as the caller compiled it */
+    int32_t n_scenes;
+    int32_t cap;
+    int32_t cap_tri;
+    int32_t gx;
+    int32_t gy;
+    int32_t gz;
+    int32_t dedupe;
+    const double* points;       /* [n_scenes, cap, 3] */
+    const double* normals;      /* [n_scenes, cap, 3] */
+    const float* colors;        /* [n_scenes, cap, 3] or NULL */
+    const int32_t* n_points;    /* [n_scenes] */
+    const int32_t* triangles;   /* [n_scenes, cap_tri, 3] */
+    const int32_t* n_triangles; /* [n_scenes] */
+    const double* origin_host;  /* HOST [n_scenes, 3] */
+    double cell;
+    double* out_points;
+    double* out_normals;
+    float* out_colors;
+    uint8_t* out_valid;
+    int32_t* out_n_points;
+    int32_t* out_count;
+    int32_t* out_triangles;
+    int32_t* out_n_triangles;
+    int32_t* vertex_map;
+    int32_t* tri_map;
+    int32_t* bad_triangles;
+    int32_t* outside_triangles;
+    int32_t* degenerate_triangles;
+    int32_t* duplicate_triangles;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} RelposeMeshDecimateArgs;
+size_t relpose_mesh_decimate_workspace_bytes(int32_t n_scenes, int32_t cap, int32_t cap_tri, int32_t gx, int32_t gy, int32_t gz);
+int relpose_mesh_decimate(const RelposeMeshDecimateArgs* args);
+
 /* Frame-to-model alignment: refine the poses of n_views depth panoramas against relpose_tsdf_fuse's volumes, so that each view's measured
  * points come to lie on the zero level of the volume it names (the KinectFusion tracking step, sampled at the measured points: no ray is
  * marched).  The contract is the project's own (tests/align_model.py restates it in numpy, the per-point rule on whole arrays

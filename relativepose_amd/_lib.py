@@ -242,6 +242,17 @@ class MeshFilterArgs(C.Structure):
                 ("workspace_bytes", c_size_t), ("stream", c_void_p)]
 
 
+class MeshDecimateArgs(C.Structure):
+    """RelposeMeshDecimateArgs (include/relpose.h): the argument block of relpose_mesh_decimate."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("cap", c_int), ("cap_tri", c_int), ("gx", c_int), ("gy", c_int), ("gz", c_int),
+                ("dedupe", c_int), ("points", c_void_p), ("normals", c_void_p), ("colors", c_void_p), ("n_points", c_void_p),
+                ("triangles", c_void_p), ("n_triangles", c_void_p), ("origin_host", c_void_p), ("cell", c_double), ("out_points", c_void_p),
+                ("out_normals", c_void_p), ("out_colors", c_void_p), ("out_valid", c_void_p), ("out_n_points", c_void_p), ("out_count", c_void_p),
+                ("out_triangles", c_void_p), ("out_n_triangles", c_void_p), ("vertex_map", c_void_p), ("tri_map", c_void_p),
+                ("bad_triangles", c_void_p), ("outside_triangles", c_void_p), ("degenerate_triangles", c_void_p),
+                ("duplicate_triangles", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
 class TsdfAlignArgs(C.Structure):
     """RelposeTsdfAlignArgs (include/relpose.h): the argument block of relpose_tsdf_align."""
     _fields_ = [("struct_size", C.c_uint32), ("n_scenes", c_int), ("n_views", c_int), ("h", c_int), ("dataset", c_int), ("nx", c_int),
@@ -348,6 +359,8 @@ SIGNATURES = {
     "relpose_mesh_components": (c_int, [C.POINTER(MeshComponentsArgs)]),
     "relpose_mesh_filter_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "relpose_mesh_filter": (c_int, [C.POINTER(MeshFilterArgs)]),
+    "relpose_mesh_decimate_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "relpose_mesh_decimate": (c_int, [C.POINTER(MeshDecimateArgs)]),
     "relpose_tsdf_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "relpose_tsdf_align": (c_int, [C.POINTER(TsdfAlignArgs)]),
     "relpose_tsdf_render_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

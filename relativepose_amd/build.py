@@ -29,6 +29,7 @@ SOURCES = [
     ("tsdf.hip", ["-ffp-contract=off"]),           # TSDF fusion: the integer volume and the surface must agree with tests/tsdf_model.py bit for bit
     ("mesh.hip", ["-ffp-contract=off"]),           # marching cubes: the vertices are tsdf.hip's surface bit for bit (tsdf_surf.h), the triangles tests/mesh_model.py's
     ("meshcc.hip", ["-ffp-contract=off"]),         # mesh components: labels, integer sums and the triangle areas must agree with tests/components_model.py bit for bit
+    ("meshdecim.hip", ["-ffp-contract=off"]),      # mesh decimation: cells, integer sums and the means must agree with tests/decimate_model.py bit for bit
     ("tsdfalign.hip", ["-ffp-contract=off"]),      # TSDF alignment: the integer sums and the stepped poses must agree with tests/align_model.py bit for bit
     ("tsdfrender.hip", ["-ffp-contract=off"]),     # TSDF rendering: every output must agree with tests/render_model.py bit for bit
     ("posesync.hip", ["-ffp-contract=off"]),       # pose synchronisation: every f64 operation rounds as tests/sync_model.py states it

@@ -25,6 +25,9 @@ unchanged" is realised by the build's own eval_pairs-style harness).
   fuse_views(mesh=True) / mesh_stats / mesh_summary
                           no counterpart: the fused volume as an indexed triangle mesh and what kind of surface it is (util.tsdf_mesh_dev,
                           DESIGN.md 4.18)
+  fuse_views(mesh=True, decimate=K) / decimate_mesh / mesh_decimate_summary
+                          no counterpart: the mesh decimated by vertex clustering on the volume's grid (util.mesh_decimate_dev /
+                          mesh_decimate_volume_dev)
   fuse_views(mesh=True, min_component=N) / mesh_component_stats / clean_mesh / mesh_clean_summary
                           no counterpart: the mesh's connected components and the mesh without the small ones (util.mesh_components_dev /
                           mesh_filter_dev / mesh_clean_dev)
@@ -297,14 +300,19 @@ def verify_summary(stats):
     return out
 
 
-def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, max_points=None, view_begin=None, mesh=False, min_component=None):
+def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, max_points=None, view_begin=None, mesh=False, min_component=None,
+               decimate=None):
     """Merge posed depth panoramas into one surface cloud per scene: depth [V,h,4h] f32 and rgb [V,3,h,4h] f32 (or None)
     CUDA tensors, R [V,4,4] host float64 world -> camera poses (the loaders' R), view_begin as util.tsdf_fuse_dev's (None: one scene).  The box
     is util.tsdf_bounds_dev's, the volume util.tsdf_fuse_dev's, the cloud util.tsdf_surface_dev's.
     -> {"points" [S,cap,3] f64, "normals", "colors" (or None), "valid" [S,cap] u8, "n_points" [S] i32, "origin", "dims", "voxel", "state"}.
     mesh=True: the same five tensors from util.tsdf_mesh_dev, and "triangles" [S,cap_tri,3] i32, "n_triangles" [S] i32.
     min_component=N (with mesh=True): the mesh without its connected components of fewer than N triangles and without unused vertices
-    (util.mesh_clean_dev), "vertex_map", and "components": mesh_clean_dev's description of the mesh before the cleaning."""
+    (util.mesh_clean_dev), "vertex_map", and "components": mesh_clean_dev's description of the mesh before the cleaning.
+    decimate=K (with mesh=True, an integer >= 1): the mesh decimated by vertex clustering on the volume's grid coarsened by K
+    (util.mesh_decimate_volume_dev), after the cleaning when both are given: its mesh tensors, "vertex_map", "tri_map", "count"
+    and the four counters replace the mesh's (the maps are relative to the mesh that was decimated), and "decimated_from": (n_points,
+    n_triangles) [S] i32 tensors of that mesh."""
     from . import util
     vb = np.array([0, int(depth.shape[0])], np.int32) if view_begin is None else view_begin
     origin, dims = util.tsdf_bounds_dev(depth, R, dataset, voxel, pad, vb)
@@ -315,9 +323,12 @@ def fuse_views(depth, rgb, R, dataset, voxel, trunc=None, pad=3, min_weight=1, m
         if min_component is not None:
             clean, comps = util.mesh_clean_dev(out, min_triangles=int(min_component))
             out.update(clean, components=comps)
+        if decimate is not None:
+            dec = util.mesh_decimate_volume_dev(out, state, int(decimate))
+            out.update(dec, decimated_from=(out["n_points"], out["n_triangles"]))
         return out
-    if min_component is not None:
-        raise ValueError("fuse_views: min_component applies to mesh=True")
+    if min_component is not None or decimate is not None:
+        raise ValueError("fuse_views: min_component and decimate apply to mesh=True")
     points, normals, colors, valid, n = util.tsdf_surface_dev(state, min_weight, max_points)
     return {"points": points, "normals": normals, "colors": colors, "valid": valid, "n_points": n, "origin": origin, "dims": dims,
             "voxel": float(voxel), "state": state}
@@ -451,6 +462,30 @@ def clean_mesh(mesh, min_component):
     clean, comps = util.mesh_clean_dev(mesh, min_triangles=int(min_component))
     removed = int(mesh["n_triangles"][0].item()) - int(clean["n_triangles"][0].item())
     return dict(mesh, **clean), mesh_component_stats(comps)[0], removed
+
+
+def decimate_mesh(mesh, factor):
+    """--mesh-decimate: -> (the mesh dict decimated on its volume's grid coarsened by factor (util.mesh_decimate_volume_dev),
+    (triangles before, triangles after, dist, within)); scene 0 of a one-scene mesh of fuse_views(mesh=True).  dist: the median distance of
+    the mesh's vertices to the vertex that replaced them (through vertex_map, with torch operators); within: the share of the new vertices
+    with a vertex of the original surface cloud inside half a cell (one reconstruction_scores call, which is one util.overlap_dev call)."""
+    import torch
+    from . import util
+    dec = util.mesh_decimate_volume_dev(mesh, mesh["state"], int(factor))
+    nv = min(max(int(mesh["n_points"][0].item()), 0), int(mesh["points"].shape[1]))
+    vm = dec["vertex_map"][0, :nv].long()
+    moved = (mesh["points"][0, :nv][vm >= 0] - dec["points"][0][vm[vm >= 0]]).norm(dim=1)
+    dist = float(moved.median().item()) if moved.numel() else float("nan")
+    within, _ = reconstruction_scores(dec, {"points": mesh["points"], "valid": mesh["valid"]}, 0.5 * dec["decimate_cell"])
+    return dict(mesh, **dec), (int(mesh["n_triangles"][0].item()), int(dec["n_triangles"][0].item()), dist, float(within[0]))
+
+
+def mesh_decimate_summary(parts):
+    """the CLI's medians of decimate_mesh's tuples over scenes"""
+    med = lambda v: float(np.nanmedian(v)) if len(v) and not np.all(np.isnan(v)) else float("nan")
+    share = [p[1] / p[0] if p[0] else float("nan") for p in parts]
+    return {"mesh_decimated_triangles_median": med([float(p[1]) for p in parts]), "mesh_decimated_share_median": med(share),
+            "mesh_decimated_dist_median": med([p[2] for p in parts]), "mesh_decimated_within_median": med([p[3] for p in parts])}
 
 
 def mesh_summary(stats):
@@ -897,7 +932,7 @@ SCENE_BAD_ROT, SCENE_BAD_TRANS = 10.0, 0.3       # a pair estimate is wrong beyo
 
 
 def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, dataset=None, keypoints=200, seed=0, exp=None, mesh=False, refine=0,
-                    render=False, mesh_min_component=None, **sync):
+                    render=False, mesh_min_component=None, mesh_decimate=None, **sync):
     """Scenes of posed views -> estimated pairs -> synchronised absolute poses -> what they do to the reconstruction.
     scenes: synth.render_scene dicts; pipe_or_method: a RelativePosePipeline, or "fgs" / "gs" / "cgs" (then `dataset` names the scenes').
     Per scene: mine_pairs, the pair method on the mined pairs through evaluate_pairs / evaluate_fgs / _gs / _cgs as they are (verify and
@@ -912,6 +947,8 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
     <exp>.scene<k>.ply.  mesh=True (with fuse): 'mesh' = mesh_stats of the estimate's fusion, and <exp>.scene<k>.mesh.ply next to the cloud;
     mesh_min_component=N: of that mesh without its components of fewer than N triangles (the cloud stays), with 'mesh_components' and
     'mesh_removed_triangles'.
+    mesh_decimate=K: of that mesh (after the cleaning) decimated on the volume's grid coarsened by K (decimate_mesh), with
+    'mesh_decimated': (triangles before, after, dist, within).
     refine=rounds (with fuse): the largest component's synchronised poses are refined against the fused volume (refine_scene,
     re-gauged to the component's first view) before the final fusion, which then uses them; the record gains 'refine_rounds',
     'refine_err_rot' / 'refine_err_t' [2, views] (absolute_pose_errors before and after), 'refine_wall_median' [2] (the surface's median
@@ -1011,6 +1048,9 @@ def evaluate_scenes(pipe_or_method, scenes, device, verify=None, fuse=None, data
                 if mesh_min_component is not None:
                     est, rec['mesh_components'], rec['mesh_removed_triangles'] = clean_mesh(est, mesh_min_component)
                     n = int(est["n_points"][0].item())
+                if mesh_decimate is not None:
+                    est, rec['mesh_decimated'] = decimate_mesh(est, mesh_decimate)
+                    n = int(est["n_points"][0].item())
                 rec['mesh'] = mesh_stats(est)[0]
                 if exp is not None:
                     rec['mesh_ply'] = f"{exp}.scene{k}.mesh.ply"
@@ -1045,6 +1085,8 @@ def scenes_summary(recs):
     if recs and any('mesh_components' in r for r in recs):
         rr = [r for r in recs if 'mesh_components' in r]
         out.update(mesh_clean_summary([r['mesh_components'] for r in rr], [r['mesh_removed_triangles'] for r in rr]))
+    if recs and any('mesh_decimated' in r for r in recs):
+        out.update(mesh_decimate_summary([r['mesh_decimated'] for r in recs if 'mesh_decimated' in r]))
     return out
 
 
@@ -1378,6 +1420,12 @@ def _cli_parser_completion():
                     help="--mesh: drop the mesh's connected components of fewer than N triangles (vertex connectivity, DESIGN.md 4.21) and its "
                          "unused vertices before the mesh statistics and <exp>.scene<k>.mesh.ply; the JSON line gains mesh_components_median, "
                          "mesh_largest_share_median (both of the mesh as extracted) and mesh_removed_triangles_median.  The cloud is not touched")
+    ap.add_argument("--mesh-decimate", type=int, default=None, metavar="K",
+                    help="--mesh: decimate the mesh by vertex clustering on the volume's grid coarsened by K (cells of K^3 voxels, DESIGN.md "
+                         "4.22), after --mesh-min-component when both are given, before the mesh statistics and <exp>.scene<k>.mesh.ply; the "
+                         "JSON line gains mesh_decimated_triangles_median, mesh_decimated_share_median (triangles after / before), "
+                         "mesh_decimated_dist_median (how far a vertex moved) and mesh_decimated_within_median (new vertices within half a cell "
+                         "of the original surface cloud).  The cloud is not touched")
     ap.add_argument("--mesh", action="store_true",
                     help="--mine-pairs --fuse VOXEL / --reconstruct --fuse VOXEL: also extract each fused scene's triangle mesh (marching cubes, "
                          "DESIGN.md 4.18); the JSON line gains the medians of mesh_stats (triangles, area, border edges) and the number of "
@@ -1427,6 +1475,8 @@ def main(argv=None):
         raise SystemExit("--mesh applies to --mine-pairs --fuse VOXEL and to --reconstruct --fuse VOXEL")
     if args.mesh_min_component is not None and (not args.mesh or args.mesh_min_component < 1):
         raise SystemExit("--mesh-min-component N >= 1 applies to --mesh")
+    if args.mesh_decimate is not None and (not args.mesh or args.mesh_decimate < 1):
+        raise SystemExit("--mesh-decimate K >= 1 applies to --mesh")
 
     if args.render and (args.fuse is None or not (args.mine_pairs or args.reconstruct)):
         raise SystemExit("--render applies to --mine-pairs --fuse VOXEL and to --reconstruct --fuse VOXEL")
@@ -1462,7 +1512,7 @@ def main(argv=None):
         scenes = [synth.render_scene(args.seed + s, args.scene_views, ds) for s in range(args.scenes)]
         recs = evaluate_scenes(who, scenes, dev, verify=args.verify, fuse=args.fuse, dataset=ds, keypoints=args.keypoints, seed=args.seed,
                                exp=args.exp, mesh=args.mesh, refine=args.refine, render=args.render,
-                               mesh_min_component=args.mesh_min_component)
+                               mesh_min_component=args.mesh_min_component, mesh_decimate=args.mesh_decimate)
         torch.cuda.synchronize()
         line = {"reconstruct": True, "method": args.method, "dataset": ds, "scenes": args.scenes, "views": args.scene_views,
                 "seconds": time.perf_counter() - t0, "verify": args.verify, "fuse": args.fuse}
@@ -1486,7 +1536,7 @@ def main(argv=None):
         entries = []
         wall, fuse_points, plys = [], 0, []
         meshes, mesh_plys = [], []
-        mesh_comps, mesh_removed = [], []
+        mesh_comps, mesh_removed, mesh_decimated = [], [], []
         renders, render_npz = [], []
         t0 = time.perf_counter()
         for s in range(args.scenes):
@@ -1517,6 +1567,11 @@ def main(argv=None):
                         mesh_removed.append(removed)
                         n = int(surf["n_points"][0].item())
                         pts = surf["points"][0, :n].cpu().numpy()
+                    if args.mesh_decimate is not None:
+                        surf, part = decimate_mesh(surf, args.mesh_decimate)
+                        mesh_decimated.append(part)
+                        n = int(surf["n_points"][0].item())
+                        pts = surf["points"][0, :n].cpu().numpy()
                     meshes.append(mesh_stats(surf)[0])
                     if args.exp is not None:
                         mesh_plys.append(f"{args.exp}.scene{s}.mesh.ply")
@@ -1539,6 +1594,8 @@ def main(argv=None):
             line.update(mesh_summary(meshes), mesh_ply=mesh_plys)
         if args.mesh_min_component is not None:
             line.update(mesh_clean_summary(mesh_comps, mesh_removed))
+        if args.mesh_decimate is not None:
+            line.update(mesh_decimate_summary(mesh_decimated))
         if args.render:
             line.update(render_summary(renders, args.fuse), render_npz=render_npz)
         print(json.dumps(line), flush=True)

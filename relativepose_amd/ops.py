@@ -47,6 +47,7 @@ Operator                    replaces (reference file:line)
   tsdf_mesh                 no counterpart: tsdf_surface's cloud plus the triangles of a marching-cubes mesh over the same volume
   mesh_components, mesh_filter
                             no counterpart: the connected components of tsdf_mesh's meshes, and the mesh without the ones not kept
+  mesh_decimate             no counterpart: tsdf_mesh's meshes decimated by vertex clustering on a regular grid
   tsdf_fuse, tsdf_surface   no counterpart: posed depth panoramas merged into a TSDF volume and its surface cloud
   pose_sync                 no counterpart: the relative poses of a scene's pairs synchronised into one pose per view
   affinity_topk             rpmodule.py:342-379
@@ -137,6 +138,12 @@ _lib.define("mesh_components(Tensor points, Tensor n_points, Tensor triangles, T
 _lib.define("mesh_filter(Tensor points, Tensor normals, Tensor? colors, Tensor n_points, Tensor triangles, Tensor n_triangles, Tensor vertex_label, "
             "Tensor tri_label, Tensor keep, bool drop_unused=True, bool truncated=False) "
             "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+# a mesh, origin f64 [S,3] (read on the host), the cell and the grid -> util.DECIMATE_KEYS: tsdf_mesh's points, normals, colors (empty without
+# colors), valid, n_points, then count i32 [S,cap], triangles, n_triangles, vertex_map i32 [S,cap], tri_map i32 [S,cap_tri] and the counters of
+# bad, outside, degenerate and duplicate triangles i32 [S]
+_lib.define("mesh_decimate(Tensor points, Tensor normals, Tensor? colors, Tensor n_points, Tensor triangles, Tensor n_triangles, Tensor origin, "
+            "float cell, int gx, int gy, int gz, bool dedupe=True, bool truncated=False) "
+            "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 # the state of tsdf_fuse, depth f32 [V,h,4h], pose f64 [V,4,4] world -> camera, scene_of_view integer [V] (read on the host) -> pose f64 [V,4,4],
 # eig f64 [V,6], held i32 [V], sums i64 [V,32], rms f64 [V,2], trace_pose f64 [V,iters+1,4,4] and trace_sums i64 [V,iters+1,32] (empty without trace)
 _lib.define("tsdf_align(Tensor tsdf_sum, Tensor weight, Tensor origin, float voxel, Tensor depth, Tensor pose, Tensor scene_of_view, int dataset, "
@@ -345,6 +352,12 @@ def _mesh_filter(points, normals, colors, n_points, triangles, n_triangles, vert
             m["triangles"], m["n_triangles"], m["vertex_map"])
 
 
+def _mesh_decimate(points, normals, colors, n_points, triangles, n_triangles, origin, cell, gx, gy, gz, dedupe=True, truncated=False):
+    mesh = {"points": points, "normals": normals, "colors": colors, "n_points": n_points, "triangles": triangles, "n_triangles": n_triangles}
+    m = _util.mesh_decimate_dev(mesh, float(cell), origin.cpu().numpy(), (int(gx), int(gy), int(gz)), bool(dedupe), bool(truncated))
+    return tuple(points.new_empty(0, dtype=torch.float32) if m[k] is None else m[k] for k in _util.DECIMATE_KEYS)
+
+
 def _tsdf_align(tsdf_sum, weight, origin, voxel, depth, pose, scene_of_view, dataset, iters=12, eig_min=0.0043, stride=1, min_weight=1, trace=False):
     S, nz, ny, nx = tsdf_sum.shape
     st = {"tsdf_sum": tsdf_sum, "weight": weight, "origin": origin.cpu().numpy(), "dims": (nx, ny, nz), "voxel": float(voxel),
@@ -399,7 +412,7 @@ for _name, _fn in (("scnet_forward", _scnet_forward), ("scnet_forward_out", _scn
                    ("completion_loss", _completion_loss), ("contrast_loss", _contrast_loss), ("depth_normals", _depth_normals),
                    ("frames_to_pano", _frames_to_pano), ("overlap", _overlap), ("visibility", _visibility),
                    ("tsdf_fuse", _tsdf_fuse), ("tsdf_surface", _tsdf_surface), ("tsdf_mesh", _tsdf_mesh), ("mesh_components", _mesh_components),
-                   ("mesh_filter", _mesh_filter), ("tsdf_align", _tsdf_align), ("tsdf_render", _tsdf_render),
+                   ("mesh_filter", _mesh_filter), ("mesh_decimate", _mesh_decimate), ("tsdf_align", _tsdf_align), ("tsdf_render", _tsdf_render),
                    ("pose_sync", _pose_sync)):
     _lib.impl(_name, _fn, "CUDA")
 
@@ -568,6 +581,14 @@ def _m_mesh_filter(points, normals, colors, n_points, triangles, n_triangles, ve
             n(torch.uint8, S, cap), n(torch.int32, S), n(torch.int32, S, cap_tri, 3), n(torch.int32, S), n(torch.int32, S, cap))
 
 
+def _m_mesh_decimate(points, normals, colors, n_points, triangles, n_triangles, origin, cell, gx, gy, gz, dedupe=True, truncated=False):
+    S, cap, cap_tri = points.shape[0], points.shape[1], triangles.shape[1]
+    n = lambda dt, *s: points.new_empty(*s, dtype=dt)
+    return (n(torch.float64, S, cap, 3), n(torch.float64, S, cap, 3), n(torch.float32, 0) if colors is None else n(torch.float32, S, cap, 3),
+            n(torch.uint8, S, cap), n(torch.int32, S), n(torch.int32, S, cap), n(torch.int32, S, cap_tri, 3), n(torch.int32, S), n(torch.int32, S, cap),
+            n(torch.int32, S, cap_tri), n(torch.int32, S), n(torch.int32, S), n(torch.int32, S), n(torch.int32, S))
+
+
 def _m_tsdf_align(tsdf_sum, weight, origin, voxel, depth, pose, scene_of_view, dataset, iters=12, eig_min=0.0043, stride=1, min_weight=1, trace=False):
     V, E = depth.shape[0], int(iters) + 1
     n = lambda dt, *s: depth.new_empty(*s, dtype=dt)
@@ -610,11 +631,12 @@ for _name, _fn in (("scnet_forward", _m_scnet_forward), ("scnet_forward_out", _m
                    ("completion_loss", _m_completion_loss), ("contrast_loss", _m_contrast_loss), ("depth_normals", _m_depth_normals),
                    ("frames_to_pano", _m_frames_to_pano), ("overlap", _m_overlap), ("visibility", _m_visibility),
                    ("tsdf_fuse", _m_tsdf_fuse), ("tsdf_surface", _m_tsdf_surface), ("tsdf_mesh", _m_tsdf_mesh), ("mesh_components", _m_mesh_components),
-                   ("mesh_filter", _m_mesh_filter), ("tsdf_align", _m_tsdf_align), ("tsdf_render", _m_tsdf_render),
+                   ("mesh_filter", _m_mesh_filter), ("mesh_decimate", _m_mesh_decimate), ("tsdf_align", _m_tsdf_align), ("tsdf_render", _m_tsdf_render),
                    ("pose_sync", _m_pose_sync)):
     _lib.impl(_name, _fn, "Meta")
 
 OPS = ("scnet_forward", "scnet_forward_out", "apply_mask", "build_view", "warp", "warp_pairs_", "pano2pc", "pose_inverse", "sample_primitives",
        "keypoints_reference", "affinity_topk", "match_pairs", "sift_detect", "fast_global_registration", "global_registration", "colored_icp",
        "color_registration", "dense_nn", "descriptor_rank", "sift_describe", "sift_rank", "completion_loss", "contrast_loss", "depth_normals",
-       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "tsdf_mesh", "mesh_components", "mesh_filter", "tsdf_align", "tsdf_render", "pose_sync")
+       "frames_to_pano", "overlap", "visibility", "tsdf_fuse", "tsdf_surface", "tsdf_mesh", "mesh_components", "mesh_filter", "mesh_decimate", "tsdf_align", "tsdf_render",
+       "pose_sync")

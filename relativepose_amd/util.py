@@ -923,6 +923,94 @@ def mesh_clean_dev(mesh, min_triangles=None, min_area=None, largest=None, drop_u
     return mesh_filter_dev(mesh, comps, comps["keep"], drop_unused, truncated), comps
 
 
+DECIMATE_COUNTERS = ("bad_triangles", "outside_triangles", "degenerate_triangles", "duplicate_triangles")
+DECIMATE_KEYS = ("points", "normals", "colors", "valid", "n_points", "count", "triangles", "n_triangles", "vertex_map", "tri_map") + DECIMATE_COUNTERS
+
+
+def mesh_decimate_grid(mesh, cell):
+    """mesh_decimate_dev's default grid, with torch operators on the device: -> (origin [S,3] float64 host array: the per-axis minimum of each
+    scene's finite vertices (0 for a scene without one), dims (gx, gy, gz): the smallest grid of `cell` that covers the finite vertices of every
+    scene).  It is the vertices' own box, NOT the volume's: see mesh_decimate_volume_dev for the grid aligned with the TSDF."""
+    import torch
+    pts = mesh["points"]
+    S, cap = int(pts.shape[0]), int(pts.shape[1])
+    live = torch.arange(cap, device=pts.device)[None] < mesh["n_points"].clamp(0, cap)[:, None]
+    live = (live & torch.isfinite(pts).all(2))[:, :, None]
+    lo = torch.where(live, pts, torch.full_like(pts, float("inf"))).amin(1)
+    hi = torch.where(live, pts, torch.full_like(pts, float("-inf"))).amax(1)
+    none = ~torch.isfinite(lo)
+    lo, hi = torch.where(none, torch.zeros_like(lo), lo), torch.where(none, torch.zeros_like(hi), hi)
+    dims = (torch.floor((hi - lo) / float(cell)).amax(0) + 1).clamp(max=float(2 ** 30))      # (max - origin) / cell rounds as the kernel's u
+    return lo.cpu().numpy().astype(np.float64), tuple(int(v) for v in dims.tolist())
+
+
+def mesh_decimate_dev(mesh, cell, origin=None, dims=None, dedupe=True, truncated=False):
+    """relpose_mesh_decimate (include/relpose.h): tsdf_mesh_dev's / mesh_filter_dev's meshes (any dict with "points", "normals"
+    [S,cap,3] f64, "colors" [S,cap,3] f32 or None, "n_points" [S] i32, "triangles" [S,cap_tri,3] i32, "n_triangles" [S] i32 on the GPU)
+    decimated by vertex clustering: the vertices inside one cell of the grid (origin [S,3] host float64, dims (gx, gy, gz), edge `cell`) become
+    one vertex with their mean position, normalised mean normal and mean colour; vertices outside the grid are dropped; triangles are
+    remapped, the degenerate ones dropped and, with dedupe, of equal ones (up to rotation, not orientation) the lowest row kept.
+    origin / dims None: mesh_decimate_grid's, the smallest grid over the finite vertices with the origin at their per-axis minimum -- these are
+    NOT the volume's origin and dimensions, so the clusters are not aligned with the TSDF's voxels (mesh_decimate_volume_dev's are).
+    -> a mesh dict of tsdf_mesh_dev's keys with the same capacities (rows beyond the new counts are zero) plus "vertex_map" [S,cap] i32 (old
+    index -> new index or -1), "tri_map" [S,cap_tri] i32 (old row -> new row, or -1 bad, -2 outside, -3 degenerate, -4 duplicate, -5 beyond the
+    count), "count" [S,cap] i32 (vertices per new vertex), the four counters "bad_triangles", "outside_triangles", "degenerate_triangles",
+    "duplicate_triangles" [S] i32, and "decimate_origin", "decimate_dims", "decimate_cell".  Only enqueued on the current stream."""
+    import torch
+    _lib.require_gpu()
+    S, cap, cap_tri = _mesh_caps(mesh, "mesh_decimate_dev", truncated)
+    if not (np.isfinite(float(cell)) and float(cell) > 0.0):
+        raise ValueError("mesh_decimate_dev: cell must be finite and > 0")
+    if origin is None or dims is None:
+        o, d = mesh_decimate_grid(mesh, cell)
+        origin, dims = (o if origin is None else origin), (d if dims is None else dims)
+    origin = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, dtype=np.float64).reshape(-1, 3), (S, 3)))
+    gx, gy, gz = (int(v) for v in dims)
+    L = _lib.lib()
+    nbytes = L.relpose_mesh_decimate_workspace_bytes(S, cap, cap_tri, gx, gy, gz)
+    if nbytes == 0:
+        raise ValueError(f"mesh_decimate_dev: sizes outside relpose_mesh_decimate's limits (dims {gx} x {gy} x {gz}: each 1 .. 1024, "
+                         "S gx gy gz < 2^27)")
+    dev = mesh["points"].device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    col = mesh.get("colors")
+    src = {k: (None if mesh.get(k) is None else mesh[k].contiguous()) for k in ("points", "normals", "colors", "n_points", "triangles", "n_triangles")}
+    z = lambda dt, *shape: torch.zeros(*shape, dtype=dt, device=dev)
+    out = {"points": z(torch.float64, S, cap, 3), "normals": z(torch.float64, S, cap, 3), "colors": None if col is None else z(torch.float32, S, cap, 3),
+           "valid": z(torch.uint8, S, cap), "n_points": z(torch.int32, S), "count": z(torch.int32, S, cap), "triangles": z(torch.int32, S, cap_tri, 3),
+           "n_triangles": z(torch.int32, S), "vertex_map": z(torch.int32, S, cap), "tri_map": z(torch.int32, S, cap_tri)}
+    out.update({k: z(torch.int32, S) for k in DECIMATE_COUNTERS})
+    a = _lib.MeshDecimateArgs()
+    a.struct_size = _lib.C.sizeof(_lib.MeshDecimateArgs)
+    a.n_scenes, a.cap, a.cap_tri, a.gx, a.gy, a.gz, a.dedupe = S, cap, cap_tri, gx, gy, gz, int(bool(dedupe))
+    for k, v in src.items():
+        setattr(a, k, 0 if v is None else v.data_ptr())
+    a.origin_host, a.cell = origin.ctypes.data, float(cell)
+    for k in ("points", "normals", "colors", "valid", "n_points", "count", "triangles", "n_triangles"):
+        setattr(a, "out_" + k, 0 if out[k] is None else out[k].data_ptr())
+    for k in ("vertex_map", "tri_map") + DECIMATE_COUNTERS:
+        setattr(a, k, out[k].data_ptr())
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), nbytes, _lib.stream_ptr()
+    rc_ = L.relpose_mesh_decimate(_lib.C.byref(a))
+    if rc_ == -1:
+        raise ValueError("relpose_mesh_decimate: invalid arguments (sizes outside the limits, or an origin that is not finite)")
+    _lib.check(rc_, "relpose_mesh_decimate")
+    out.update(decimate_origin=origin, decimate_dims=(gx, gy, gz), decimate_cell=float(cell))
+    return out                                                 # (the workspace is freed in stream order: the launches are only enqueued)
+
+
+def mesh_decimate_volume_dev(mesh, state, factor, dedupe=True, truncated=False):
+    """mesh_decimate_dev on the grid of tsdf_fuse_dev's `state` coarsened by the integer `factor` >= 1: cell = factor * voxel, the volume's
+    origin, dims = ceil(n / factor) per axis.  The cells are unions of factor^3 voxels of the TSDF, so a cluster never straddles a coarse
+    voxel and meshes of volumes that share an origin decimate alike."""
+    factor = int(factor)
+    if factor < 1:
+        raise ValueError("mesh_decimate_volume_dev takes an integer factor >= 1")
+    _, nz, ny, nx = (int(v) for v in state["tsdf_sum"].shape)
+    dims = tuple(-(-n // factor) for n in (nx, ny, nz))
+    return mesh_decimate_dev(mesh, factor * float(state["voxel"]), state["origin"], dims, dedupe, truncated)
+
+
 def tsdf_align_dev(state, depth, R, scene_of_view=None, iters=12, eig_min=None, stride=1, trace=False, min_weight=1):
     """relpose_tsdf_align (include/relpose.h): refine the world -> camera poses R [V,4,4] (float64 host array or CUDA tensor)
     of the depth panoramas depth [V,h,4h] f32 against tsdf_fuse_dev's state, so that each view's measured points lie on the zero level of the
